@@ -13,6 +13,10 @@ Launch forms (both give the same ranks):
   * `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`   -- torchrun provides the environment.
 
 One JSON line on rank 0.
+  ms_per_step       wall time of one timed step (--steps of them, after --warmup untimed ones), max over ranks.
+  dumped_outputs    (--dump-outputs DIR) what rank 0's timed path returned in its last step, written as DIR/<name>.npy: `sr` (infer, epit: the SR
+                    patch batch), `loss` + `sr` (train: train_step's return), `sr_scene` (lft: the LFintegrate'd scene); a fixed seeded sample
+                    where the outputs exceed 60 MB.  Weights and inputs are seeded, so runs with the same arguments see the same inputs.
   roofline          the dominant kernel (per-view 3x3 64->64 conv, 77 % of DistgSSR FLOPs, fp32-MFMA-bound): `achieved` = the
                     flops the op EXECUTES on the matrix pipe per launch (Winograd F(4x4,3x3): 36 position-GEMMs of
                     [16 tiles x 64] x [64 x 64] per 8x32-pixel tile = 2.25/9 of the direct 2 x 576 x 64 x pixels of SURVEY 8d)
@@ -66,7 +70,13 @@ def parse():
     ap.add_argument("--workload", choices=["infer", "train", "epit", "lft"], default="infer",
                     help="infer = configs[1] (headline, default); train = configs[3]: DistgSSR x4 fp32 train step, batch 8 per GPU, RCCL bucket "
                          "all-reduce; epit = configs[2]; lft = configs[4] (full scene through LFdivide / LFintegrate, patches sharded)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step (rank 0's) as DIR/<name>.npy, float32, at most "
+                         "60 MB in all (a fixed seeded sample of a larger output); the inputs depend on the arguments only, so two builds compare output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -293,6 +303,33 @@ def _base_line(args, world, el, patches_per_step, metric, workload, extra_cfg):
             "config": dict({"workload": workload, "batch_per_gpu": patches_per_step}, **extra_cfg)}
 
 
+DUMP_CAP_BYTES = 60 * 10 ** 6
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: tensor} -> DIR/<name>.npy (float64 stays float64, everything else is written as float32), at most DUMP_CAP_BYTES in all.
+    An output larger than its share of the cap (shares by size) is written as a sample instead: the flattened output at the sorted, de-duplicated indices of
+    numpy PCG64 seed 0 draws -- the same positions in every run of the same shape.  Returns what was written, for the result line."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in host.values())
+    written = {}
+    for name, a in host.items():
+        rec = {"file": f"{name}.npy", "shape": list(a.shape), "dtype": str(a.dtype)}
+        share = DUMP_CAP_BYTES * a.nbytes // total if total > DUMP_CAP_BYTES else a.nbytes
+        if a.nbytes > share:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, size=share // a.itemsize))
+            a = a.reshape(-1)[idx]
+            rec["sample"] = {"elements": int(a.size), "of": int(np.prod(rec["shape"])), "indices": "sorted unique of default_rng(0).integers(0, size, n) over the flattened output"}
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        written[name] = rec
+    return {"dir": dirname, "arrays": written}
+
+
 def train_arithmetic(all_f32):
     """(dtype, per-operator arithmetic) of the DistgSSR training step under the library's arithmetic selection (lfsr_set_arithmetic): by default the EPI branch's
     forward, fuse.0's forward and fuse.0's data gradient run with fp32 operands carried as three exact bf16 terms; everything else is fp32 MFMA."""
@@ -327,7 +364,7 @@ def bench_train(args, rank, world, dev, dist):
     opt = torch.optim.AdamW(net.parameters(), lr=2e-4, weight_decay=1e-4, fused=True)   # (one multi-tensor launch per step instead of ~30 foreach launches)
     x = torch.from_numpy(synth_input((Bt, 1, A * H, A * W), seed=1 + rank)).to(dev)
     y = torch.from_numpy(synth_input((Bt, 1, A * H * S, A * W * S), seed=100 + rank)).to(dev)
-    el, (loss, _), seen = timed_loop(lambda: train_step(net, crit, opt, x, y), args, dev, dist)
+    el, (loss, out), seen = timed_loop(lambda: train_step(net, crit, opt, x, y), args, dev, dist)
     if rank == 0:
         line = base_line(args, world, el, Bt, "5x5 x4-SR LF patches/sec (32^2->128^2), DistgSSR training step (fwd+bwd+allreduce+AdamW)",
                          "configs[3]: DistgSSR 5x5 x4 training, batch 8 per GPU, data-parallel, one RCCL all-reduce of the flat gradient bucket",
@@ -335,6 +372,8 @@ def bench_train(args, rank, world, dev, dist):
         line["dtype"], line["config"]["gemm_arithmetic"] = train_arithmetic(args.arithmetic == "f32")
         line["loss"] = float(loss)
         line["model_tflops"] = 3 * FLOP_PER_PATCH["distgssr"] * world * Bt * args.steps / el / 1e12
+        if args.dump_outputs:
+            line["dumped_outputs"] = dump_outputs(args.dump_outputs, {"loss": loss, "sr": out})
         print(json.dumps(line), flush=True)
     finish(dist)
 
@@ -381,6 +420,8 @@ def bench_model(args, rank, world, dev, dist):
                    args.arithmetic == "f32" or (lab and os.environ.get("LFSR_UPTAIL", "")[:1] == "v")]
         line["dtype"] = "f32" if all(f32_sel) else "f32 (linear / FFN / tail GEMMs: fp32 operands as three exact bf16 terms on the bf16 MFMA pipe, fp32 accumulation; 3x3 convs and attention: fp32 MFMA)"
         line["config"]["gemm_arithmetic"] = {"rowgemm": "f32" if f32_sel[0] else "bf16x3", "ffn": "f32" if f32_sel[1] else "bf16x3", "up_tail": "f32" if f32_sel[2] else "bf16x3"}
+        if args.dump_outputs:
+            line["dumped_outputs"] = dump_outputs(args.dump_outputs, {"sr" if name == "epit" else "sr_scene": y})
         print(json.dumps(line), flush=True)
     finish(dist)
 
@@ -603,6 +644,7 @@ def bench_infer(args, rank, world, dev, dist):
     rt.profile(0)
     if rank == 0:
         assert torch.isfinite(y).all()
+        dumped = dump_outputs(args.dump_outputs, {"sr": y}) if args.dump_outputs else None
         # B = 32 forward == the same patches run one at a time (batch independence of the path; bit-equal expected)
         batch_split_max_abs_diff = None
         if not args.no_split_check:
@@ -686,6 +728,8 @@ def bench_infer(args, rank, world, dev, dist):
         line["kernel_ms_per_step"] = {k: v[0] / nb for k, v in prof_all.items()}
         line["kernel_ms_per_step_note"] = f"separate untimed pass of {nb} steps with events around every operator class"
         line["batch_split_max_abs_diff"] = batch_split_max_abs_diff
+        if dumped:
+            line["dumped_outputs"] = dumped
         if world == 1 and not args.no_other_workloads:
             del rt
             torch.cuda.empty_cache()

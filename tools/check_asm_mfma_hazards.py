@@ -6,7 +6,7 @@ other half of the pair.
 usage: python tools/check_asm_mfma_hazards.py [file.hip ...]   (default: rowgemm_b3.hip ffn_b3.hip up_tail.hip epi_b3.hip lnlin_b3.hip)"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = [d for d in os.listdir(ROOT) if d.endswith("_amd")][0] + "/csrc"
+CSRC = [d for d in sorted(os.listdir(ROOT)) if d.endswith("_amd") and os.path.isdir(os.path.join(ROOT, d, "csrc"))][0] + "/csrc"   # (lfsr_amd/ is the import alias, no sources)
 files = sys.argv[1:] or ["rowgemm_b3.hip", "ffn_b3.hip", "up_tail.hip", "epi_b3.hip", "lnlin_b3.hip"]
 NEED_BEFORE, NEED_AFTER = 2, 18
 
