@@ -130,6 +130,17 @@ int lfsr_epiconv_hv_fwd(const float* x, int x_stride, int x_choff, const float* 
                         float* tmp, float* y, int y_stride, int choff_h, int choff_v, int B, int A, int h, int w,
                         float slope, void* stream);
 
+/* DisentgBlock tail, DistgSSR.py:84-99 at A = 5 under the default arithmetic: the angular and both epipolar branches of x, the concat
+ * (spa | ang | epiH | epiV, 144 channels) and fuse.0 with its LeakyReLU, without the concat in memory: y (64 channels) = lrelu(fuse.0(concat)).
+ * spa: the SpaConv.2 output (64 channels).  Weights packed as lfsr_angconv_fwd (w_ang0, w_ang2), lfsr_epiconv_hv_fwd (w_epi0, w_epi2) and
+ * lfsr_pointwise_fwd (w_fuse0, cin 144) take them.  t_a (B*h*w*16), t_h, t_v (B*A*h*w*32 each) receive the stage-1 activations.  The result bits are those
+ * of lfsr_angconv_fwd + lfsr_epiconv_hv_fwd + lfsr_pointwise_fwd over a (B*A*A*h*w, 144) concat whenever that pointwise call runs the three-term bf16
+ * row-GEMM (M >= 2048).  LFSR_E_ARG: not covered (A != 5, h or w > 32, fp32 arithmetic or an fp32 lab selection, a tensor of 2^31 bytes or more). */
+int lfsr_distg_branch_tail_fwd(const float* x, int x_stride, int x_choff, const float* spa, int spa_stride, int spa_choff,
+                               const float* w_ang0, const float* w_ang2, const float* w_epi0, const float* w_epi2, const float* w_fuse0,
+                               float* t_a, float* t_h, float* t_v, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope,
+                               void* stream);
+
 /* init_conv, DistgSSR.py:22,32 fused with SAI2MacPI (DistgSSR.py:31): x (B,1,A*h,A*w) SAI mosaic NCHW,
  * w (64,1,3,3) raw PyTorch layout -> y VCL 64 channels. */
 int lfsr_initconv_fwd(const float* x, const float* w, float* y, int y_stride, int y_choff, int B, int A, int h, int wd,

@@ -38,6 +38,7 @@ SIGNATURES = {
     "lfsr_angconv_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
     "lfsr_epiconv_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
     "lfsr_epiconv_hv_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "lfsr_distg_branch_tail_fwd": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
     "lfsr_initconv_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_fold_head": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
     "lfsr_upsample_head_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
@@ -605,6 +606,20 @@ def epiconv_hv(x, w1p, w2p, B, A, h, w, slope, out, choff_h, choff_v):
     check(lib.lfsr_epiconv_hv_fwd(dev_ptr(x), x.shape[1], 0, dev_ptr(w1p), dev_ptr(w2p), dev_ptr(tmp), dev_ptr(out), out.shape[1], choff_h, choff_v,
                                   B, A, h, w, slope, stream_ptr()), "epiconv_hv_fwd")
     return out
+
+
+def distg_branch_tail(x, spa, w_ang0, w_ang2, w_epi0, w_epi2, w_fuse0, B, A, h, w, slope):
+    """DisentgBlock tail (lfsr_distg_branch_tail_fwd): lrelu(fuse.0(spa | ang | epiH | epiV)) of the block input x and the SpaConv.2 output spa, both VCL 64-ch.
+    Weights packed as angconv / epiconv_hv / pointwise take them.  Returns (y (B*A*A*h*w, 64), t_a, t_h, t_v)."""
+    lib = load()
+    y = torch.empty((x.shape[0], 64), dtype=torch.float32, device=x.device)
+    t_a = torch.empty((B * h * w, 16), dtype=torch.float32, device=x.device)
+    t_h = torch.empty((B * A * h * w, 32), dtype=torch.float32, device=x.device)
+    t_v = torch.empty((B * A * h * w, 32), dtype=torch.float32, device=x.device)
+    check(lib.lfsr_distg_branch_tail_fwd(dev_ptr(x), x.shape[1], 0, dev_ptr(spa), spa.shape[1], 0, dev_ptr(w_ang0), dev_ptr(w_ang2), dev_ptr(w_epi0),
+                                         dev_ptr(w_epi2), dev_ptr(w_fuse0), dev_ptr(t_a), dev_ptr(t_h), dev_ptr(t_v), dev_ptr(y), 64, 0, B, A, h, w, slope,
+                                         stream_ptr()), "distg_branch_tail_fwd")
+    return y, t_a, t_h, t_v
 
 
 def initconv(x, w, A):

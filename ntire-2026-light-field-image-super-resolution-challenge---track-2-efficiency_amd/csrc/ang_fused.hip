@@ -27,6 +27,8 @@ struct AngArgs {
   float slope;
 };
 
+// S2 = false: stage 1 only (T written, no W2 staging, no stage 2): the DistgSSR forward's tail kernel (distg_tail.hip) forms stage 2 itself
+template <bool S2>
 __global__ __launch_bounds__(512) void k_ang_fused(AngArgs p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int AA = p.A * p.A, HW = p.H * p.W, M = p.B * HW;
@@ -65,7 +67,7 @@ __global__ __launch_bounds__(512) void k_ang_fused(AngArgs p) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int idx = tid + q * 512;
-      w2v[q] = idx < AA * 64 ? reinterpret_cast<const float4*>(p.W2)[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+      w2v[q] = S2 && idx < AA * 64 ? reinterpret_cast<const float4*>(p.W2)[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     if (g0 < ngroups) load_row(g0, 0, fb[0]);
 #pragma unroll
@@ -76,7 +78,7 @@ __global__ __launch_bounds__(512) void k_ang_fused(AngArgs p) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int idx = tid + q * 512;
-      if (idx < AA * 64) reinterpret_cast<float4*>(sW2)[idx] = w2v[q];
+      if (S2 && idx < AA * 64) reinterpret_cast<float4*>(sW2)[idx] = w2v[q];
     }
   }
   __syncthreads();
@@ -126,6 +128,7 @@ __global__ __launch_bounds__(512) void k_ang_fused(AngArgs p) {
     const float4 a2 = *reinterpret_cast<const float4*>(st + i * TROW + 4 * kq);   // A operand: row i, k = 4 kq .. + 3
     if (ok) *reinterpret_cast<float4*>(p.T + (long long)m * 16 + 4 * kq) = a2;
     __builtin_amdgcn_wave_barrier();
+    if (!S2) continue;
     for (int view = 0; view < AA; ++view) {
       const float4 b = *reinterpret_cast<const float4*>(b2 + view * 256);
       f32x4a o = {0.f, 0.f, 0.f, 0.f};
@@ -156,14 +159,16 @@ size_t lfsr_ang_fused_smem(int A, int waves) {
 
 bool lfsr_ang_fused_ok(int A) { return A >= 1 && A <= 5 && lfsr_ang_fused_smem(A, 8) <= 160 * 1024; }
 
+// y = NULL: stage 1 only (t written, w2_packed unused)
 int lfsr_ang_fused_launch(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed, float* t, float* y,
                           int y_stride, int y_choff, int B, int A, int h, int w, float slope, hipStream_t st) {
-  if (!lfsr_ang_fused_ok(A)) return LFSR_E_ARG;
+  if (!lfsr_ang_fused_ok(A) || !t) return LFSR_E_ARG;
   static std::atomic<bool> attr_set[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
   if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ang_fused), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ang_fused<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ang_fused<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return LFSR_HIP_ERR(e);
     attr_set[dev] = true;
   }
@@ -174,7 +179,8 @@ int lfsr_ang_fused_launch(const float* x, int x_stride, int x_choff, const float
   const int waves = 8;
   long long grid = (ngroups + waves - 1) / waves;
   if (grid > 256) grid = 256;
-  hipLaunchKernelGGL(k_ang_fused, dim3((unsigned)grid), dim3(waves * 64), lfsr_ang_fused_smem(A, waves), st, p);
+  if (y) hipLaunchKernelGGL(k_ang_fused<true>, dim3((unsigned)grid), dim3(waves * 64), lfsr_ang_fused_smem(A, waves), st, p);
+  else hipLaunchKernelGGL(k_ang_fused<false>, dim3((unsigned)grid), dim3(waves * 64), lfsr_ang_fused_smem(A, waves), st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }

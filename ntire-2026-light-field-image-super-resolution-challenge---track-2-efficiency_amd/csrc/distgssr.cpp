@@ -247,19 +247,20 @@ int lfsr_distgssr_finalize(lfsr_distgssr* c, void* stream) {
   return LFSR_OK;
 }
 
-static void ws_layout(const lfsr_distgssr* c, int B, int h, int w, size_t off[8], size_t* total) {
+static void ws_layout(const lfsr_distgssr* c, int B, int h, int w, size_t off[9], size_t* total) {
   const size_t npix = (size_t)B * c->A * c->A * h * w;
   size_t o = 0;
   for (int i = 0; i < 5; ++i) { off[i] = o; o += align64(npix * 64); }   // pool[0..3], T
   off[5] = o; o += align64(npix * 144);                                   // CAT
   off[6] = o; o += align64((size_t)B * h * w * 16);                       // ang stage-1
-  off[7] = o; o += align64((size_t)B * c->A * h * w * 32);                // epi stage-1
+  off[7] = o; o += align64((size_t)B * c->A * h * w * 32);                // epi stage-1 (the horizontal pass's, t_H, on the fused tail's path)
+  off[8] = o; o += align64((size_t)B * c->A * h * w * 32);                // t_V (fused tail)
   *total = o;
 }
 
 size_t lfsr_distgssr_workspace_bytes(const lfsr_distgssr* c, int B, int h, int w) {
   if (!c || B <= 0 || h <= 0 || w <= 0) return 0;
-  size_t off[8], tot;
+  size_t off[9], tot;
   ws_layout(c, B, h, w, off, &tot);
   return tot * sizeof(float);
 }
@@ -268,7 +269,7 @@ int lfsr_distgssr_forward_taps(lfsr_distgssr* c, const float* x, float* out, int
                                size_t workspace_bytes, float* const* taps, void* stream) {
   if (!c || !x || !out || !workspace || B <= 0 || h <= 0 || w <= 0 || !c->finalized) return LFSR_E_ARG;
   if ((uintptr_t)workspace & 15) return LFSR_E_ARG;
-  size_t off[8], tot;
+  size_t off[9], tot;
   ws_layout(c, B, h, w, off, &tot);
   if (workspace_bytes < tot * sizeof(float)) return LFSR_E_WS;
   if ((long long)B * c->A * c->A * h * w * 160 * 4 >= (1LL << 30)) return LFSR_E_ARG;  // every activation tensor < 1 GiB (the F(4x4) conv kernel's offset range; 32-bit byte offsets everywhere): callers split the batch (capi.py)
@@ -278,8 +279,15 @@ int lfsr_distgssr_forward_taps(lfsr_distgssr* c, const float* x, float* out, int
   float* CAT = ws + off[5];
   float* A16 = ws + off[6];
   float* E32 = ws + off[7];
+  float* EV32 = ws + off[8];
   const int A = c->A, AA = A * A, nimg = B * AA;
   const float L = 0.1f;  // LeakyReLU(0.1), DistgSSR.py:80-101
+  // The block tail (AngConv.2, EPIConv.2 of both passes, the concat and fuse.0) as ONE kernel (distg_tail.hip) at angRes 5 under the default arithmetic: the
+  // 144-channel concat never goes through HBM.  Same bits as the three-kernel sequence below, which stays for lfsr_set_arithmetic(F32), A != 5, the LFSR_EPI /
+  // LFSR_ROWGEMM / LFSR_ANG lab overrides, inputs whose fuse.0 would not run the bf16 row-GEMM (fewer than 2048 pixels), block (0,0) when the concat tap
+  // is asked for, and LFSR_DISTG_TAIL=0 (same-process A/B)
+  const char* tsel = lfsr_sel("LFSR_DISTG_TAIL");
+  const bool tail_ok = !(tsel && tsel[0] == '0') && (long long)nimg * h * w >= 2048 && lfsr_distg_tail_ok(A, h, w, nullptr, 64, 0, E32, EV32);
   int rc;
 #define RC(call) do { rc = (call); if (rc) return rc; } while (0)
 #define PROF(cls, call)                                                              \
@@ -318,6 +326,20 @@ int lfsr_distgssr_forward_taps(lfsr_distgssr* c, const float* x, float* out, int
       std::string p = "disentg.Group." + std::to_string(g) + ".Block." + std::to_string(b) + ".";
       float* o = pick(F0, gin, cur);
       PROF(0, conv(cur, p + "SpaConv.0.weight", T, 64, 0, nullptr, L));
+      if (tail_ok && !(taps && taps[4] && g == 0 && b == 0)) {
+        // SpaConv.2 into o (free until fuse.2 writes the block output there), the stage-1 halves of the branches, then the fused tail into T
+        PROF(0, conv(T, p + "SpaConv.2.weight", o, 64, 0, nullptr, L));
+        hipStream_t st = lfsr_stream(stream);
+        PROF(1, lfsr_ang_fused_launch(cur, 64, 0, c->w(p + "AngConv.0.weight"), nullptr, A16, nullptr, 0, 0, B, A, h, w, L, st));
+        PROF(2, lfsr_epi_b3_launch(cur, 64, 0, c->w(p + "EPIConv.0.weight") + 25 * 32 * 64 + LFSR_EPI_WINO_FLOATS, nullptr, nullptr, 0, 0, 0, E32, EV32,
+                                   B, A, h, w, 3, L, st));
+        PROF(3, lfsr_distg_tail_launch(o, 64, 0, A16, E32, EV32, c->w(p + "AngConv.2.weight"), c->w(p + "EPIConv.2.weight") + 160 * 32,
+                                       c->w(p + "fuse.0.weight"), T, 64, 0, B, A, h, w, L, st));
+        PROF(0, conv(T, p + "fuse.2.weight", o, 64, 0, cur, 1.0f));
+        cur = o;
+        if (g == 0 && b == 0) RC(tap(1, cur, 64, 64));
+        continue;
+      }
       PROF(0, conv(T, p + "SpaConv.2.weight", CAT, 144, 0, nullptr, L));
       PROF(1, lfsr_angconv_fwd(cur, 64, 0, c->w(p + "AngConv.0.weight"), c->w(p + "AngConv.2.weight"), A16, CAT, 144, 64, B, A, h, w, L, stream));
       PROF(2, lfsr_epiconv_hv_fwd(cur, 64, 0, c->w(p + "EPIConv.0.weight"), c->w(p + "EPIConv.2.weight"), E32, CAT, 144, 80, 112, B, A, h, w, L, stream));

@@ -36,6 +36,7 @@ constexpr int EB_STAGE_BYTES = EB_STAGE_SLOTS * 16;         // 30720
 constexpr int EB_W2_SLOTS = 3 * 4 * 160;                    // [plane][k-group][n']
 constexpr int EB_W2_BYTES = EB_W2_SLOTS * 16;               // 30720
 constexpr int EB_SMEM = 4 * EB_STAGE_BYTES + EB_W2_BYTES;   // two views of stage-1 planes (two K steps each) + the stage-2 planes: 153600
+constexpr int EB_SMEM1 = 4 * EB_STAGE_BYTES;                // stage 1 only: 122880
 
 struct EpiB3Args {
   const float* X; int x_stride; int x_choff; int x_bytes;
@@ -95,6 +96,8 @@ __device__ __forceinline__ void eb_shift_add(f32x4e (&t)[2], const f32x4e (&z)[2
   }
 }
 
+// S2 = false: stage 1 only -- TH / TV written, no W2 staging and no stage 2 (the DistgSSR forward's tail kernel, distg_tail.hip, forms stage 2 itself)
+template <bool S2>
 __global__ __launch_bounds__(512) void k_epi_b3(EpiB3Args p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   unsigned char* const sW = smem_raw;                                   // [2 views][2 K steps][EB_STAGE_BYTES]
@@ -196,7 +199,7 @@ __global__ __launch_bounds__(512) void k_epi_b3(EpiB3Args p) {
   load_x(L, 0, rawA);
   load_x(L, 1, rawB);
   load_w(0);
-  {   // stage-2 weight planes: once per block
+  if (S2) {   // stage-2 weight planes: once per block
     uint4 w2r[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) { const int idx = tid + 512 * i; w2r[i] = idx < EB_W2_SLOTS ? p.W2p[idx] : make_uint4(0u, 0u, 0u, 0u); }
@@ -306,6 +309,12 @@ __global__ __launch_bounds__(512) void k_epi_b3(EpiB3Args p) {
           if (save && pos < L.len) *reinterpret_cast<f32x4e*>(tsave + (L.rowbase + (long long)pos * L.rowstep) * 32 + 16 * mt + 4 * g) = tv[mt][nt];
         }
       if (save) asm volatile("s_nop 1" : "+v"(tv[0][0]), "+v"(tv[0][1]), "+v"(tv[1][0]), "+v"(tv[1][1]));     // (same store-data hazard as below)
+    }
+    if (!S2) {
+      if (!more) break;
+      ++it;
+      L = Ln;
+      continue;
     }
     // ---- stage 2: y[n'][x] = lrelu(sum_k W2[n'][k] t[x][k]), K = 32 = one K step.  The lane (position, g) already HOLDS eight of its position's channels
     //      (16 mt + 4 g + r): they are its B operand as they stand once the pack stores W2's columns in that order (k slot 8 g + 4 mt + r <-> channel 16 mt + 4 g + r) ----
@@ -425,16 +434,18 @@ int lfsr_pack_epi_b3_batch(const LfsrPackDesc* table_dev, int n, hipStream_t st)
 int lfsr_epi_b3_launch(const float* x, int x_stride, int x_choff, const float* w1_planes, const float* w2_planes, float* y, int y_stride,
                        int choffH, int choffV, float* t_h, float* t_v, int B, int A, int h, int w, int which, float slope, hipStream_t st) {
   if (A != 5 || h > 32 || w > 32 || h <= 0 || w <= 0 || B <= 0) return LFSR_E_ARG;
+  if (!y && (which != 3 || !t_h || !t_v)) return LFSR_E_ARG;      // y = NULL: stage 1 of both passes only (t_h, t_v written; w2_planes unused)
   if ((x_stride | x_choff | y_stride | choffH | choffV) & 3) return LFSR_E_ARG;
   if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w1_planes | (uintptr_t)w2_planes | (uintptr_t)t_h | (uintptr_t)t_v) & 15) return LFSR_E_ARG;
-  if ((long long)B * A * A * h * w * x_stride * 4 >= (1LL << 31) || (long long)B * A * A * h * w * y_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
+  if ((long long)B * A * A * h * w * x_stride * 4 >= (1LL << 31) || (y && (long long)B * A * A * h * w * y_stride * 4 >= (1LL << 31))) return LFSR_E_ARG;   // 32-bit byte offsets
   if (!(slope >= 0.f && slope <= 1.f)) return LFSR_E_ARG;      // LeakyReLU as max(v, slope v)
   static std::atomic<bool> attr_set[64];
   static std::atomic<int> cus[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
   if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_b3), hipFuncAttributeMaxDynamicSharedMemorySize, EB_SMEM);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_b3<true>), hipFuncAttributeMaxDynamicSharedMemorySize, EB_SMEM);
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_b3<false>), hipFuncAttributeMaxDynamicSharedMemorySize, EB_SMEM1);
     if (e != hipSuccess) return LFSR_HIP_ERR(e);
     int v = 0;
     cus[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
@@ -444,7 +455,7 @@ int lfsr_epi_b3_launch(const float* x, int x_stride, int x_choff, const float* w
   p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.x_bytes = (int)((long long)B * A * A * h * w * x_stride * 4);
   p.W1p = reinterpret_cast<const uint4*>(w1_planes); p.W2p = reinterpret_cast<const uint4*>(w2_planes);
   p.Y = y; p.y_stride = y_stride; p.choffH = choffH; p.choffV = choffV; p.TH = t_h; p.TV = t_v;
-  p.y_bytes = (int)((long long)B * A * A * h * w * y_stride * 4);
+  p.y_bytes = y ? (int)((long long)B * A * A * h * w * y_stride * 4) : 0;
   p.B = B; p.H = h; p.W = w; p.slope = slope;
   p.tilesH = (which & 1) ? (B * A * h + EB_LINES - 1) / EB_LINES : 0;
   p.tilesV = (which & 2) ? (B * A * w + EB_LINES - 1) / EB_LINES : 0;
@@ -453,7 +464,8 @@ int lfsr_epi_b3_launch(const float* x, int x_stride, int x_choff, const float* w
   if (which == 3 && (A * h) % EB_LINES == 0 && (A * w) % EB_LINES == 0) { p.tpiH = A * h / EB_LINES; p.tpiV = A * w / EB_LINES; }
   int grid = cus[dev];
   if (grid > ngroups) grid = ngroups;
-  hipLaunchKernelGGL(k_epi_b3, dim3((unsigned)grid), dim3(512), EB_SMEM, st, p);
+  if (y) hipLaunchKernelGGL(k_epi_b3<true>, dim3((unsigned)grid), dim3(512), EB_SMEM, st, p);
+  else hipLaunchKernelGGL(k_epi_b3<false>, dim3((unsigned)grid), dim3(512), EB_SMEM1, st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }

@@ -106,7 +106,7 @@ int lfsr_conv3x3_wino_launch(const float* x, int x_stride, int x_choff, const fl
 // ang_fused.hip: the AngConv branch (conv AxA stride A 64->16, 1x1 16->16AA, PixelShuffle(A)) in one launch
 bool lfsr_ang_fused_ok(int A);
 int lfsr_ang_fused_launch(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed, float* t, float* y,
-                          int y_stride, int y_choff, int B, int A, int h, int w, float slope, hipStream_t st);
+                          int y_stride, int y_choff, int B, int A, int h, int w, float slope, hipStream_t st);     // y = NULL: stage 1 only
 // epi_fused.hip: Winograd F(2,5) pack of an EPIConv.0 weight (O = 32, C = 64, taps = 25 = 5 x 5): LFSR_EPI_WINO_FLOATS after the direct pack
 #define LFSR_EPI_WINO_FLOATS (5 * 6 * 32 * 64)
 // epi_b3.hip: the three bf16 planes of the EPI branch's weights in the order k_epi_b3 stages them: after the F(2,5) copy of EPIConv.0 (O = 32, C = 64, taps = 25)
@@ -117,8 +117,14 @@ bool lfsr_epi_use_b3();     // (epi_fused.hip) LFSR_EPI unset: the three-term bf
 int lfsr_pack_epi_b3(const float* direct_packed, float* out, int kind, hipStream_t st);              // kind 0: EPIConv.0, 1: EPIConv.2
 int lfsr_pack_epi_b3_batch(const LfsrPackDesc* table_dev, int n, hipStream_t st);                     // src = the direct pack, dst = its planes, kind as above
 int lfsr_epi_b3_launch(const float* x, int x_stride, int x_choff, const float* w1_planes, const float* w2_planes, float* y, int y_stride,
-                       int choffH, int choffV, float* t_h, float* t_v, int B, int A, int h, int w, int which, float slope, hipStream_t st);
+                       int choffH, int choffV, float* t_h, float* t_v, int B, int A, int h, int w, int which, float slope, hipStream_t st);   // y = NULL (which = 3): stage 1 only
 int lfsr_pack_epi_wino(const float* w1_direct_packed, float* out, hipStream_t st);
+// distg_tail.hip: DistgSSR's block tail at angRes 5 -- the branches' second stages, the concat and fuse.0 in one launch (t_a / t_h / t_v: the stage-1 results
+// of lfsr_ang_fused_launch / lfsr_epi_b3_launch with y = NULL; we2_planes: EPIConv.2's three bf16 planes; wf_packed: fuse.0 [64][144])
+bool lfsr_distg_tail_ok(int A, int h, int w, const float* x, int x_stride, int x_choff, const float* t_h, const float* t_v);
+int lfsr_distg_tail_launch(const float* spa, int spa_stride, int spa_choff, const float* t_a, const float* t_h, const float* t_v, const float* wa2_packed,
+                           const float* we2_planes, const float* wf_packed, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope,
+                           hipStream_t st);
 // epi_fused.hip  (t_h / t_v: optional (B*A*h*w, 32) buffers receiving the post-LeakyReLU stage-1 activations for backward)
 bool lfsr_epi_fused_ok(int A, int h, int w);
 int lfsr_epi_fused_launch(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed, float* y, int y_stride,
