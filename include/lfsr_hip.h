@@ -355,6 +355,23 @@ int lfsr_internet_finalize(lfsr_internet* ctx, void* stream);
 size_t lfsr_internet_workspace_bytes(const lfsr_internet* ctx, int B, int h, int w);
 int lfsr_internet_forward(lfsr_internet* ctx, const float* x, float* out, int B, int h, int w, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* ---- LF_InterNet training (n_groups = n_layers = 4; other geometries: LFSR_E_ARG): the same contract as the DistgSSR training ABI.
+ * Gradients go into ONE flat fp32 bucket in state_dict order (lfsr_internet_param_offset gives each parameter's span).  forward_train runs
+ * the inference forward's launches (bit-identical output), keeps every activation the backward reads and builds the transposed weight packs
+ * the backward reads from the current packed weights; the workspace must be the same memory for forward_train and the backward that follows.
+ * train_workspace_bytes returns 0 for a geometry the path refuses (the forward's per-tensor bound: B*A*A*h*w*320 < 2^31). */
+size_t lfsr_internet_num_params(const lfsr_internet* ctx);
+int lfsr_internet_param_offset(const lfsr_internet* ctx, const char* key, size_t* offset, size_t* numel);
+size_t lfsr_internet_train_workspace_bytes(const lfsr_internet* ctx, int B, int h, int w);
+int lfsr_internet_forward_train(lfsr_internet* ctx, const float* x, float* out, int B, int h, int w,
+                                void* workspace, size_t workspace_bytes, void* stream);
+/* parity aid: offset (floats, into the training workspace) and size of an activation forward_train saved.  which: 0 a chain layer's input
+ * rows [xs | spa2] (VCL, 128), 1 its rows [xa | ang2] (rows (b,y,x), 128), 2 ReLU(SpaConvSq) (VCL, 64), 3 ReLU(AngConvSq) ((b,y,x), 64),
+ * 4 ReLU(SpaBottle) (VCL, 64), 5 ReLU(AngBottle) ((b,y,x), 64); index = g * n_layers + l (0..15) for 0..3, 0 for 4 / 5. */
+int lfsr_internet_train_saved(const lfsr_internet* ctx, int B, int h, int w, int which, int index, size_t* offset_floats, size_t* numel);
+/* dout (B,1,A*h*s,A*w*s) = dLoss/dOut; grads: n_grads == lfsr_internet_num_params(ctx) floats, overwritten */
+int lfsr_internet_backward(lfsr_internet* ctx, const float* x, const float* dout, int B, int h, int w,
+                           void* workspace, size_t workspace_bytes, float* grads, size_t n_grads, void* stream);
 
 /* ---- backward of the disentangling branches as operators (disentg_branches_bwd; reference layers DistgSSR.py:84-97,108, differentiated by
  * autograd in train.py:256-264).  Raw PyTorch-layout weights in (the entry points pack what their kernels read into the workspace), raw-layout weight

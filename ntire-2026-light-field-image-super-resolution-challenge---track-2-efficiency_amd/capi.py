@@ -72,6 +72,12 @@ SIGNATURES = {
     "lfsr_internet_finalize": (c_i, [c_p, c_p]),
     "lfsr_internet_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
     "lfsr_internet_forward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "lfsr_internet_num_params": (c_sz, [c_p]),
+    "lfsr_internet_param_offset": (c_i, [c_p, C.c_char_p, C.POINTER(c_sz), C.POINTER(c_sz)]),
+    "lfsr_internet_train_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
+    "lfsr_internet_forward_train": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "lfsr_internet_train_saved": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_sz), C.POINTER(c_sz)]),
+    "lfsr_internet_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p, c_sz, c_p]),
     "lfsr_lft_create": (c_i, [C.POINTER(c_p), c_i, c_i, c_i, c_i]),
     "lfsr_lft_destroy": (None, [c_p]),
     "lfsr_lft_packed_bytes": (c_sz, [c_p]),
@@ -698,6 +704,75 @@ class ModelRuntime:
         ws = self.ws[key]
         check(self._f("forward")(self.ctx, dev_ptr(x), dev_ptr(out), B, h, w, dev_ptr(ws), ws.numel(), stream_ptr()), f"{self.name}_forward")
         return out
+
+
+class InterNetRuntime(ModelRuntime):
+    """LF_InterNet runtime with the training entry points (lfsr_internet_forward_train / _backward): one training workspace,
+    gradients into one flat fp32 bucket in state_dict order."""
+
+    def __init__(self, A, scale, n_groups=4, n_layers=4):
+        super().__init__("internet", A, scale, n_groups, n_layers)
+        self.train_generation = 0     # bumped by every forward_train: identifies whose activations the training workspace holds
+        self.tws = {}                 # the training workspace, apart from the inference one: a no-grad forward between a training forward and its backward keeps it
+
+    def num_params(self):
+        return self.lib.lfsr_internet_num_params(self.ctx)
+
+    def param_span(self, key):
+        off, n = c_sz(0), c_sz(0)
+        check(self.lib.lfsr_internet_param_offset(self.ctx, key.encode(), C.byref(off), C.byref(n)), f"param_offset({key})")
+        return off.value, n.value
+
+    def train_workspace_bytes(self, B, h, w):
+        return self.lib.lfsr_internet_train_workspace_bytes(self.ctx, B, h, w)
+
+    def _train_workspace(self, B, h, w, device):
+        key = (B, h, w, device)
+        if key not in self.tws:
+            n = self.train_workspace_bytes(B, h, w)
+            if n == 0:     # refused before anything is allocated
+                raise LfsrError(f"internet training: geometry B={B} h={h} w={w} is outside what the training path covers")
+            self.tws.clear()
+            self.tws[key] = torch.empty(n, dtype=torch.uint8, device=device)
+        return self.tws[key]
+
+    def _geometry(self, x):
+        B, c1, Hh, Ww = x.shape
+        if c1 != 1 or Hh % self.A or Ww % self.A or x.dtype != torch.float32:
+            raise LfsrError(f"bad training input {tuple(x.shape)} {x.dtype}")
+        return B, Hh // self.A, Ww // self.A
+
+    def forward_train(self, x):
+        B, h, w = self._geometry(x)
+        x = x.contiguous()
+        ws = self._train_workspace(B, h, w, x.device)
+        out = torch.empty((B, 1, x.shape[2] * self.scale, x.shape[3] * self.scale), dtype=torch.float32, device=x.device)
+        check(self.lib.lfsr_internet_forward_train(self.ctx, dev_ptr(x), dev_ptr(out), B, h, w, dev_ptr(ws), ws.numel(), stream_ptr()),
+              "internet_forward_train")
+        self.train_generation += 1
+        return out
+
+    def backward(self, x, dout, grads=None):
+        """dLoss/dOut -> flat fp32 gradient bucket (state_dict order).  Must follow forward_train(x) of the same x."""
+        B, h, w = self._geometry(x)
+        n = self.num_params()
+        if grads is None:
+            grads = torch.empty(n, dtype=torch.float32, device=x.device)
+        ws = self._train_workspace(B, h, w, x.device)
+        dout = dout.contiguous()
+        if dout.dtype != torch.float32:
+            dout = dout.float()
+        check(self.lib.lfsr_internet_backward(self.ctx, dev_ptr(x.contiguous()), dev_ptr(dout), B, h, w, dev_ptr(ws), ws.numel(),
+                                              dev_ptr(grads), n, stream_ptr()), "internet_backward")
+        return grads
+
+    def train_saved(self, x, which, index):
+        """the activation forward_train(x) saved for the backward, as a flat fp32 view of the training workspace (lfsr_internet_train_saved)"""
+        B, h, w = self._geometry(x)
+        off, n = c_sz(0), c_sz(0)
+        check(self.lib.lfsr_internet_train_saved(self.ctx, B, h, w, which, index, C.byref(off), C.byref(n)), "train_saved")
+        ws = self._train_workspace(B, h, w, x.device).view(torch.float32)
+        return ws[off.value:off.value + n.value]
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -9,7 +9,7 @@
 // ReconBlock's PreConv -> MacPI2SAI -> PixelShuffle(s) -> FinalConv chain is linear and is folded to one 3x3 conv 64->s^2
 // whose epilogue scatters straight into the HR SAI mosaic.
 #include "gemm_gather_kernel.h"
-#include "param_table.h"
+#include "internet_ctx.h"
 
 namespace {
 
@@ -69,12 +69,19 @@ inline unsigned cap_grid(long long total, unsigned cap = 8192) {
 
 }  // namespace
 
-struct lfsr_internet {
-  int A, s, ngroups, nlayers;
-  LfsrParamTable P;
-  size_t off_wf = 0;
-  bool finalized = false;
-};
+// AngFE and the 64-channel slice copy as host launches: the training forward (internet_train.hip) issues the same launches
+int lfsr_internet_angfe(const float* x, const float* w, float* y, int y_stride, int y_choff, int B, int A, int h, int wd, hipStream_t st) {
+  const long long nlr = (long long)B * h * wd;
+  hipLaunchKernelGGL(k_angfe, dim3(cap_grid(nlr * 16)), dim3(256), 64 * A * A * sizeof(float), st, x, w, y, y_stride, y_choff, B, A, h, wd);
+  LFSR_CHECK_LAUNCH();
+  return LFSR_OK;
+}
+
+int lfsr_internet_copy64(const float* src, int s_stride, int s_choff, float* dst, int d_stride, int d_choff, long long M, hipStream_t st) {
+  hipLaunchKernelGGL(k_copy64, dim3(cap_grid(M * 16)), dim3(256), 0, st, src, s_stride, s_choff, dst, d_stride, d_choff, M);
+  LFSR_CHECK_LAUNCH();
+  return LFSR_OK;
+}
 
 extern "C" {
 
