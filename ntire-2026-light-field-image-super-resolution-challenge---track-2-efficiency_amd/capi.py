@@ -393,127 +393,174 @@ class GraphedForward:
 
 
 # ---------------------------------------------------------------------------------------------------
-# DistgSSR whole-model runtime
+# whole-model runtimes: every model drives one C-ABI life cycle, lfsr_<name>_create / packed_bytes / set_packed / load_param /
+# finalize / workspace_bytes / forward; the trainable ones (distgssr, internet) add num_params / param_offset /
+# train_workspace_bytes / forward_train / train_saved / backward
 # ---------------------------------------------------------------------------------------------------
 
-class DistgSSRRuntime:
-    """Owns one lfsr_distgssr context + its packed weights and workspaces (torch allocations)."""
+class ModelRuntime:
+    """ctx = lfsr_<name>_create(A, scale, *create_args); packed weights and workspaces are torch allocations owned here.
+    The training workspace is kept apart from the inference one: a no-grad forward between a training forward and its backward
+    leaves the activations that backward reads in place."""
 
-    def __init__(self, A, scale, n_group=4, n_block=4, channels=64):
+    widest_row_floats, offset_limit = 256, 1 << 31    # max_patches_per_launch: the 256-float q | k rows of EPIT / LFT
+
+    def __init__(self, name, A, scale, *create_args):
         self.lib = load()
-        self.A, self.scale = A, scale
+        self.name, self.A, self.scale = name, A, scale
         ctx = c_p()
-        check(self.lib.lfsr_distgssr_create(C.byref(ctx), A, scale, n_group, n_block, channels), "distgssr_create")
+        check(self._f("create")(C.byref(ctx), A, scale, *create_args), f"{name}_create")
         self.ctx = ctx
         self.packed = None
-        self.ws = {}
-        self.loaded_version = None
+        self.ws = {}                  # the inference workspace
+        self.tws = {}                 # the training workspace
         self.train_generation = 0     # bumped by every forward_train: identifies whose activations the training workspace holds
+
+    def _f(self, fn):
+        sym = f"lfsr_{self.name}_{fn}"
+        if sym not in SIGNATURES:
+            raise LfsrError(f"{self.name}: the C ABI has no {sym}")
+        return getattr(self.lib, sym)
 
     def __del__(self):
         try:
             if getattr(self, "ctx", None):
-                self.lib.lfsr_distgssr_destroy(self.ctx)
+                self._f("destroy")(self.ctx)
                 self.ctx = None
         except Exception:
             pass
 
-    def load_state(self, named_tensors, device, fanout=None, batched=False):
-        """named_tensors: iterable of (key, fp32 CUDA tensor) with the reference's state_dict names.
-        fanout: a list of side streams; the pack launches of parameter i then go to stream i % len(fanout), forked from and joined back into the
-        current stream (the ~270 pack kernels of a repack are 4-us launches of 16 blocks each: independent, so they overlap instead of queueing)."""
-        nbytes = self.lib.lfsr_distgssr_packed_bytes(self.ctx)
+    def load_state(self, named_tensors, device):
+        """named_tensors: iterable of (key, CUDA tensor) with the reference's state_dict names."""
+        nbytes = self._f("packed_bytes")(self.ctx)
         if self.packed is None or self.packed.device != device:
             self.packed = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        check(self.lib.lfsr_distgssr_set_packed(self.ctx, dev_ptr(self.packed), nbytes), "distgssr_set_packed")
-        cur = torch.cuda.current_stream(device)
+        check(self._f("set_packed")(self.ctx, dev_ptr(self.packed), nbytes), f"{self.name}_set_packed")
         st = stream_ptr()
-        keep = []
-        if batched:     # one launch per pack kind at finalize (the tensors handed over must stay alive until then: `keep`)
-            check(self.lib.lfsr_distgssr_begin_batched_load(self.ctx), "distgssr_begin_batched_load")
-        if fanout:
-            fork = torch.cuda.Event()
-            fork.record(cur)
-            for s in fanout:
-                s.wait_event(fork)
-        for i, (k, t) in enumerate(named_tensors):
-            t = t.detach()
-            if t.dtype != torch.float32:
-                t = t.float()
-            t = t.contiguous()
-            sp = C.c_void_p(fanout[i % len(fanout)].cuda_stream) if fanout else st
+        keep = []     # a batched load (DistgSSRRuntime) reads the tensors at finalize
+        for k, t in named_tensors:
+            t = t.detach().float().contiguous()
             keep.append(t)
-            check(self.lib.lfsr_distgssr_load_param(self.ctx, k.encode(), dev_ptr(t, k), t.numel(), sp), f"distgssr_load_param({k})")
-        if fanout:
-            for s in fanout:
-                e = torch.cuda.Event()
-                e.record(s)
-                cur.wait_event(e)
-        check(self.lib.lfsr_distgssr_finalize(self.ctx, st), "distgssr_finalize")
+            check(self._f("load_param")(self.ctx, k.encode(), dev_ptr(t, k), t.numel(), st), f"{self.name}_load_param({k})")
+        check(self._f("finalize")(self.ctx, st), f"{self.name}_finalize")
 
-    def _workspace(self, B, h, w, device):
+    def _geometry(self, x):
+        B, c1, Hh, Ww = x.shape
+        if c1 != 1 or Hh % self.A or Ww % self.A:
+            raise LfsrError(f"bad input shape {tuple(x.shape)} for angRes {self.A}")
+        if x.dtype != torch.float32:
+            raise LfsrError(f"{self.name} HIP path computes in fp32; got {x.dtype}")
+        return B, Hh // self.A, Ww // self.A
+
+    def _output(self, x):
+        return torch.empty((x.shape[0], 1, x.shape[2] * self.scale, x.shape[3] * self.scale), dtype=torch.float32, device=x.device)
+
+    def _workspace(self, B, h, w, device, train=False):
+        """one live workspace of each kind per runtime"""
+        cache = self.tws if train else self.ws
         key = (B, h, w, device)
-        if key not in self.ws:
-            self.ws.clear()   # one live workspace per runtime
-            n = self.lib.lfsr_distgssr_workspace_bytes(self.ctx, B, h, w)
-            self.ws[key] = torch.empty(n, dtype=torch.uint8, device=device)
-        return self.ws[key]
+        if key not in cache:
+            n = self.train_workspace_bytes(B, h, w) if train else self._f("workspace_bytes")(self.ctx, B, h, w)
+            if train and n == 0:     # refused before anything is allocated
+                raise LfsrError(f"{self.name} training: geometry B={B} h={h} w={w} is outside what the training path covers")
+            cache.clear()
+            cache[key] = torch.empty(n, dtype=torch.uint8, device=device)
+        return cache[key]
 
-    # ---- training ---------------------------------------------------------------------------------
+    def forward(self, x):
+        """x (B,1,A*h,A*w) fp32 CUDA -> (B,1,A*h*s,A*w*s)"""
+        B, h, w = self._geometry(x)
+        x = x.contiguous()
+        nmax = max_patches_per_launch(self.A, h, w, self.widest_row_floats, self.offset_limit)
+        if B > nmax:
+            return _forward_in_chunks(self.forward, x, nmax)
+        out = self._output(x)
+        ws = self._workspace(B, h, w, x.device)
+        check(self._f("forward")(self.ctx, dev_ptr(x), dev_ptr(out), B, h, w, dev_ptr(ws), ws.numel(), stream_ptr()), f"{self.name}_forward")
+        return out
+
+    # ---- training: gradients into one flat fp32 bucket in state_dict order ---------------------------
     def num_params(self):
-        return self.lib.lfsr_distgssr_num_params(self.ctx)
+        return self._f("num_params")(self.ctx)
 
     def param_span(self, key):
         off, n = c_sz(0), c_sz(0)
-        check(self.lib.lfsr_distgssr_param_offset(self.ctx, key.encode(), C.byref(off), C.byref(n)), f"param_offset({key})")
+        check(self._f("param_offset")(self.ctx, key.encode(), C.byref(off), C.byref(n)), f"param_offset({key})")
         return off.value, n.value
 
-    def _train_workspace(self, B, h, w, device):
-        key = ("train", B, h, w, device)
-        if key not in self.ws:
-            self.ws.clear()
-            n = self.lib.lfsr_distgssr_train_workspace_bytes(self.ctx, B, h, w)
-            self.ws[key] = torch.empty(n, dtype=torch.uint8, device=device)
-        return self.ws[key]
+    def train_workspace_bytes(self, B, h, w):
+        return self._f("train_workspace_bytes")(self.ctx, B, h, w)
 
     def forward_train(self, x):
-        B, c1, Hh, Ww = x.shape
-        if c1 != 1 or Hh % self.A or Ww % self.A or x.dtype != torch.float32:
-            raise LfsrError(f"bad training input {tuple(x.shape)} {x.dtype}")
-        h, w = Hh // self.A, Ww // self.A
+        B, h, w = self._geometry(x)
         x = x.contiguous()
-        out = torch.empty((B, 1, Hh * self.scale, Ww * self.scale), dtype=torch.float32, device=x.device)
-        ws = self._train_workspace(B, h, w, x.device)
-        check(self.lib.lfsr_distgssr_forward_train(self.ctx, dev_ptr(x), dev_ptr(out), B, h, w, dev_ptr(ws), ws.numel(), stream_ptr()),
-              "distgssr_forward_train")
+        ws = self._workspace(B, h, w, x.device, train=True)
+        out = self._output(x)
+        check(self._f("forward_train")(self.ctx, dev_ptr(x), dev_ptr(out), B, h, w, dev_ptr(ws), ws.numel(), stream_ptr()),
+              f"{self.name}_forward_train")
         self.train_generation += 1
         return out
 
     def backward(self, x, dout, grads=None):
         """dLoss/dOut -> flat fp32 gradient bucket (state_dict order).  Must follow forward_train(x) of the same x."""
-        B, _, Hh, Ww = x.shape
-        h, w = Hh // self.A, Ww // self.A
+        B, h, w = self._geometry(x)
         n = self.num_params()
         if grads is None:
             grads = torch.empty(n, dtype=torch.float32, device=x.device)
-        ws = self._train_workspace(B, h, w, x.device)
+        ws = self._workspace(B, h, w, x.device, train=True)
         dout = dout.contiguous()
         if dout.dtype != torch.float32:
             dout = dout.float()
-        check(self.lib.lfsr_distgssr_backward(self.ctx, dev_ptr(x.contiguous()), dev_ptr(dout), B, h, w, dev_ptr(ws), ws.numel(),
-                                              dev_ptr(grads), n, stream_ptr()), "distgssr_backward")
+        check(self._f("backward")(self.ctx, dev_ptr(x.contiguous()), dev_ptr(dout), B, h, w, dev_ptr(ws), ws.numel(),
+                                  dev_ptr(grads), n, stream_ptr()), f"{self.name}_backward")
         return grads
 
     def train_saved(self, x, which, index):
-        """the activation forward_train(x) saved for the backward, as a flat fp32 view of the training workspace (lfsr_distgssr_train_saved)"""
-        B, _, Hh, Ww = x.shape
-        h, w = Hh // self.A, Ww // self.A
+        """the activation forward_train(x) saved for the backward, as a flat fp32 view of the training workspace (lfsr_<name>_train_saved)"""
+        B, h, w = self._geometry(x)
         off, n = c_sz(0), c_sz(0)
-        check(self.lib.lfsr_distgssr_train_saved(self.ctx, B, h, w, which, index, C.byref(off), C.byref(n)), "train_saved")
-        ws = self._train_workspace(B, h, w, x.device).view(torch.float32)
+        check(self._f("train_saved")(self.ctx, B, h, w, which, index, C.byref(off), C.byref(n)), "train_saved")
+        ws = self._workspace(B, h, w, x.device, train=True).view(torch.float32)
         return ws[off.value:off.value + n.value]
 
+
+class DistgSSRRuntime(ModelRuntime):
+    """lfsr_distgssr: the batched weight load, the tapped forward and the per-class profile on top of the shared life cycle."""
+
+    widest_row_floats, offset_limit = 160, 1 << 30    # the 144-channel concat buffer (counted as 160); 1 GiB: see max_patches_per_launch
     PROFILE_CLASSES = ("conv3x3", "angconv", "epiconv", "pointwise", "init_conv", "upsample_head")
+
+    def __init__(self, A, scale, n_group=4, n_block=4, channels=64):
+        super().__init__("distgssr", A, scale, n_group, n_block, channels)
+
+    def load_state(self, named_tensors, device, batched=False):
+        """batched: the packs are recorded into a device-side descriptor table (re-uploaded only when an address changed) and run at
+        finalize as one launch per pack kind instead of ~280 small launches (lfsr_distgssr_begin_batched_load)."""
+        if batched:
+            check(self.lib.lfsr_distgssr_begin_batched_load(self.ctx), "distgssr_begin_batched_load")
+        super().load_state(named_tensors, device)
+
+    def forward(self, x, taps=None):
+        """x (B,1,A*h,A*w) fp32 CUDA -> (B,1,A*h*s,A*w*s).  taps: optional list of 5 bools -> (out, the 5 tapped activations or None)."""
+        if taps is None:
+            return super().forward(x)
+        B, h, w = self._geometry(x)
+        x = x.contiguous()
+        out = self._output(x)
+        ws = self._workspace(B, h, w, x.device)
+        bufs = []
+        arr = (c_p * 5)()
+        for i in range(5):
+            if taps[i]:
+                t = torch.empty((B, 144 if i == 4 else 64, x.shape[2], x.shape[3]), dtype=torch.float32, device=x.device)
+                arr[i] = t.data_ptr()
+            else:
+                t = None
+                arr[i] = None
+            bufs.append(t)
+        check(self.lib.lfsr_distgssr_forward_taps(self.ctx, dev_ptr(x), dev_ptr(out), B, h, w, dev_ptr(ws), ws.numel(), arr, stream_ptr()),
+              "distgssr_forward_taps")
+        return out, bufs
 
     def profile(self, enable):
         check(self.lib.lfsr_distgssr_profile(self.ctx, int(enable)), "distgssr_profile")
@@ -524,38 +571,6 @@ class DistgSSRRuntime:
         n = (C.c_longlong * 6)()
         check(self.lib.lfsr_distgssr_profile_read(self.ctx, ms, n), "distgssr_profile_read")
         return {k: (ms[i], n[i]) for i, k in enumerate(self.PROFILE_CLASSES)}
-
-    def forward(self, x, taps=None):
-        """x (B,1,A*h,A*w) fp32 CUDA -> (B,1,A*h*s,A*w*s).  taps: optional list of 5 bools."""
-        B, c1, Hh, Ww = x.shape
-        if c1 != 1 or Hh % self.A or Ww % self.A:
-            raise LfsrError(f"bad input shape {tuple(x.shape)} for angRes {self.A}")
-        if x.dtype != torch.float32:
-            raise LfsrError("DistgSSR HIP path computes in fp32; got " + str(x.dtype))
-        h, w = Hh // self.A, Ww // self.A
-        x = x.contiguous()
-        if taps is None and B > max_patches_per_launch(self.A, h, w, 160, 1 << 30):
-            return _forward_in_chunks(self.forward, x, max_patches_per_launch(self.A, h, w, 160, 1 << 30))
-        out = torch.empty((B, 1, Hh * self.scale, Ww * self.scale), dtype=torch.float32, device=x.device)
-        ws = self._workspace(B, h, w, x.device)
-        if taps is None:
-            check(self.lib.lfsr_distgssr_forward(self.ctx, dev_ptr(x), dev_ptr(out), B, h, w, dev_ptr(ws), ws.numel(), stream_ptr()),
-                  "distgssr_forward")
-            return out
-        bufs = []
-        arr = (c_p * 5)()
-        for i in range(5):
-            if taps[i]:
-                t = torch.empty((B, 144 if i == 4 else 64, Hh, Ww), dtype=torch.float32, device=x.device)
-                arr[i] = t.data_ptr()
-            else:
-                t = None
-                arr[i] = None
-            bufs.append(t)
-        check(self.lib.lfsr_distgssr_forward_taps(self.ctx, dev_ptr(x), dev_ptr(out), B, h, w, dev_ptr(ws), ws.numel(), arr, stream_ptr()),
-              "distgssr_forward_taps")
-        return out, bufs
-
 
 # ---------------------------------------------------------------------------------------------------
 # d1-d9 operator-level wrappers on VCL tensors (2-D torch tensors: (pixels, stride))
@@ -648,131 +663,6 @@ def upsample_head(f, w0, b0, w2, x_lr, A, s):
     check(lib.lfsr_upsample_head_fwd(dev_ptr(f), f.shape[1], 0, dev_ptr(wf), dev_ptr(bf), dev_ptr(x_lr), dev_ptr(out), B, A, h, w, s, stream_ptr()),
           "upsample_head_fwd")
     return out
-
-
-# ---------------------------------------------------------------------------------------------------
-# generic whole-model runtime (EPIT, LFT, LF_InterNet drivers share one C-ABI life cycle)
-# ---------------------------------------------------------------------------------------------------
-
-class ModelRuntime:
-    """ctx = lfsr_<name>_create(...); packed weights + workspace are torch allocations owned here."""
-
-    def __init__(self, name, A, scale, *create_args):
-        self.lib = load()
-        self.name, self.A, self.scale = name, A, scale
-        self._f = lambda fn: getattr(self.lib, f"lfsr_{name}_{fn}")
-        ctx = c_p()
-        check(self._f("create")(C.byref(ctx), A, scale, *create_args), f"{name}_create")
-        self.ctx = ctx
-        self.packed = None
-        self.ws = {}
-
-    def __del__(self):
-        try:
-            if getattr(self, "ctx", None):
-                self._f("destroy")(self.ctx)
-                self.ctx = None
-        except Exception:
-            pass
-
-    def load_state(self, named_tensors, device):
-        nbytes = self._f("packed_bytes")(self.ctx)
-        if self.packed is None or self.packed.device != device:
-            self.packed = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        check(self._f("set_packed")(self.ctx, dev_ptr(self.packed), nbytes), f"{self.name}_set_packed")
-        st = stream_ptr()
-        for k, t in named_tensors:
-            t = t.detach().float().contiguous()
-            check(self._f("load_param")(self.ctx, k.encode(), dev_ptr(t, k), t.numel(), st), f"{self.name}_load_param({k})")
-        check(self._f("finalize")(self.ctx, st), f"{self.name}_finalize")
-
-    def forward(self, x):
-        B, c1, Hh, Ww = x.shape
-        if c1 != 1 or Hh % self.A or Ww % self.A:
-            raise LfsrError(f"bad input shape {tuple(x.shape)} for angRes {self.A}")
-        if x.dtype != torch.float32:
-            raise LfsrError(f"{self.name} HIP path computes in fp32; got {x.dtype}")
-        h, w = Hh // self.A, Ww // self.A
-        x = x.contiguous()
-        if B > max_patches_per_launch(self.A, h, w, 256):
-            return _forward_in_chunks(self.forward, x, max_patches_per_launch(self.A, h, w, 256))
-        out = torch.empty((B, 1, Hh * self.scale, Ww * self.scale), dtype=torch.float32, device=x.device)
-        key = (B, h, w, x.device)
-        if key not in self.ws:
-            self.ws.clear()
-            self.ws[key] = torch.empty(self._f("workspace_bytes")(self.ctx, B, h, w), dtype=torch.uint8, device=x.device)
-        ws = self.ws[key]
-        check(self._f("forward")(self.ctx, dev_ptr(x), dev_ptr(out), B, h, w, dev_ptr(ws), ws.numel(), stream_ptr()), f"{self.name}_forward")
-        return out
-
-
-class InterNetRuntime(ModelRuntime):
-    """LF_InterNet runtime with the training entry points (lfsr_internet_forward_train / _backward): one training workspace,
-    gradients into one flat fp32 bucket in state_dict order."""
-
-    def __init__(self, A, scale, n_groups=4, n_layers=4):
-        super().__init__("internet", A, scale, n_groups, n_layers)
-        self.train_generation = 0     # bumped by every forward_train: identifies whose activations the training workspace holds
-        self.tws = {}                 # the training workspace, apart from the inference one: a no-grad forward between a training forward and its backward keeps it
-
-    def num_params(self):
-        return self.lib.lfsr_internet_num_params(self.ctx)
-
-    def param_span(self, key):
-        off, n = c_sz(0), c_sz(0)
-        check(self.lib.lfsr_internet_param_offset(self.ctx, key.encode(), C.byref(off), C.byref(n)), f"param_offset({key})")
-        return off.value, n.value
-
-    def train_workspace_bytes(self, B, h, w):
-        return self.lib.lfsr_internet_train_workspace_bytes(self.ctx, B, h, w)
-
-    def _train_workspace(self, B, h, w, device):
-        key = (B, h, w, device)
-        if key not in self.tws:
-            n = self.train_workspace_bytes(B, h, w)
-            if n == 0:     # refused before anything is allocated
-                raise LfsrError(f"internet training: geometry B={B} h={h} w={w} is outside what the training path covers")
-            self.tws.clear()
-            self.tws[key] = torch.empty(n, dtype=torch.uint8, device=device)
-        return self.tws[key]
-
-    def _geometry(self, x):
-        B, c1, Hh, Ww = x.shape
-        if c1 != 1 or Hh % self.A or Ww % self.A or x.dtype != torch.float32:
-            raise LfsrError(f"bad training input {tuple(x.shape)} {x.dtype}")
-        return B, Hh // self.A, Ww // self.A
-
-    def forward_train(self, x):
-        B, h, w = self._geometry(x)
-        x = x.contiguous()
-        ws = self._train_workspace(B, h, w, x.device)
-        out = torch.empty((B, 1, x.shape[2] * self.scale, x.shape[3] * self.scale), dtype=torch.float32, device=x.device)
-        check(self.lib.lfsr_internet_forward_train(self.ctx, dev_ptr(x), dev_ptr(out), B, h, w, dev_ptr(ws), ws.numel(), stream_ptr()),
-              "internet_forward_train")
-        self.train_generation += 1
-        return out
-
-    def backward(self, x, dout, grads=None):
-        """dLoss/dOut -> flat fp32 gradient bucket (state_dict order).  Must follow forward_train(x) of the same x."""
-        B, h, w = self._geometry(x)
-        n = self.num_params()
-        if grads is None:
-            grads = torch.empty(n, dtype=torch.float32, device=x.device)
-        ws = self._train_workspace(B, h, w, x.device)
-        dout = dout.contiguous()
-        if dout.dtype != torch.float32:
-            dout = dout.float()
-        check(self.lib.lfsr_internet_backward(self.ctx, dev_ptr(x.contiguous()), dev_ptr(dout), B, h, w, dev_ptr(ws), ws.numel(),
-                                              dev_ptr(grads), n, stream_ptr()), "internet_backward")
-        return grads
-
-    def train_saved(self, x, which, index):
-        """the activation forward_train(x) saved for the backward, as a flat fp32 view of the training workspace (lfsr_internet_train_saved)"""
-        B, h, w = self._geometry(x)
-        off, n = c_sz(0), c_sz(0)
-        check(self.lib.lfsr_internet_train_saved(self.ctx, B, h, w, which, index, C.byref(off), C.byref(n)), "train_saved")
-        ws = self._train_workspace(B, h, w, x.device).view(torch.float32)
-        return ws[off.value:off.value + n.value]
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -2,25 +2,18 @@
 
 Same plugin surface -- ``get_model(args)``, ``get_loss(args)``, ``weights_init(m)`` (reference
 train.py:48-50,94; DistgSSR.py:14-36,158-170) -- and the same ``state_dict`` key names / shapes
-(SURVEY 8c), so reference checkpoints load unchanged.  The modules below are parameter containers only:
-``forward`` hands the tensors to the gfx950 HIP library through the C ABI (lfsr_amd.capi); none of the
-``nn.Conv2d.forward`` paths is ever executed and there is no CPU fallback.
+(SURVEY 8c), so reference checkpoints load unchanged.  The modules below are parameter containers only; ``forward``
+and, with grad enabled, the backward run in the gfx950 HIP library (lfsr_amd.hip_model).
 """
 import torch
 import torch.nn as nn
 
 from lfsr_amd import capi
+from lfsr_amd.hip_model import HipModel, _Holder
 
 
 def _dil_conv(cin, cout, A):
     return nn.Conv2d(cin, cout, kernel_size=3, stride=1, dilation=A, padding=A, bias=False)
-
-
-class _Holder(nn.Module):
-    """Parameter container whose forward must never run."""
-
-    def forward(self, *a, **k):  # pragma: no cover
-        raise RuntimeError("parameter container: the HIP path computes this layer")
 
 
 class _Block(_Holder):
@@ -53,40 +46,9 @@ class _Cascade(_Holder):
         self.conv = _dil_conv(ch, ch, A)
 
 
-class _DistgSSRFunction(torch.autograd.Function):
-    """Whole-model autograd node: forward and backward both run in the HIP library; the gradients of all 137
-    parameters come back as views of ONE flat fp32 bucket (``model.grad_bucket``) ready for a single all-reduce."""
+class get_model(HipModel):
+    hip_name = "DistgSSR"
 
-    @staticmethod
-    def forward(ctx, model, x, *params):
-        rt = model._runtime(x.device)
-        ctx.model, ctx.rt = model, rt
-        ctx.save_for_backward(x)
-        out = rt.forward_train(x)
-        ctx.generation = rt.train_generation      # the saved activations live in the runtime's ONE training workspace
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        (x,) = ctx.saved_tensors
-        model, rt = ctx.model, ctx.rt
-        if ctx.generation != rt.train_generation:
-            raise capi.LfsrError("DistgSSR backward: a later forward (with grad enabled) has overwritten the training workspace this "
-                                 "graph's activations lived in; run backward before the next training forward")
-        # A FRESH bucket per backward: autograd's AccumulateGrad keeps (steals) the tensors returned here as p.grad, so handing it
-        # views of a buffer that the next backward overwrites would make `p.grad += new` run on aliased memory (zero_grad(set_to_none=
-        # False) or gradient accumulation would silently double the gradients).  model.grad_bucket is the latest one.
-        bucket = torch.empty(rt.num_params(), dtype=torch.float32, device=x.device)
-        rt.backward(x, dout, bucket)
-        model.grad_bucket = bucket
-        grads = []
-        for name, p in model.named_parameters():
-            off, n = model._spans[name]
-            grads.append(bucket[off:off + n].view_as(p) if p.requires_grad else None)
-        return (None, None, *grads)
-
-
-class get_model(nn.Module):
     def __init__(self, args):
         super().__init__()
         channels, n_group, n_block = 64, 4, 4
@@ -96,66 +58,13 @@ class get_model(nn.Module):
         self.disentg = _Cascade(n_group, n_block, self.angRes, channels)
         self.upsample = nn.Sequential(nn.Conv2d(channels, channels * self.factor ** 2, kernel_size=1),
                                       nn.PixelShuffle(self.factor), nn.Conv2d(channels, 1, kernel_size=1, bias=False))
-        self._rt = None
-        self._rt_version = None
-        self._pack_graph, self._pack_ptrs, self._pack_eager_count = None, None, 0
-        self._spans = None
-        self.grad_bucket = None      # flat fp32 gradient bucket filled by the HIP backward (state_dict order)
 
-    # -- HIP runtime plumbing ------------------------------------------------------------------------
-    def _runtime(self, device):
-        if self._rt is None:
-            self._rt = capi.DistgSSRRuntime(self.angRes, self.factor)
-        if self._spans is None:
-            self._spans = {k: self._rt.param_span(k) for k, _ in self.named_parameters()}
-        ver = (device, tuple((p.data_ptr(), p._version) for p in self.parameters()))
-        if ver != self._rt_version:   # (re)pack after load_state_dict / .to() / an optimizer step
-            self._repack(device)
-            self._rt_version = ver
-        return self._rt
+    def _new_runtime(self):
+        return capi.DistgSSRRuntime(self.angRes, self.factor)
 
     def _repack(self, device):
-        """Hand the current parameter values to the HIP library.  An optimizer step changes values, not addresses.  Default: the packs are recorded
-        into a device-side descriptor table (re-uploaded only when an address changed) and run as one launch per pack kind.  LFSR_PACK_BATCH=0: the
-        ~280 small pack launches are replayed from ONE captured graph instead (LFSR_PACK_GRAPH=0: re-issued one by one; any change of a parameter's
-        address falls back to the eager path and re-captures)."""
-        import os
-        ptrs = (device, tuple(p.data_ptr() for p in self.parameters()))
-        fp32 = all(p.dtype == torch.float32 and p.is_contiguous() for p in self.parameters())
-        if fp32 and os.environ.get("LFSR_PACK_BATCH", "1") != "0":
-            # one launch per pack kind from a device-side descriptor table (re-uploaded only when an address changed): ~280 4-us launches -> 4
-            self._pack_graph = None
-            self._rt.load_state(self.state_dict().items(), device, batched=True)
-            self._pack_ptrs = ptrs
-            return
-        if self._pack_graph is not None and ptrs == self._pack_ptrs:
-            self._pack_graph.replay()
-            return
-        self._pack_graph = None
-        self._rt.load_state(self.state_dict().items(), device)
-        self._pack_eager_count = self._pack_eager_count + 1 if ptrs == self._pack_ptrs else 1
-        self._pack_ptrs = ptrs
-        if self._pack_eager_count >= 2 and os.environ.get("LFSR_PACK_GRAPH", "1") != "0" and fp32:
-            torch.cuda.synchronize(device)
-            g = torch.cuda.CUDAGraph()
-            nfan = int(os.environ.get("LFSR_PACK_FANOUT", "1"))   # > 1: parallel branches over side streams -- measured SLOWER (27.7 vs 26.0 ms per training step with 8 or 16: profiles/r02_logs/ab_bench_lines.json: bench25_*.json)
-            self._pack_streams = [torch.cuda.Stream(device) for _ in range(nfan)] if nfan > 1 else None
-            with torch.cuda.graph(g):
-                self._rt.load_state(self.state_dict().items(), device, fanout=self._pack_streams)
-            self._pack_graph = g
-
-    def invalidate_packed(self):
-        """Force a repack of the HIP library's weight copies at the next forward.  The runtime notices parameter updates through
-        (data_ptr, _version); writes that bypass the version counter (``p.data.copy_``, collectives on ``p.data``) must call this."""
-        self._rt_version = None
-
-    def forward(self, x, info=None):
-        if not x.is_cuda:
-            raise capi.LfsrError("DistgSSR: input must live on the MI355X (no CPU fallback in the HIP path)")
-        x = x.float() if x.dtype != torch.float32 else x
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            return _DistgSSRFunction.apply(self, x, *self.parameters())      # train.py:257
-        return self._runtime(x.device).forward(x)
+        # one launch per pack kind from a device-side descriptor table (re-uploaded only when an address changed): ~280 4-us launches -> 4
+        self._rt.load_state(self.state_dict().items(), device, batched=True)
 
 
 class get_loss(nn.Module):

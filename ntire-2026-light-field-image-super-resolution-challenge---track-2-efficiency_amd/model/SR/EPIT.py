@@ -8,11 +8,7 @@ import torch
 import torch.nn as nn
 
 from lfsr_amd import capi
-
-
-class _Holder(nn.Module):
-    def forward(self, *a, **k):  # pragma: no cover
-        raise RuntimeError("parameter container: the HIP path computes this layer")
+from lfsr_amd.hip_model import HipModel, _Holder
 
 
 def _conv133(cin, cout):
@@ -43,7 +39,10 @@ class _AltFilter(_Holder):
                                   nn.LeakyReLU(0.2, inplace=True), _conv133(channels, channels))
 
 
-class get_model(nn.Module):
+class get_model(HipModel):
+    hip_name = "EPIT"
+    inference_only = "EPIT is inference-only here (its training is broken upstream, EPIT.py:178): call under torch.no_grad()"
+
     def __init__(self, args):
         super().__init__()
         channels = 64
@@ -55,28 +54,9 @@ class get_model(nn.Module):
         self.altblock = nn.Sequential(*[_AltFilter(self.angRes, channels) for _ in range(5)])
         self.upsampling = nn.Sequential(nn.Conv2d(channels, channels * self.scale ** 2, kernel_size=1, padding=0, bias=False),
                                         nn.PixelShuffle(self.scale), nn.LeakyReLU(0.2), nn.Conv2d(channels, 1, kernel_size=3, padding=1, bias=False))
-        self._rt = None
-        self._rt_version = None
 
-    def _runtime(self, device):
-        if self._rt is None:
-            self._rt = capi.ModelRuntime("epit", self.angRes, self.scale, 5, 64)
-        ver = (device, tuple((p.data_ptr(), p._version) for p in self.parameters()))
-        if ver != self._rt_version:
-            self._rt.load_state(self.state_dict().items(), device)
-            self._rt_version = ver
-        return self._rt
-
-    def invalidate_packed(self):
-        """Force a repack at the next forward (for weight writes that bypass p._version: ``p.data.copy_``, collectives)."""
-        self._rt_version = None
-
-    def forward(self, lr, info=None):
-        if not lr.is_cuda:
-            raise capi.LfsrError("EPIT: input must live on the MI355X (no CPU fallback in the HIP path)")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise NotImplementedError("EPIT is inference-only here (its training is broken upstream, EPIT.py:178): call under torch.no_grad()")
-        return self._runtime(lr.device).forward(lr.float() if lr.dtype != torch.float32 else lr)
+    def _new_runtime(self):
+        return capi.ModelRuntime("epit", self.angRes, self.scale, 5, 64)
 
 
 class get_loss(nn.Module):

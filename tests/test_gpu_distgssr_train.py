@@ -335,11 +335,11 @@ def test_amp_loop_shape_gradscaler():
     assert diff / sum(p.numel() for p in nets[0].parameters()) < 1e-3
 
 
-def test_repack_modes_equal_eager(monkeypatch):
-    """After an optimizer step only parameter VALUES change (model/SR/DistgSSR.py:_repack): the weight repack runs as ONE launch per pack kind from a
-    device-side descriptor table (default), or is replayed from a captured graph (LFSR_PACK_BATCH=0), or is re-issued launch by launch
-    (LFSR_PACK_BATCH=0 LFSR_PACK_GRAPH=0).  Five training steps in each mode are equal bit for bit -- for angRes 3 (generic 3x3 packs) and angRes 5
-    (the F(2,5) EPI pack as well)."""
+def test_batched_repack_equals_per_parameter_load():
+    """After an optimizer step only parameter VALUES change: the plugin repacks through a device-side descriptor table, one launch per pack kind
+    (DistgSSRRuntime.load_state(batched=True)); without `batched` the ~280 packs are issued launch by launch.  Five training steps with either
+    repack are equal bit for bit, and both paths pack the trained state_dict into the same bytes with bit-equal forwards -- for angRes 3 (generic
+    3x3 packs) and angRes 5 (the F(2,5) EPI pack as well)."""
     from lfsr_amd.train_step import train_step
     for tag, A, s in (("a3h6w8s2", 3, 2), ("a5h8s4", 5, 4)):
         case, sd, x, _ = model_case("DistgSSR", tag)
@@ -347,20 +347,66 @@ def test_repack_modes_equal_eager(monkeypatch):
         label = torch.from_numpy(synth_input((xa.shape[0], 1, xa.shape[2] * s, xa.shape[3] * s), seed=2)).cuda()
         M = load_plugin()
         runs = []
-        for batch, graph in (("1", "1"), ("0", "1"), ("0", "0")):
-            monkeypatch.setenv("LFSR_PACK_BATCH", batch)
-            monkeypatch.setenv("LFSR_PACK_GRAPH", graph)
+        for batched in (True, False):
             net = build(M, A, s, sd)
+            if not batched:     # the plugin's repack through the per-parameter load
+                net._repack = lambda device, net=net: net._rt.load_state(net.state_dict().items(), device)
             opt = torch.optim.AdamW(net.parameters(), lr=2e-4, weight_decay=1e-4)
             crit = M.get_loss(None)
             losses = [float(train_step(net, crit, opt, xa, label)[0]) for _ in range(5)]
-            assert (net._pack_graph is not None) == (batch == "0" and graph == "1")
             runs.append((losses, [p.detach().clone() for p in net.parameters()]))
-        for r in runs[1:]:
-            assert runs[0][0] == r[0], tag
-            assert all(torch.equal(a, b) for a, b in zip(runs[0][1], r[1])), tag
-        assert runs[0][0][-1] < runs[0][0][0]      # and it trains
-    monkeypatch.delenv("LFSR_PACK_BATCH"); monkeypatch.delenv("LFSR_PACK_GRAPH")
+        assert runs[0][0] == runs[1][0], tag
+        assert all(torch.equal(a, b) for a, b in zip(runs[0][1], runs[1][1])), tag
+        assert runs[0][0][-1] < runs[0][0][0], tag      # and it trains
+        state = net.state_dict()
+        packed, outs = [], []
+        for batched in (True, False):
+            rt = capi.DistgSSRRuntime(A, s)
+            rt.packed = torch.zeros(rt.lib.lfsr_distgssr_packed_bytes(rt.ctx), dtype=torch.uint8, device=xa.device)   # bytes neither path writes compare equal
+            rt.load_state(state.items(), xa.device, batched=batched)
+            with torch.no_grad():
+                outs.append(rt.forward(xa))
+            packed.append(rt.packed)
+        assert torch.equal(packed[0], packed[1]), tag
+        assert torch.equal(outs[0], outs[1]), tag
+
+
+def test_fused_adamw_steps_repack():
+    """AdamW(fused=True) updates the parameters without bumping p._version: every training forward repacks, so after two steps a no-grad
+    forward equals that of a fresh model loaded from the updated state_dict, bit for bit"""
+    from lfsr_amd.train_step import train_step
+    A, s = 3, 2
+    case, sd, x, _ = model_case("DistgSSR", "a3h6w8s2")
+    M = load_plugin()
+    net = build(M, A, s, sd)
+    xa = torch.from_numpy(x).cuda()
+    label = torch.from_numpy(synth_input((xa.shape[0], 1, xa.shape[2] * s, xa.shape[3] * s), seed=2)).cuda()
+    opt = torch.optim.AdamW(net.parameters(), lr=1e-3, fused=True)
+    for _ in range(2):
+        train_step(net, M.get_loss(None), opt, xa, label)
+    with torch.no_grad():
+        y = net(xa, None)
+    upd = {k: v.detach().cpu().numpy() for k, v in net.state_dict().items()}
+    assert any(not np.array_equal(upd[k], sd[k]) for k in sd)
+    fresh = build(M, A, s, upd)
+    with torch.no_grad():
+        assert torch.equal(y, fresh(xa, None))
+
+
+def test_inference_between_training_forward_and_backward():
+    A, s = 3, 2
+    case, sd, x, _ = model_case("DistgSSR", "a3h6w8s2")
+    M = load_plugin()
+    net = build(M, A, s, sd)
+    xa = torch.from_numpy(x).cuda()
+    label = torch.from_numpy(synth_input((xa.shape[0], 1, xa.shape[2] * s, xa.shape[3] * s), seed=2)).cuda()
+    torch.nn.functional.l1_loss(net(xa, None), label).backward()
+    ref = net.grad_bucket.clone()
+    y = net(xa, None)
+    with torch.no_grad():
+        net(xa[:1], None)        # another shape: the inference workspace is replaced, the training one stays
+    torch.nn.functional.l1_loss(y, label).backward()
+    assert torch.equal(net.grad_bucket, ref)
 
 
 @pytest.mark.parametrize("ragged", [False, True])

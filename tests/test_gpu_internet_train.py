@@ -1,4 +1,4 @@
-"""GPU: LF_InterNet training through the HIP path (lfsr_internet_forward_train / _backward, the plugin's _InterNetFunction)."""
+"""GPU: LF_InterNet training through the HIP path (lfsr_internet_forward_train / _backward, the whole-model autograd node of lfsr_amd.hip_model)."""
 import json
 import os
 from argparse import Namespace
