@@ -12,6 +12,10 @@ Launch forms (both give the same ranks):
     torch or touched the GPU, relays rank 0's JSON line and exits with the worst child status;
   * `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`   -- torchrun provides the environment.
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints its line; its figures are the headline and what the timed steps
+record themselves (`roofline`, `multi_gpu`).  What takes work of its own -- `all_fp32_mfma`, `roofline_classes`, `kernel_ms_per_step`,
+`batch_split_max_abs_diff`, `other_workloads`, `cpu_baseline` -- runs after the timed steps and only with --full (~40 s, most of it `cpu_baseline`).
+
 One JSON line on rank 0.
   ms_per_step       wall time of one timed step (--steps of them, after --warmup untimed ones), max over ranks.
   dumped_outputs    (--dump-outputs DIR) what rank 0's timed path returned in its last step, written as DIR/<name>.npy: `sr` (infer, epit: the SR
@@ -23,13 +27,13 @@ One JSON line on rank 0.
                     / that op's average duration, measured with hipEvents on the launch stream inside the timed region;
                     `frac` = max(MFMA floor, HBM floor) / duration on that executed work -- a true roofline fraction (< 1).
                     The direct-conv-equivalent rate and the algorithmic speed-up over a direct conv are separate fields.
-  roofline_classes  one line per other kernel class of the forward (and the stand-alone SAI<->MacPI / PixelShuffle kernels),
+  roofline_classes  (--full) one line per other kernel class of the forward (and the stand-alone SAI<->MacPI / PixelShuffle kernels),
                     algorithmic bytes or flops / hipEvent time, against 8 TB/s (and the 6.3 TB/s a float4 copy reaches) or the
                     fp32 MFMA peak; taken in a separate untimed pass (events around every class cost ~0.8 ms per step).
-  other_workloads   (N = 1) configs[2] EPIT B = 8, configs[3] DistgSSR training step B = 8, configs[4] LFT 64-patch scene, run after the headline timing:
+  other_workloads   (--full, N = 1) configs[2] EPIT B = 8, configs[3] DistgSSR training step B = 8, configs[4] LFT 64-patch scene, run after the headline timing:
                     value, ms_per_step, arithmetic, the dominant operator's in-run duration (event hooks of the library) and its executed-work
                     roofline fraction; EPIT / LFT with their GEMMs on the three-term bf16 pipe and, beside it, with every GEMM on fp32 MFMA.
-  cpu_baseline      SURVEY 8d: oracle/lfsr_torch_port.py (stock torch CPU ops = what the reference's CPU path runs), fp32,
+  cpu_baseline      (--full) SURVEY 8d: oracle/lfsr_torch_port.py (stock torch CPU ops = what the reference's CPU path runs), fp32,
                     B = 4 chunks, thread count = a short sweep around the physical cores this process may use; plus one line
                     each for configs 1, 3, 5 (rank 0, N = 1 only; bounded to ~30-40 s).
 """
@@ -56,14 +60,17 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what takes work of its own: the all-fp32-MFMA headline, per-class kernel times and "
+                         "rooflines, the batch-independence check, configs[2] / [3] / [4] and the CPU baseline (off: only what the headline needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-split-check", action="store_true",
-                    help="skip the B = 1 re-runs of the batch-independence check (profiling passes: keeps every launch of a kernel the same size)")
+                    help="--full without the B = 1 re-runs of the batch-independence check (profiling passes: keeps every launch of a kernel the same size)")
     ap.add_argument("--rank-timeout", type=float, default=900.0, help="--gpus N self-launch: seconds after which a still-running rank is killed (with the others) and the run fails")
     ap.add_argument("--arithmetic", choices=["default", "f32"], default="default",
                     help="default: the GEMMs that have an exact-three-term-bf16 form run it (EPI branch, fuse.0, the transformers' linears / FFN / tail); "
                          "f32: every GEMM on fp32 MFMA (lfsr_set_arithmetic)")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the configs[2] / [3] / [4] lines (EPIT, training step, LFT scene) of the default run")
+    ap.add_argument("--no-other-workloads", action="store_true", help="--full without the configs[2] / [3] / [4] lines (EPIT, training step, LFT scene)")
     ap.add_argument("--scene-size", type=int, default=128, help="--workload lft: the scene is 5x5 views of SIZE x SIZE (128 -> 64 patches, the default; 512 -> 1024 "
                     "patches, i.e. 128 per GPU at 8 GPUs: the strong-scaling leg with every GPU's convs at full tile rounds)")
     ap.add_argument("--batch", type=int, default=0, help="patches per GPU (default: 32 infer, 8 train / epit / lft)")
@@ -623,31 +630,32 @@ def bench_infer(args, rank, world, dev, dist):
     el, y, seen = timed_loop(lambda: rt.forward(x), argparse.Namespace(warmup=0, steps=args.steps), dev, dist)
     prof = rt.profile_read()
     # the same timed loop with every GEMM of the forward on fp32 MFMA (lfsr_set_arithmetic(LFSR_ARITH_F32): the F(2,5) fp32 kernel of the EPI branch, fuse.0 on the
-    # fp32 row-GEMM): printed beside the headline whenever the headline uses the exact three-term bf16 form for those two operators
+    # fp32 row-GEMM): printed beside the headline whenever the headline uses the exact three-term bf16 form for those two operators.  It, the pass with events
+    # around every operator class and the checks below run only with --full, so a plain run ends with the timed steps.
     lab = "LFSR_LAB" in os.environ          # (the library's A/B selectors are live only then)
     user_sel = {k: (os.environ.get(k) if lab else None) for k in ("LFSR_EPI", "LFSR_ROWGEMM")}
     b3_ops = [] if args.arithmetic == "f32" else [k for k, v in user_sel.items() if not (v and v[:1] in ("w", "d", "f", "g", "1"))]
-    el_f32 = None
-    if b3_ops:
-        capi.set_arithmetic(capi.ARITH_F32)
-        for _ in range(2):
+    el_f32, prof_all, nb = None, None, 3
+    if args.full:
+        if b3_ops:
+            capi.set_arithmetic(capi.ARITH_F32)
+            for _ in range(2):
+                rt.forward(x)
+            el_f32, _, _ = timed_loop(lambda: rt.forward(x), argparse.Namespace(warmup=0, steps=args.steps), dev, dist)
+            capi.set_arithmetic(capi.ARITH_DEFAULT)
             rt.forward(x)
-        el_f32, _, _ = timed_loop(lambda: rt.forward(x), argparse.Namespace(warmup=0, steps=args.steps), dev, dist)
-        capi.set_arithmetic(capi.ARITH_DEFAULT)
-        rt.forward(x)
-    rt.profile(1)
-    nb = 3
-    for _ in range(nb):
-        rt.forward(x)
-    torch.cuda.synchronize()
-    prof_all = rt.profile_read()
+        rt.profile(1)
+        for _ in range(nb):
+            rt.forward(x)
+        torch.cuda.synchronize()
+        prof_all = rt.profile_read()
     rt.profile(0)
     if rank == 0:
         assert torch.isfinite(y).all()
         dumped = dump_outputs(args.dump_outputs, {"sr": y}) if args.dump_outputs else None
         # B = 32 forward == the same patches run one at a time (batch independence of the path; bit-equal expected)
         batch_split_max_abs_diff = None
-        if not args.no_split_check:
+        if args.full and not args.no_split_check:
             y1 = torch.cat([rt.forward(x[i:i + 1]) for i in (0, B - 1)], 0)
             batch_split_max_abs_diff = float((y1 - rt.forward(x)[[0, B - 1]]).abs().max())
         M = B * A * A * H * W
@@ -679,6 +687,7 @@ def bench_infer(args, rank, world, dev, dist):
                              "error against fp64 not above the fp32-MFMA kernels', tests/test_gpu_b3_accuracy.py; 3x3 convs, angular branch, init, head: fp32 MFMA)")
             line["config"]["gemm_arithmetic"] = {"conv3x3": "f32", "epiconv": "bf16x3" if "LFSR_EPI" in b3_ops else "f32", "fuse.0": "bf16x3" if "LFSR_ROWGEMM" in b3_ops else "f32",
                                                  "angconv": "f32", "head": "f32"}
+        if b3_ops and args.full:
             line["all_fp32_mfma"] = {"value": world * B * args.steps / el_f32, "unit": "patches/s", "ms_per_step": el_f32 / args.steps * 1e3, "dtype": "f32",
                                      "selection": "lfsr_set_arithmetic(LFSR_ARITH_F32) (same process, same weights, timed right after the headline loop)"}
         line["roofline"] = {
@@ -690,51 +699,52 @@ def bench_infer(args, rank, world, dev, dist):
             "algorithmic_speedup_over_direct_form": direct_flop / exec_flop,
             "note": "frac is on the work the kernel executes (Winograd domain), so it is a true fraction; direct_equivalent_tflops = SURVEY 8d's "
                     "2 x 576 x 64 x pixels / time may exceed the peak and is not a roofline figure"}
-        # per-class lines: algorithmic bytes (one read of every input + one write of every output, fp32) and flops per launch at this B
-        npx = float(M)
-        epi_b3, pw_b3 = "LFSR_EPI" in b3_ops, "LFSR_ROWGEMM" in b3_ops
-        cls_spec = {   # class -> (kernel, bound, bytes, flop)
-            # executed flops: stage 1 in Winograd F(2,5) form runs 6 products per 2 outputs instead of 10 (x 0.6; LFSR_EPI=direct: x 1.0); in the three-term bf16 form the
-            # direct sums run as six bf16 products each (x 6 on the bf16 pipe)
-            "epiconv": (("k_epi_b3 (both EPI passes, direct form, fp32 operands as three exact bf16 terms: six bf16 MFMA products per fp32 product; DistgSSR.py:91-97,108)", "mfma-bf16x3",
-                         (64 + 64) * npx * 4, 6 * 2 * (0.524e9 + 0.052e9) * B) if epi_b3 else
-                        ("k_epi_wino5 (both EPI passes: 1xA^2 conv 64->32 in F(2,5) form, LReLU, 1x1 32->160, LReLU, PixelShuffle1D; DistgSSR.py:91-97,108)", "mfma",
-                         (64 + 64) * npx * 4, 2 * (0.524e9 * (1.0 if os.environ.get("LFSR_EPI", "")[:1] == "d" else 0.6) + 0.052e9) * B)),
-            "pointwise": ("fuse.0 144->64 + LReLU (DistgSSR.py:98-100,109)" + (" on k_rowgemm_b3 (three-term bf16 operands, 144 of 160 operand columns valid)" if pw_b3 else ""), "hbm",
-                          (144 + 64) * npx * 4, 0.472e9 * B),
-            "angconv": ("k_ang_fused (AngConv.0 + LReLU + AngConv.2 + LReLU + PixelShuffle(A); DistgSSR.py:84-90)", "hbm", (64 + 16) * npx * 4, 0.065e9 * B),
-            "init_conv": ("k_initconv (SAI2MacPI + 3x3 1->64; DistgSSR.py:22,31-32)", "hbm", (1 + 64) * npx * 4, 0.029e9 * B),
-            "upsample_head": ("k_head<4> (MacPI2SAI + folded 64->16 1x1 + PixelShuffle(4) + bilinear skip; DistgSSR.py:24-35)", "hbm",
-                              (64 + 1 + 16) * npx * 4, 2.0 * 64 * 16 * npx),
-        }
-        classes = []
-        for cls, (kern, bound, nbytes, flop) in cls_spec.items():
-            ms, n = prof_all[cls]
-            if not n:
-                continue
-            us = ms / n * 1e3
-            e = {"class": cls, "kernel": kern, "bound": bound, "launches_per_step": n // nb, "bytes": nbytes, "flop": flop, "us": us,
-                 "TBps": nbytes / us / 1e6, "TFLOPs": flop / us / 1e6}
-            if bound == "hbm":
-                e.update(achieved=e["TBps"], unit="TB/s", frac=e["TBps"] / HBM_PEAK_TBPS, frac_of_copy=e["TBps"] / HBM_COPY_TBPS)
-            elif bound == "mfma-bf16x3":
-                e.update(achieved=e["TFLOPs"], unit="TFLOP/s (bf16 products executed)", frac=max(e["TFLOPs"] / BF16_MFMA_PEAK_TFLOPS, e["TBps"] / HBM_PEAK_TBPS),
-                         f32_equivalent_TFLOPs=e["TFLOPs"] / 6.0)
-            else:
-                e.update(achieved=e["TFLOPs"], unit="TFLOP/s", frac=e["TFLOPs"] / FP32_MFMA_PEAK_TFLOPS)
-            classes.append(e)
-        line["roofline_classes"] = classes + index_micro(dev)
         line["model_tflops"] = FLOP_PER_PATCH["distgssr"] * line["value"] / 1e12
-        line["kernel_ms_per_step"] = {k: v[0] / nb for k, v in prof_all.items()}
-        line["kernel_ms_per_step_note"] = f"separate untimed pass of {nb} steps with events around every operator class"
-        line["batch_split_max_abs_diff"] = batch_split_max_abs_diff
+        if args.full:
+            # per-class lines: algorithmic bytes (one read of every input + one write of every output, fp32) and flops per launch at this B
+            npx = float(M)
+            epi_b3, pw_b3 = "LFSR_EPI" in b3_ops, "LFSR_ROWGEMM" in b3_ops
+            cls_spec = {   # class -> (kernel, bound, bytes, flop)
+                # executed flops: stage 1 in Winograd F(2,5) form runs 6 products per 2 outputs instead of 10 (x 0.6; LFSR_EPI=direct: x 1.0); in the three-term bf16 form the
+                # direct sums run as six bf16 products each (x 6 on the bf16 pipe)
+                "epiconv": (("k_epi_b3 (both EPI passes, direct form, fp32 operands as three exact bf16 terms: six bf16 MFMA products per fp32 product; DistgSSR.py:91-97,108)", "mfma-bf16x3",
+                             (64 + 64) * npx * 4, 6 * 2 * (0.524e9 + 0.052e9) * B) if epi_b3 else
+                            ("k_epi_wino5 (both EPI passes: 1xA^2 conv 64->32 in F(2,5) form, LReLU, 1x1 32->160, LReLU, PixelShuffle1D; DistgSSR.py:91-97,108)", "mfma",
+                             (64 + 64) * npx * 4, 2 * (0.524e9 * (1.0 if os.environ.get("LFSR_EPI", "")[:1] == "d" else 0.6) + 0.052e9) * B)),
+                "pointwise": ("fuse.0 144->64 + LReLU (DistgSSR.py:98-100,109)" + (" on k_rowgemm_b3 (three-term bf16 operands, 144 of 160 operand columns valid)" if pw_b3 else ""), "hbm",
+                              (144 + 64) * npx * 4, 0.472e9 * B),
+                "angconv": ("k_ang_fused (AngConv.0 + LReLU + AngConv.2 + LReLU + PixelShuffle(A); DistgSSR.py:84-90)", "hbm", (64 + 16) * npx * 4, 0.065e9 * B),
+                "init_conv": ("k_initconv (SAI2MacPI + 3x3 1->64; DistgSSR.py:22,31-32)", "hbm", (1 + 64) * npx * 4, 0.029e9 * B),
+                "upsample_head": ("k_head<4> (MacPI2SAI + folded 64->16 1x1 + PixelShuffle(4) + bilinear skip; DistgSSR.py:24-35)", "hbm",
+                                  (64 + 1 + 16) * npx * 4, 2.0 * 64 * 16 * npx),
+            }
+            classes = []
+            for cls, (kern, bound, nbytes, flop) in cls_spec.items():
+                ms, n = prof_all[cls]
+                if not n:
+                    continue
+                us = ms / n * 1e3
+                e = {"class": cls, "kernel": kern, "bound": bound, "launches_per_step": n // nb, "bytes": nbytes, "flop": flop, "us": us,
+                     "TBps": nbytes / us / 1e6, "TFLOPs": flop / us / 1e6}
+                if bound == "hbm":
+                    e.update(achieved=e["TBps"], unit="TB/s", frac=e["TBps"] / HBM_PEAK_TBPS, frac_of_copy=e["TBps"] / HBM_COPY_TBPS)
+                elif bound == "mfma-bf16x3":
+                    e.update(achieved=e["TFLOPs"], unit="TFLOP/s (bf16 products executed)", frac=max(e["TFLOPs"] / BF16_MFMA_PEAK_TFLOPS, e["TBps"] / HBM_PEAK_TBPS),
+                             f32_equivalent_TFLOPs=e["TFLOPs"] / 6.0)
+                else:
+                    e.update(achieved=e["TFLOPs"], unit="TFLOP/s", frac=e["TFLOPs"] / FP32_MFMA_PEAK_TFLOPS)
+                classes.append(e)
+            line["roofline_classes"] = classes + index_micro(dev)
+            line["kernel_ms_per_step"] = {k: v[0] / nb for k, v in prof_all.items()}
+            line["kernel_ms_per_step_note"] = f"separate untimed pass of {nb} steps with events around every operator class"
+            line["batch_split_max_abs_diff"] = batch_split_max_abs_diff
         if dumped:
             line["dumped_outputs"] = dumped
-        if world == 1 and not args.no_other_workloads:
+        if args.full and world == 1 and not args.no_other_workloads:
             del rt
             torch.cuda.empty_cache()
             line["other_workloads"] = other_workloads(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(sd, x_np)
         print(json.dumps(line), flush=True)
     finish(dist)

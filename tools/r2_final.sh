@@ -4,7 +4,7 @@ export LFSR_LAB=1   # (A/B selectors of the library are live only under LFSR_LAB
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 O=$R/gpurun_out/r2/final; mkdir -p $O; rm -rf $O/prof_* $O/pmc_*
 cd $R
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 for wl in epit lft train; do timeout -k 10 300 python bench.py --workload $wl > $O/bench_$wl.json 2> $O/bench_$wl.err || exit 1; done
 # the same two transformer workloads with every GEMM on the fp32-MFMA kernels (the default runs the linears / FFN / tail on the bf16 pipe with exact three-term operands)
 for wl in epit lft; do LFSR_ROWGEMM=f32 LFSR_FFN=f32 LFSR_UPTAIL=v2 timeout -k 10 300 python bench.py --workload $wl > $O/bench_${wl}_f32.json 2> $O/bench_${wl}_f32.err || exit 1; done

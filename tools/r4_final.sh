@@ -1,10 +1,10 @@
 #!/bin/bash
-# round 4, final evidence: the default bench line (headline + all_fp32_mfma + other_workloads + cpu_baseline), the three other workloads' own lines, rocprofv3
+# round 4, final evidence: the --full bench line (headline + all_fp32_mfma + other_workloads + cpu_baseline), the three other workloads' own lines, rocprofv3
 # kernel-trace stats of each, FETCH_SIZE / WRITE_SIZE passes of the headline (separate --pmc passes, kernel trace only)
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=/root/repo
 O=$R/gpurun_out/r4/final; mkdir -p $O; rm -rf $O/prof_* $O/pmc_*
 cd $R
-timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 for wl in epit lft train; do timeout -k 10 300 python bench.py --workload $wl > $O/bench_$wl.json 2> $O/bench_$wl.err || exit 1; done
 for wl in epit lft; do timeout -k 10 300 python bench.py --workload $wl --arithmetic f32 > $O/bench_${wl}_f32.json 2> $O/bench_${wl}_f32.err || exit 1; done
 python - <<'PY'
