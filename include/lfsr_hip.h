@@ -325,6 +325,25 @@ int lfsr_lft_finalize(lfsr_lft* ctx, void* stream);
 size_t lfsr_lft_workspace_bytes(const lfsr_lft* ctx, int B, int h, int w);
 int lfsr_lft_forward(lfsr_lft* ctx, const float* x, float* out, int B, int h, int w, void* workspace, size_t workspace_bytes,
                      void* stream);
+/* ---- LFT training: the same contract as the LF_InterNet training ABI.  Gradients go into ONE flat fp32 bucket in state_dict order (78 tensors
+ * at n_layer = 4; the packed table's internal entries MLP.weight#lo / #hi are not parameters and lfsr_lft_param_offset refuses them).
+ * forward_train runs the inference forward's launches (bit-identical output in either arithmetic) and keeps the sublayer inputs the backward
+ * reads; the backward recomputes LayerNorm statistics, feed-forward hidden rows and the HR map.  The workspace must be the same memory for
+ * forward_train and the backward that follows.  train_workspace_bytes returns 0 for a geometry the path refuses (every activation, the
+ * 64 s^2-float HR rows included, below 2 GiB). */
+size_t lfsr_lft_num_params(const lfsr_lft* ctx);
+int lfsr_lft_param_offset(const lfsr_lft* ctx, const char* key, size_t* offset, size_t* numel);
+size_t lfsr_lft_train_workspace_bytes(const lfsr_lft* ctx, int B, int h, int w);
+int lfsr_lft_forward_train(lfsr_lft* ctx, const float* x, float* out, int B, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
+/* parity aid: offset (floats, into the training workspace) and size of an activation forward_train saved (VCL rows).  which: 0 the input of
+ * AltFilter `index` (64; index = n_layer: the tail's input), 1 the angular feed-forward input (64), 2 the spatial feed-forward input (128),
+ * 3 the spatial tokens (128), 4 the spatial feed-forward output (128) of layer `index`; 5 conv_init's LeakyReLU outputs (64; index 0 / 1).
+ * After a backward, what it rebuilt and took its ReLU / LeakyReLU decisions from: 6 / 7 the angular (128) / spatial (256) feed-forward hidden
+ * rows after the ReLU of layer `index`, 8 conv_init.4's LeakyReLU output without the residual (64), 9 the HR pre-activation ((B, A h s, A w s, 64)). */
+int lfsr_lft_train_saved(const lfsr_lft* ctx, int B, int h, int w, int which, int index, size_t* offset_floats, size_t* numel);
+/* dout (B,1,A*h*s,A*w*s) = dLoss/dOut; grads: n_grads == lfsr_lft_num_params(ctx) floats, overwritten */
+int lfsr_lft_backward(lfsr_lft* ctx, const float* x, const float* dout, int B, int h, int w, void* workspace, size_t workspace_bytes,
+                      float* grads, size_t n_grads, void* stream);
 
 /* ---- "next" rows: the steps either side of the hot path in the training loop, on the device ----
  * N2: cal_metrics (utils/utils.py:91-134): per-view PSNR (and SSIM, skimage semantics with gaussian_weights=True) of two

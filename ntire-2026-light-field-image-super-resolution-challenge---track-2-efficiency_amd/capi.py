@@ -86,6 +86,12 @@ SIGNATURES = {
     "lfsr_lft_finalize": (c_i, [c_p, c_p]),
     "lfsr_lft_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
     "lfsr_lft_forward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "lfsr_lft_num_params": (c_sz, [c_p]),
+    "lfsr_lft_param_offset": (c_i, [c_p, C.c_char_p, C.POINTER(c_sz), C.POINTER(c_sz)]),
+    "lfsr_lft_train_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
+    "lfsr_lft_forward_train": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p]),
+    "lfsr_lft_train_saved": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_sz), C.POINTER(c_sz)]),
+    "lfsr_lft_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p, c_sz, c_p]),
     "lfsr_linear_fwd": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_i, C.c_longlong, c_i, c_f, c_p]),
     "lfsr_ycbcr2rgb_views": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, C.POINTER(C.c_double), C.POINTER(C.c_double), c_p]),
     "lfsr_ffn_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_i, C.c_longlong, c_i, c_i, c_i, c_f, c_p]),
@@ -394,7 +400,7 @@ class GraphedForward:
 
 # ---------------------------------------------------------------------------------------------------
 # whole-model runtimes: every model drives one C-ABI life cycle, lfsr_<name>_create / packed_bytes / set_packed / load_param /
-# finalize / workspace_bytes / forward; the trainable ones (distgssr, internet) add num_params / param_offset /
+# finalize / workspace_bytes / forward; the trainable ones (distgssr, internet, lft) add num_params / param_offset /
 # train_workspace_bytes / forward_train / train_saved / backward
 # ---------------------------------------------------------------------------------------------------
 

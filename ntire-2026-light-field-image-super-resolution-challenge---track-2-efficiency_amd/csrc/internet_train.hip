@@ -223,6 +223,12 @@ std::vector<std::pair<std::string, size_t>> bucket_order(const lfsr_internet* c)
 
 }  // namespace
 
+int lfsr_pack_T_from_fwd(const float* Wp, float* out, int T, int Npad_in, int C, int O, int k0, int Kc, int flip, hipStream_t st) {
+  hipLaunchKernelGGL(k_pack_T_from_fwd, dim3(cap_grid((long long)T * Kc * O)), dim3(256), 0, st, Wp, out, T, Npad_in, C, O, k0, Kc, flip);
+  LFSR_CHECK_LAUNCH();
+  return LFSR_OK;
+}
+
 extern "C" {
 
 size_t lfsr_internet_num_params(const lfsr_internet* c) {

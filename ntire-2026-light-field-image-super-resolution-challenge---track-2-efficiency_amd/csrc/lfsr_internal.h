@@ -156,6 +156,8 @@ int lfsr_head_fold_bwd(const float* dWf, const float* colsum_partial, int nblk, 
 int lfsr_init_gather9(const float* x, float* xg, int B, int A, int h, int w, hipStream_t st);
 int lfsr_add_inplace(float* a, const float* b, long long n, hipStream_t st);   // a += b
 int lfsr_pack_weight_chunkT(const float* w, float* out, int O, int C, int ch, int perm, hipStream_t st);
+// internet_train.hip: dgrad pack from a forward pack Wp[T][Npad_in][C]: out[t'][k'][n] = Wp[flip ? T-1-t' : t'][n][k0 + k'] (n < O, k' < Kc)
+int lfsr_pack_T_from_fwd(const float* Wp, float* out, int T, int Npad_in, int C, int O, int k0, int Kc, int flip, hipStream_t st);
 
 // rowgemm.hip: persistent row-streaming GEMM with LDS-resident weights; LFSR_E_ARG = shape not covered (use the gather-GEMM)
 int lfsr_rowgemm_dgrad144_launch(const float* dy, int dy_stride, int dy_choff, const float* wT_packed, const float* mk, int mk_stride, int mk_choff, float mk_slope,

@@ -1,6 +1,6 @@
 """LFT plugin (drop-in for the reference's ``model/SR/LFT.py``): ``get_model`` / ``get_loss`` / ``weights_init`` with the
-reference's state_dict key names and shapes; ``forward`` runs in the gfx950 HIP library through the C ABI
-(inference; the backward of the transformer models is not built)."""
+reference's state_dict key names and shapes; ``forward`` runs in the gfx950 HIP library through the C ABI, and
+with grad enabled so does the backward (lfsr_amd.hip_model)."""
 import math
 
 import torch
@@ -55,7 +55,6 @@ class _AltFilter(_Holder):
 
 class get_model(HipModel):
     hip_name = "LFT"
-    inference_only = "LFT HIP backward is not built: call under torch.no_grad()"
 
     def __init__(self, args):
         super().__init__()
