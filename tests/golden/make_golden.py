@@ -113,8 +113,8 @@ def gen_index_ops(out):
 MODEL_CASES = {
     # name: list of (tag, A, h, w, s, B)
     "DistgSSR": [("a5h8s4", 5, 8, 8, 4, 1), ("a3h6w8s2", 3, 6, 8, 2, 2)],
-    "EPIT": [("a5h8s4", 5, 8, 8, 4, 1), ("a3h6w8s2", 3, 6, 8, 2, 2)],
-    "LFT": [("a5h8s4", 5, 8, 8, 4, 1), ("a3h6w8s2", 3, 6, 8, 2, 2)],
+    "EPIT": [("a5h8s4", 5, 8, 8, 4, 1), ("a3h6w8s2", 3, 6, 8, 2, 2), ("a3h6w8s3", 3, 6, 8, 3, 2)],
+    "LFT": [("a5h8s4", 5, 8, 8, 4, 1), ("a3h6w8s2", 3, 6, 8, 2, 2), ("a3h6w8s3", 3, 6, 8, 3, 2)],
     "LF_InterNet": [("a5h8s2", 5, 8, 8, 2, 1), ("a3h6w8s4", 3, 6, 8, 4, 2)],
 }
 FULL_CASES = {"DistgSSR": (5, 32, 32, 4, 1), "EPIT": (5, 32, 32, 4, 1), "LFT": (5, 32, 32, 4, 1), "LF_InterNet": (5, 32, 32, 2, 1)}

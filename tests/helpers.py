@@ -1,3 +1,4 @@
+import contextlib
 import json
 import os
 
@@ -20,6 +21,24 @@ def model_case(name, tag):
     x = synth_input((case["B"], 1, case["A"] * case["h"], case["A"] * case["w"]), seed=1)
     npz = np.load(os.path.join(GOLDEN, f"model_{name}.npz"))
     return case, sd, x, npz
+
+
+def model_spec(name, A, s):
+    """(key, shape) list of `name` at angRes A and scale s: the golden case with that angRes, with upsampling.0 (64 s^2 outputs: the one
+    parameter whose shape follows the scale) resized"""
+    case = next(c for c in models_meta()["models"][name]["cases"].values() if c["A"] == A)
+    return [(k, (64 * s * s,) + tuple(sh[1:]) if k == "upsampling.0.weight" else tuple(sh)) for k, sh in case["spec"]]
+
+
+@contextlib.contextmanager
+def arithmetic(mode):
+    """lfsr_set_arithmetic(mode) for the block, the default again after it (the setting is process-wide)"""
+    from lfsr_amd import capi
+    capi.set_arithmetic(mode)
+    try:
+        yield
+    finally:
+        capi.set_arithmetic(capi.ARITH_DEFAULT)
 
 
 def psnr(a, b):

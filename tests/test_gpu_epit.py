@@ -7,9 +7,9 @@ import pytest
 import torch
 
 from lfsr_amd import capi
-from lfsr_amd.synth import synth_input
+from lfsr_amd.synth import synth_input, synth_state_dict
 from oracle import lfsr_oracle as O
-from tests.helpers import model_case, psnr
+from tests.helpers import arithmetic, model_case, model_spec, psnr
 
 pytestmark = pytest.mark.gpu
 ATOL = 1e-4
@@ -175,13 +175,61 @@ def test_epi_attention_vs_masked_mha(vertical, geom, path, monkeypatch):
     assert np.abs(got - ref_seq).max() < 1e-5
 
 
-TAGS = ["a5h8s4", "a3h6w8s2"]
+TAGS = ["a5h8s4", "a3h6w8s2", "a3h6w8s3"]     # a3h6w8s3: scale 3, the two-kernel tail (lfsr_upsample_ps_fwd + lfsr_hr_tail_fwd)
 
 
 def runtime(case, sd):
     rt = capi.ModelRuntime("epit", case["A"], case["s"], 5, 64)
     rt.load_state([(k, dev(v)) for k, v in sd.items()], torch.device("cuda", 0))
     return rt
+
+
+@pytest.mark.parametrize("tag", ["a5h8s4", "a3h6w8s2"])
+def test_epit_fp32_arithmetic_vs_golden_and_oracle(tag):
+    """lfsr_set_arithmetic(LFSR_ARITH_F32): every GEMM on fp32 MFMA, the up-sampling tail as k_up_tail2"""
+    case, sd, x, npz = model_case("EPIT", tag)
+    rt = runtime(case, sd)
+    with arithmetic(capi.ARITH_F32):
+        y = rt.forward(dev(x)).cpu().numpy()
+    gold = npz[tag + "_out"]
+    assert np.abs(y - O.epit_forward(x, sd, case["A"], case["s"])).max() < ATOL
+    assert np.abs(y - gold).max() < ATOL
+    assert psnr(y, gold) >= 80.0
+
+
+@pytest.mark.parametrize("arith", ["default", "f32"])
+def test_epit_5x5_ragged_geometry_vs_oracle(arith):
+    """h = 13, w = 16, B = 2: EPI lines of 80 / 65 tokens, a mosaic ragged against the tail's 4 x 32 tiles, the whole output against the fp64 oracle"""
+    A, s, B, h, w = 5, 4, 2, 13, 16
+    sd = synth_state_dict(model_spec("EPIT", A, s), seed=0)
+    x = synth_input((B, 1, A * h, A * w), seed=9)
+    rt = runtime(dict(A=A, s=s), sd)
+    with arithmetic(capi.ARITH_F32 if arith == "f32" else capi.ARITH_DEFAULT):
+        y = rt.forward(dev(x)).cpu().numpy()
+    assert np.abs(y - O.epit_forward(x, sd, A, s)).max() < ATOL
+
+
+@pytest.mark.parametrize("A,h,w,B", [(3, 6, 8, 2), (5, 8, 8, 1)])
+def test_epit_scale3_vs_oracle(A, h, w, B):
+    s = 3
+    sd = synth_state_dict(model_spec("EPIT", A, s), seed=0)
+    x = synth_input((B, 1, A * h, A * w), seed=1)
+    y = runtime(dict(A=A, s=s), sd).forward(dev(x)).cpu().numpy()
+    assert y.shape == (B, 1, A * h * s, A * w * s)
+    assert np.abs(y - O.epit_forward(x, sd, A, s)).max() < ATOL
+
+
+@pytest.mark.parametrize("tag", ["a5h8s4", "a3h6w8s2"])
+def test_epit_two_kernel_tail_at_scales_2_and_4(tag, monkeypatch):
+    """LFSR_NO_UPTAIL: the tail as lfsr_upsample_ps_fwd + lfsr_hr_tail_fwd, against the oracle and against the fused tail"""
+    case, sd, x, npz = model_case("EPIT", tag)
+    rt = runtime(case, sd)
+    monkeypatch.delenv("LFSR_NO_UPTAIL", raising=False)
+    y1 = rt.forward(dev(x)).cpu().numpy()
+    monkeypatch.setenv("LFSR_NO_UPTAIL", "1")
+    y2 = rt.forward(dev(x)).cpu().numpy()
+    assert np.abs(y2 - O.epit_forward(x, sd, case["A"], case["s"])).max() < ATOL
+    assert np.abs(y2 - y1).max() < ATOL
 
 
 @pytest.mark.parametrize("ln_fuse", ["default", "0", "1"])   # default: all norms inside the consuming kernels / every norm its own launch / only the feed-forward norm fused

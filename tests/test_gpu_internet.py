@@ -8,7 +8,7 @@ import torch
 
 from lfsr_amd import capi
 from oracle import lfsr_oracle as O
-from tests.helpers import model_case, psnr
+from tests.helpers import arithmetic, model_case, psnr
 
 pytestmark = pytest.mark.gpu
 
@@ -31,6 +31,19 @@ def test_internet_small_vs_golden_and_oracle(tag):
     ref = O.internet_forward(x, sd, case["A"], case["s"])
     tol = 1e-4 * max(1.0, np.abs(gold).max())
     assert np.abs(y - ref).max() < tol
+    assert np.abs(y - gold).max() < tol
+
+
+@pytest.mark.parametrize("tag", ["a5h8s2", "a3h6w8s4"])
+def test_internet_fp32_arithmetic_vs_golden_and_oracle(tag):
+    """lfsr_set_arithmetic(LFSR_ARITH_F32): every GEMM that has a three-term bf16 form on fp32 MFMA instead"""
+    case, sd, x, npz = model_case("LF_InterNet", tag)
+    rt = runtime(case, sd)
+    with arithmetic(capi.ARITH_F32):
+        y = rt.forward(dev(x)).cpu().numpy()
+    gold = npz[tag + "_out"]
+    tol = 1e-4 * max(1.0, np.abs(gold).max())
+    assert np.abs(y - O.internet_forward(x, sd, case["A"], case["s"])).max() < tol
     assert np.abs(y - gold).max() < tol
 
 

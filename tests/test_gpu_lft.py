@@ -8,9 +8,9 @@ import torch
 
 from lfsr_amd import capi
 from lfsr_amd.dispatch import sr_scene
-from lfsr_amd.synth import synth_input
+from lfsr_amd.synth import synth_input, synth_state_dict
 from oracle import lfsr_oracle as O
-from tests.helpers import model_case, psnr
+from tests.helpers import arithmetic, model_case, model_spec, psnr
 
 pytestmark = pytest.mark.gpu
 ATOL = 1e-4
@@ -84,7 +84,7 @@ def test_angular_attention_vs_mha(B, A, h, w):
 
 
 @pytest.mark.parametrize("ln_fuse", ["default", "0", "1"])   # default: all norms inside the consuming kernels / every norm its own launch / only the feed-forward norms fused
-@pytest.mark.parametrize("tag", ["a5h8s4", "a3h6w8s2"])
+@pytest.mark.parametrize("tag", ["a5h8s4", "a3h6w8s2", "a3h6w8s3"])     # a3h6w8s3: scale 3, the two-kernel tail
 def test_lft_small_vs_golden_and_oracle(tag, ln_fuse, monkeypatch):
     if ln_fuse == "default":
         monkeypatch.delenv("LFSR_LN_FUSE", raising=False)
@@ -97,6 +97,71 @@ def test_lft_small_vs_golden_and_oracle(tag, ln_fuse, monkeypatch):
     assert np.abs(y - ref).max() < ATOL
     assert np.abs(y - gold).max() < ATOL
     assert psnr(y, gold) >= 80.0
+
+
+@pytest.mark.parametrize("tag", ["a5h8s4", "a3h6w8s2"])
+def test_lft_fp32_arithmetic_vs_golden_and_oracle(tag):
+    """lfsr_set_arithmetic(LFSR_ARITH_F32): every GEMM on fp32 MFMA, the up-sampling tail as k_up_tail2"""
+    case, sd, x, npz = model_case("LFT", tag)
+    rt = runtime(case, sd)
+    with arithmetic(capi.ARITH_F32):
+        y = rt.forward(dev(x)).cpu().numpy()
+    gold = npz[tag + "_out"]
+    assert np.abs(y - O.lft_forward(x, sd, case["A"], case["s"])).max() < ATOL
+    assert np.abs(y - gold).max() < ATOL
+    assert psnr(y, gold) >= 80.0
+
+
+@pytest.mark.parametrize("arith", ["default", "f32"])
+def test_lft_5x5_ragged_geometry_vs_oracle(arith):
+    """h = 13, w = 15, B = 2: two strips of spatial-attention queries per view (the second ragged), the h-for-w column clamp cutting windows (13 < 15), a
+    mosaic ragged against the tail's 4 x 32 tiles; the whole output against the fp64 oracle.  (w stays below h + 3: past it the clamp leaves queries without
+    keys, and the reference's softmax over an all -inf mask row gives NaN.)"""
+    A, s, B, h, w = 5, 4, 2, 13, 15
+    sd = synth_state_dict(model_spec("LFT", A, s), seed=0)
+    x = synth_input((B, 1, A * h, A * w), seed=9)
+    rt = runtime(dict(A=A, s=s), sd)
+    with arithmetic(capi.ARITH_F32 if arith == "f32" else capi.ARITH_DEFAULT):
+        y = rt.forward(dev(x)).cpu().numpy()
+    assert np.abs(y - O.lft_forward(x, sd, A, s)).max() < ATOL
+
+
+def test_lft_arithmetic_switch_on_one_runtime():
+    """default -> F32 -> default on one runtime: the F32 output holds the gate and is not the default's; the default comes back bit for bit"""
+    case, sd, x, npz = model_case("LFT", "a3h6w8s2")
+    rt = runtime(case, sd)
+    xd = dev(x)
+    y0 = rt.forward(xd).cpu().numpy()
+    with arithmetic(capi.ARITH_F32):
+        y1 = rt.forward(xd).cpu().numpy()
+    y2 = rt.forward(xd).cpu().numpy()
+    ref = O.lft_forward(x, sd, case["A"], case["s"])
+    assert np.abs(y1 - ref).max() < ATOL
+    assert not np.array_equal(y1, y0)
+    assert np.array_equal(y2, y0)
+
+
+@pytest.mark.parametrize("A,h,w,B", [(3, 6, 8, 2), (5, 8, 8, 1)])
+def test_lft_scale3_vs_oracle(A, h, w, B):
+    s = 3
+    sd = synth_state_dict(model_spec("LFT", A, s), seed=0)
+    x = synth_input((B, 1, A * h, A * w), seed=1)
+    y = runtime(dict(A=A, s=s), sd).forward(dev(x)).cpu().numpy()
+    assert y.shape == (B, 1, A * h * s, A * w * s)
+    assert np.abs(y - O.lft_forward(x, sd, A, s)).max() < ATOL
+
+
+@pytest.mark.parametrize("tag", ["a5h8s4", "a3h6w8s2"])
+def test_lft_two_kernel_tail_at_scales_2_and_4(tag, monkeypatch):
+    """LFSR_NO_UPTAIL: the tail as lfsr_upsample_ps_fwd + lfsr_hr_tail_fwd, against the oracle and against the fused tail"""
+    case, sd, x, npz = model_case("LFT", tag)
+    rt = runtime(case, sd)
+    monkeypatch.delenv("LFSR_NO_UPTAIL", raising=False)
+    y1 = rt.forward(dev(x)).cpu().numpy()
+    monkeypatch.setenv("LFSR_NO_UPTAIL", "1")
+    y2 = rt.forward(dev(x)).cpu().numpy()
+    assert np.abs(y2 - O.lft_forward(x, sd, case["A"], case["s"])).max() < ATOL
+    assert np.abs(y2 - y1).max() < ATOL
 
 
 def test_lft_full_patch_and_scene():

@@ -170,6 +170,26 @@ def test_baseline_geometry_against_fp64(fp64_port):
     assert mx0 <= 1e-2
 
 
+def test_scale3_grads_match_fp64_port_and_bucket(fp64_port):
+    """s = 3: the training forward's two-kernel tail, k_tail_bwd with s^2 = 9 (its element-wise store branch) and k_pack_up0_T with s2 = 9; every parameter's
+    gradient against the fp64 port with the HIP path's ReLU / LeakyReLU decisions, the bucket against the concatenated .grad"""
+    A, s, B, h, w = 3, 3, 2, 6, 8
+    sd = spec_sd(A, s)
+    net, _ = make_net(A, s, sd)
+    x = synth_input((B, 1, A * h, A * w), seed=1)
+    label = synth_input((B, 1, A * h * s, A * w * s), seed=2)
+    xg = torch.from_numpy(x).cuda()
+    loss, bucket, out = hip_step(net, xg, torch.from_numpy(label).cuda())
+    forced, flips = forced_fp64_grads(net._rt, xg, sd, x, label, A, s)
+    print(f"s=3: ReLU / LeakyReLU decisions of the HIP path that differ from fp64: {flips}")
+    for k, p in net.named_parameters():
+        assert rel(p.grad.detach().cpu().numpy(), forced[k]) < 1e-4, k
+    cat = torch.cat([p.grad.reshape(-1) for p in net.parameters()])
+    assert torch.equal(cat, net.grad_bucket)
+    ref_out = P.lft_forward.__wrapped__(torch.as_tensor(x).double(), {k: torch.tensor(v, dtype=torch.float64) for k, v in sd.items()}, A, s)
+    assert float((out.cpu().double() - ref_out).abs().max()) < 1e-4
+
+
 @pytest.mark.parametrize("arith", ["default", "f32"])
 def test_train_forward_output_bit_equal_to_inference(arith):
     case, sd, x, _ = model_case("LFT", "a3h6w8s2")

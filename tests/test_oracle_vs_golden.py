@@ -102,7 +102,7 @@ def test_interp_against_torch():
     torch = pytest.importorskip("torch")
     import torch.nn.functional as F
     x = np.random.default_rng(0).random((2, 1, 7, 9))
-    for s in (2, 4):
+    for s in (2, 3, 4):
         tb = F.interpolate(torch.from_numpy(x), scale_factor=s, mode="bilinear", align_corners=False).numpy()
         tc = F.interpolate(torch.from_numpy(x), scale_factor=s, mode="bicubic", align_corners=False).numpy()
         assert np.abs(O.interp_bilinear(x, s) - tb).max() < 1e-12
@@ -119,7 +119,7 @@ def test_torch_port_distgssr(tag):
     assert np.abs(y - npz[tag + "_out"]).max() < 1e-5
 
 
-@pytest.mark.parametrize("name,tag", [("EPIT", "a5h8s4"), ("EPIT", "a3h6w8s2"), ("LFT", "a5h8s4"), ("LFT", "a3h6w8s2"),
+@pytest.mark.parametrize("name,tag", [("EPIT", "a5h8s4"), ("EPIT", "a3h6w8s2"), ("EPIT", "a3h6w8s3"), ("LFT", "a5h8s4"), ("LFT", "a3h6w8s2"), ("LFT", "a3h6w8s3"),
                                       ("LF_InterNet", "a5h8s2"), ("LF_InterNet", "a3h6w8s4")])
 def test_torch_port_other_models(name, tag):
     """the torch-CPU forms timed as bench.py's cpu_baseline lines for configs 1, 3, 5 against the reference's outputs"""
@@ -131,7 +131,7 @@ def test_torch_port_other_models(name, tag):
     assert np.abs(y - npz[tag + "_out"]).max() < 1e-5
 
 
-@pytest.mark.parametrize("tag", ["a5h8s4", "a3h6w8s2"])
+@pytest.mark.parametrize("tag", ["a5h8s4", "a3h6w8s2", "a3h6w8s3"])
 def test_epit_small(tag):
     case, sd, x, npz = model_case("EPIT", tag)
     y = O.epit_forward(x, sd, case["A"], case["s"])
@@ -141,7 +141,7 @@ def test_epit_small(tag):
     assert psnr(y, g) > 95.0
 
 
-@pytest.mark.parametrize("tag", ["a5h8s4", "a3h6w8s2"])
+@pytest.mark.parametrize("tag", ["a5h8s4", "a3h6w8s2", "a3h6w8s3"])
 def test_lft_small(tag):
     case, sd, x, npz = model_case("LFT", tag)
     y = O.lft_forward(x, sd, case["A"], case["s"])
