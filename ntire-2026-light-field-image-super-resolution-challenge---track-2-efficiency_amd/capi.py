@@ -17,7 +17,7 @@ c_i = C.c_int
 c_f = C.c_float
 c_sz = C.c_size_t
 
-# name -> (restype, argtypes): mirrors include/lfsr_hip.h line by line
+# name -> (restype, argtypes): mirrors include/lfsr_hip.h (the model life cycles are added below, from _MODELS)
 SIGNATURES = {
     "lfsr_version": (C.c_char_p, []),
     "lfsr_sai2macpi": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
@@ -42,56 +42,14 @@ SIGNATURES = {
     "lfsr_initconv_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_fold_head": (c_i, [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p]),
     "lfsr_upsample_head_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "lfsr_distgssr_create": (c_i, [C.POINTER(c_p), c_i, c_i, c_i, c_i, c_i]),
-    "lfsr_distgssr_destroy": (None, [c_p]),
-    "lfsr_distgssr_packed_bytes": (c_sz, [c_p]),
-    "lfsr_distgssr_set_packed": (c_i, [c_p, c_p, c_sz]),
-    "lfsr_distgssr_load_param": (c_i, [c_p, C.c_char_p, c_p, c_sz, c_p]),
-    "lfsr_distgssr_finalize": (c_i, [c_p, c_p]),
     "lfsr_distgssr_begin_batched_load": (c_i, [c_p]),
-    "lfsr_distgssr_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
-    "lfsr_distgssr_forward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p]),
     "lfsr_distgssr_forward_taps": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, C.POINTER(c_p), c_p]),
-    "lfsr_distgssr_num_params": (c_sz, [c_p]),
-    "lfsr_distgssr_param_offset": (c_i, [c_p, C.c_char_p, C.POINTER(c_sz), C.POINTER(c_sz)]),
-    "lfsr_distgssr_train_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
-    "lfsr_distgssr_forward_train": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p]),
-    "lfsr_distgssr_train_saved": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_sz), C.POINTER(c_sz)]),
-    "lfsr_distgssr_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p, c_sz, c_p]),
     "lfsr_layernorm_fwd": (c_i, [c_p, c_i, c_i, c_p, c_i, C.c_longlong, C.c_longlong, c_p, c_p, c_p, c_i, c_i, C.c_longlong, c_i, c_f, c_p]),
     "lfsr_conv3x3_n_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
     "lfsr_lft_position_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_view_metrics": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_mask_views": (c_i, [c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_mask_views_fill": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
-    "lfsr_internet_create": (c_i, [C.POINTER(c_p), c_i, c_i, c_i, c_i]),
-    "lfsr_internet_destroy": (None, [c_p]),
-    "lfsr_internet_packed_bytes": (c_sz, [c_p]),
-    "lfsr_internet_set_packed": (c_i, [c_p, c_p, c_sz]),
-    "lfsr_internet_load_param": (c_i, [c_p, C.c_char_p, c_p, c_sz, c_p]),
-    "lfsr_internet_finalize": (c_i, [c_p, c_p]),
-    "lfsr_internet_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
-    "lfsr_internet_forward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p]),
-    "lfsr_internet_num_params": (c_sz, [c_p]),
-    "lfsr_internet_param_offset": (c_i, [c_p, C.c_char_p, C.POINTER(c_sz), C.POINTER(c_sz)]),
-    "lfsr_internet_train_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
-    "lfsr_internet_forward_train": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p]),
-    "lfsr_internet_train_saved": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_sz), C.POINTER(c_sz)]),
-    "lfsr_internet_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p, c_sz, c_p]),
-    "lfsr_lft_create": (c_i, [C.POINTER(c_p), c_i, c_i, c_i, c_i]),
-    "lfsr_lft_destroy": (None, [c_p]),
-    "lfsr_lft_packed_bytes": (c_sz, [c_p]),
-    "lfsr_lft_set_packed": (c_i, [c_p, c_p, c_sz]),
-    "lfsr_lft_load_param": (c_i, [c_p, C.c_char_p, c_p, c_sz, c_p]),
-    "lfsr_lft_finalize": (c_i, [c_p, c_p]),
-    "lfsr_lft_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
-    "lfsr_lft_forward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p]),
-    "lfsr_lft_num_params": (c_sz, [c_p]),
-    "lfsr_lft_param_offset": (c_i, [c_p, C.c_char_p, C.POINTER(c_sz), C.POINTER(c_sz)]),
-    "lfsr_lft_train_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
-    "lfsr_lft_forward_train": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p]),
-    "lfsr_lft_train_saved": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_sz), C.POINTER(c_sz)]),
-    "lfsr_lft_backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p, c_sz, c_p]),
     "lfsr_linear_fwd": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_i, C.c_longlong, c_i, c_f, c_p]),
     "lfsr_ycbcr2rgb_views": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, C.POINTER(C.c_double), C.POINTER(C.c_double), c_p]),
     "lfsr_ffn_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_i, C.c_longlong, c_i, c_i, c_i, c_f, c_p]),
@@ -102,14 +60,6 @@ SIGNATURES = {
     "lfsr_upsample_ps_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_up_tail_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
     "lfsr_hr_tail_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
-    "lfsr_epit_create": (c_i, [C.POINTER(c_p), c_i, c_i, c_i, c_i]),
-    "lfsr_epit_destroy": (None, [c_p]),
-    "lfsr_epit_packed_bytes": (c_sz, [c_p]),
-    "lfsr_epit_set_packed": (c_i, [c_p, c_p, c_sz]),
-    "lfsr_epit_load_param": (c_i, [c_p, C.c_char_p, c_p, c_sz, c_p]),
-    "lfsr_epit_finalize": (c_i, [c_p, c_p]),
-    "lfsr_epit_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
-    "lfsr_epit_forward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p]),
     "lfsr_packed_weight_tr_floats": (c_sz, [c_i, c_i, c_i]),
     "lfsr_pack_conv_weight_tr": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p]),
     "lfsr_conv3x3_dgrad": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_f, c_i, c_i, c_i, c_p]),
@@ -135,6 +85,35 @@ SIGNATURES = {
     "lfsr_distgssr_profile": (c_i, [c_p, c_i]),
     "lfsr_distgssr_profile_read": (c_i, [c_p, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
 }
+
+
+def _model_signatures(name, n_create_ints, trainable):
+    """the C life cycle of one model (what ModelRuntime drives): lfsr_<name>_create (ctx**, A, scale and n_create_ints more ints), destroy,
+    packed_bytes, set_packed, load_param, finalize, workspace_bytes, forward; the trainable ones add num_params, param_offset,
+    train_workspace_bytes, forward_train, train_saved, backward"""
+    fwd = [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p]          # ctx, x, out, B, h, w, workspace, workspace_bytes, stream
+    sig = {"create": (c_i, [C.POINTER(c_p), c_i, c_i] + [c_i] * n_create_ints),
+           "destroy": (None, [c_p]),
+           "packed_bytes": (c_sz, [c_p]),
+           "set_packed": (c_i, [c_p, c_p, c_sz]),
+           "load_param": (c_i, [c_p, C.c_char_p, c_p, c_sz, c_p]),
+           "finalize": (c_i, [c_p, c_p]),
+           "workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
+           "forward": (c_i, fwd)}
+    if trainable:
+        sig.update({"num_params": (c_sz, [c_p]),
+                    "param_offset": (c_i, [c_p, C.c_char_p, C.POINTER(c_sz), C.POINTER(c_sz)]),
+                    "train_workspace_bytes": (c_sz, [c_p, c_i, c_i, c_i]),
+                    "forward_train": (c_i, list(fwd)),
+                    "train_saved": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, C.POINTER(c_sz), C.POINTER(c_sz)]),
+                    "backward": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, c_p, c_sz, c_p])})
+    return {f"lfsr_{name}_{fn}": s for fn, s in sig.items()}
+
+
+# (model, ints lfsr_<model>_create takes after A and scale, trainable)
+_MODELS = (("distgssr", 3, True), ("internet", 2, True), ("lft", 2, True), ("epit", 2, False))
+for _m in _MODELS:
+    SIGNATURES.update(_model_signatures(*_m))
 
 _lib = None
 

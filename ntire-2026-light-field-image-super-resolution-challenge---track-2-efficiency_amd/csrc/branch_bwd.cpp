@@ -7,7 +7,6 @@
 #include "lfsr_internal.h"
 
 namespace {
-inline size_t al64(size_t v) { return (v + 63) & ~(size_t)63; }
 inline int pad32(int v) { return (v + 31) / 32 * 32; }
 
 // out[row][c] = dy[row][c] * LeakyReLU'(y[row][c]) for C channels (a multiple of 4) of strided VCL operands: the gradient at a branch's stage-2 pre-activation
@@ -42,20 +41,17 @@ int mask_lrelu(const float* dy, int dy_stride, int dy_choff, const float* y, int
 int lfsr_ang_branch_bwd_p1(const float* dcat, int dc_stride, int dc_choff, const float* xin, const float* a16, const float* w2T_packed, float* dw0, float* dw2,
                            float* dA16, float* P, int B, int A, int h, int w, float slope, hipStream_t st) {
   const int AA = A * A, nlr = B * h * w;
-  int rc;
-#define RC(call) do { rc = (call); if (rc) return rc; } while (0)
-  RC(lfsr_wgrad_launch(LFSR_IN_ANG, LFSR_IN_SAME, dcat, dc_stride, dc_choff, a16, 16, 0, P, nlr, 16, 16, A, h, w, AA, st));
-  RC(lfsr_wgrad_reduce(P, lfsr_wgrad_splits(nlr, AA, 16), nullptr, 0, dw2, 16 * AA, 16, AA, 1, 16, 0, 0, 1, st));
+  LFSR_RC(lfsr_wgrad_launch(LFSR_IN_ANG, LFSR_IN_SAME, dcat, dc_stride, dc_choff, a16, 16, 0, P, nlr, 16, 16, A, h, w, AA, st));
+  LFSR_RC(lfsr_wgrad_reduce(P, lfsr_wgrad_splits(nlr, AA, 16), nullptr, 0, dw2, 16 * AA, 16, AA, 1, 16, 0, 0, 1, st));
   {
     LfsrGemm q{};
     q.in_mode = LFSR_IN_ANG; q.out_mode = LFSR_OUT_SAME; q.cin = 16; q.X = dcat; q.x_stride = dc_stride; q.x_choff = dc_choff; q.Wp = w2T_packed;
     q.Y = dA16; q.y_stride = 16; q.Mk = a16; q.mk_stride = 16; q.mk_slope = slope;
     q.M = nlr; q.N = 16; q.A = A; q.h = h; q.w = w; q.ntaps = AA; q.CH = 16;
-    RC(lfsr_bwd_gemm(q, st));
+    LFSR_RC(lfsr_bwd_gemm(q, st));
   }
-  RC(lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_ANG, dA16, 16, 0, xin, 64, 0, P, nlr, 16, 64, A, h, w, AA, st));
-  RC(lfsr_wgrad_reduce(P, lfsr_wgrad_splits(nlr, AA, 64), nullptr, 0, dw0, 16, 64, AA, 0, 0, 0, 0, 0, st));
-#undef RC
+  LFSR_RC(lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_ANG, dA16, 16, 0, xin, 64, 0, P, nlr, 16, 64, A, h, w, AA, st));
+  LFSR_RC(lfsr_wgrad_reduce(P, lfsr_wgrad_splits(nlr, AA, 64), nullptr, 0, dw0, 16, 64, AA, 0, 0, 0, 0, 0, st));
   return LFSR_OK;
 }
 
@@ -83,22 +79,19 @@ int lfsr_ang_branch_bwd(const float* dcat, int dc_stride, int dc_choff, const fl
 int lfsr_epi_branch_bwd_p1(const float* dcat, int dc_stride, int choff_h, int choff_v, const float* eh, const float* ev, const float* w2T_packed, float* dw2,
                            float* dEh, float* dEv, float* const P[4], int B, int A, int h, int w, float slope, hipStream_t st) {
   const int nepi = B * A * h * w;
-  int rc;
-#define RC(call) do { rc = (call); if (rc) return rc; } while (0)
   for (int vert = 0; vert < 2; ++vert) {
     const float* E = vert ? ev : eh;
     float* dE = vert ? dEv : dEh;
     const int choff = vert ? choff_v : choff_h;
     float* Pa = P[vert ? 2 : 0];   // EPIConv.2 partials
-    RC(lfsr_wgrad_launch(vert ? LFSR_IN_CHK_V : LFSR_IN_CHK_H, LFSR_IN_SAME, dcat, dc_stride, choff, E, 32, 0, Pa, nepi, 32, 32, A, h, w, A, st));
+    LFSR_RC(lfsr_wgrad_launch(vert ? LFSR_IN_CHK_V : LFSR_IN_CHK_H, LFSR_IN_SAME, dcat, dc_stride, choff, E, 32, 0, Pa, nepi, 32, 32, A, h, w, A, st));
     LfsrGemm q{};
     q.in_mode = vert ? LFSR_IN_CHK_V : LFSR_IN_CHK_H; q.out_mode = LFSR_OUT_SAME; q.cin = 32; q.X = dcat; q.x_stride = dc_stride; q.x_choff = choff;
     q.Wp = w2T_packed; q.Y = dE; q.y_stride = 32; q.Mk = E; q.mk_stride = 32; q.mk_slope = slope;
     q.M = nepi; q.N = 32; q.A = A; q.h = h; q.w = w; q.ntaps = A; q.CH = 32;
-    RC(lfsr_bwd_gemm(q, st));
+    LFSR_RC(lfsr_bwd_gemm(q, st));
   }
-  RC(lfsr_wgrad_reduce(P[0], lfsr_wgrad_splits(nepi, A, 32), P[2], lfsr_wgrad_splits(nepi, A, 32), dw2, 32 * A, 32, A, 0, 32, 0, 0, 1, st));
-#undef RC
+  LFSR_RC(lfsr_wgrad_reduce(P[0], lfsr_wgrad_splits(nepi, A, 32), P[2], lfsr_wgrad_splits(nepi, A, 32), dw2, 32 * A, 32, A, 0, 32, 0, 0, 1, st));
   return LFSR_OK;
 }
 
@@ -121,24 +114,21 @@ int lfsr_epi_branch_bwd_p2d(const float* dEh, const float* dEv, const float* w0_
 int lfsr_epi_branch_bwd_p2w(const float* dEh, const float* dEv, const float* xin, float* dw0, float* const P[4], int B, int A, int h, int w, hipStream_t st) {
   const int AA = A * A, nepi = B * A * h * w;
   const long long npix = (long long)B * AA * h * w;
-  int rc;
-#define RC(call) do { rc = (call); if (rc) return rc; } while (0)
   // the two passes share EPIConv.0's weights: where the EPI-line kernel applies, ONE weight-gradient launch covers both (one slab per block instead of
   // two sets); else the gather form per pass
   const char* wsel = lfsr_sel("LFSR_WGRAD_EPI");
   const bool epi_merged = lfsr_wgrad_epi0_blocks(B, A, h, w, 2) > 0 && A == 5 && h <= 32 && w <= 32 && npix * 64 * 4 < (1LL << 31) && !(wsel && wsel[0] == 'g');
   int epi_slabs[2] = {0, 0};
   if (epi_merged) {
-    RC(lfsr_wgrad_epi0_launch(dEh, dEv, xin, 64, 0, P[1], B, A, h, w, 2, st));
+    LFSR_RC(lfsr_wgrad_epi0_launch(dEh, dEv, xin, 64, 0, P[1], B, A, h, w, 2, st));
     epi_slabs[0] = lfsr_wgrad_epi0_blocks(B, A, h, w, 2);
   } else {
     for (int vert = 0; vert < 2; ++vert) {
-      RC(lfsr_wgrad_launch(LFSR_IN_SAME, vert ? LFSR_IN_EPIV : LFSR_IN_EPIH, vert ? dEv : dEh, 32, 0, xin, 64, 0, P[vert ? 3 : 1], nepi, 32, 64, A, h, w, AA, st));
+      LFSR_RC(lfsr_wgrad_launch(LFSR_IN_SAME, vert ? LFSR_IN_EPIV : LFSR_IN_EPIH, vert ? dEv : dEh, 32, 0, xin, 64, 0, P[vert ? 3 : 1], nepi, 32, 64, A, h, w, AA, st));
       epi_slabs[vert] = lfsr_wgrad_splits(nepi, AA, 64);
     }
   }
-  RC(lfsr_wgrad_reduce(P[1], epi_slabs[0], epi_slabs[1] ? P[3] : nullptr, epi_slabs[1], dw0, 32, 64, AA, 0, 0, 0, 0, 0, st));
-#undef RC
+  LFSR_RC(lfsr_wgrad_reduce(P[1], epi_slabs[0], epi_slabs[1] ? P[3] : nullptr, epi_slabs[1], dw0, 32, 64, AA, 0, 0, 0, 0, 0, st));
   return LFSR_OK;
 }
 
@@ -165,32 +155,26 @@ size_t lfsr_branch_bwd_partial_floats(int B, int A, int h, int w) {
 }
 
 namespace {
-struct AngWs { float *w0p, *w0T, *w2T, *dA16, *P, *dym; size_t total; };
-void ang_layout(int B, int A, int h, int w, float* base, AngWs& t) {
+struct AngWs { float *w0p, *w0T, *w2T, *dA16, *P, *dym; };
+void ang_layout(int B, int A, int h, int w, LfsrArena& ws, AngWs& t) {
   const int AA = A * A;
-  size_t o = 0;
-  auto take = [&](size_t f) { float* p = base ? base + o : nullptr; o += al64(f); return p; };
-  t.w0p = take(lfsr_packed_weight_floats(16, 64, AA));
-  t.w0T = take((size_t)AA * pad32(64) * 16);
-  t.w2T = take((size_t)AA * pad32(16) * 16);
-  t.dA16 = take((size_t)B * h * w * 16);
-  t.P = take(lfsr_branch_bwd_partial_floats(B, A, h, w));
-  t.dym = take((size_t)B * AA * h * w * 16);
-  t.total = o;
+  t.w0p = ws.take(lfsr_packed_weight_floats(16, 64, AA));
+  t.w0T = ws.take((size_t)AA * pad32(64) * 16);
+  t.w2T = ws.take((size_t)AA * pad32(16) * 16);
+  t.dA16 = ws.take((size_t)B * h * w * 16);
+  t.P = ws.take(lfsr_branch_bwd_partial_floats(B, A, h, w));
+  t.dym = ws.take((size_t)B * AA * h * w * 16);
 }
-struct EpiWs { float *w0p, *w0T, *w2T, *dEh, *dEv, *P[4], *dym; size_t total; };
-void epi_layout(int B, int A, int h, int w, float* base, EpiWs& t) {
+struct EpiWs { float *w0p, *w0T, *w2T, *dEh, *dEv, *P[4], *dym; };
+void epi_layout(int B, int A, int h, int w, LfsrArena& ws, EpiWs& t) {
   const int AA = A * A;
-  size_t o = 0;
-  auto take = [&](size_t f) { float* p = base ? base + o : nullptr; o += al64(f); return p; };
-  t.w0p = take(lfsr_packed_weight_floats(32, 64, AA));
-  t.w0T = take((size_t)AA * pad32(64) * 32);
-  t.w2T = take((size_t)A * pad32(32) * 32);
-  t.dEh = take((size_t)B * A * h * w * 32);
-  t.dEv = take((size_t)B * A * h * w * 32);
-  for (int i = 0; i < 4; ++i) t.P[i] = take(lfsr_branch_bwd_partial_floats(B, A, h, w));
-  t.dym = take((size_t)B * AA * h * w * 64);
-  t.total = o;
+  t.w0p = ws.take(lfsr_packed_weight_floats(32, 64, AA));
+  t.w0T = ws.take((size_t)AA * pad32(64) * 32);
+  t.w2T = ws.take((size_t)A * pad32(32) * 32);
+  t.dEh = ws.take((size_t)B * A * h * w * 32);
+  t.dEv = ws.take((size_t)B * A * h * w * 32);
+  for (int i = 0; i < 4; ++i) t.P[i] = ws.take(lfsr_branch_bwd_partial_floats(B, A, h, w));
+  t.dym = ws.take((size_t)B * AA * h * w * 64);
 }
 }  // namespace
 
@@ -198,9 +182,10 @@ extern "C" {
 
 size_t lfsr_angconv_bwd_workspace_floats(int B, int A, int h, int w) {
   if (B <= 0 || A <= 0 || A > 15 || h <= 0 || w <= 0) return 0;
+  LfsrArena ws;
   AngWs t;
-  ang_layout(B, A, h, w, nullptr, t);
-  return t.total;
+  ang_layout(B, A, h, w, ws, t);
+  return ws.floats;
 }
 
 int lfsr_angconv_bwd(const float* dy, int dy_stride, int dy_choff, const float* y, int y_stride, int y_choff, const float* x, const float* a16, const float* w0, const float* w2,
@@ -208,9 +193,10 @@ int lfsr_angconv_bwd(const float* dy, int dy_stride, int dy_choff, const float* 
   if (!dy || !x || !a16 || !w0 || !w2 || !dx || !dw0 || !dw2 || !workspace || B <= 0 || A <= 0 || A > 15 || !(A & 1) || h <= 0 || w <= 0) return LFSR_E_ARG;
   if (dy_stride < dy_choff + 16 || (y && y_stride < y_choff + 16) || ((uintptr_t)workspace & 15)) return LFSR_E_ARG;
   if ((long long)B * A * A * h * w >= (1LL << 31) / 144) return LFSR_E_ARG;
+  LfsrArena ws(workspace);
   AngWs t;
-  ang_layout(B, A, h, w, workspace, t);
-  if (workspace_floats < t.total) return LFSR_E_WS;
+  ang_layout(B, A, h, w, ws, t);
+  if (workspace_floats < ws.floats) return LFSR_E_WS;
   hipStream_t st = lfsr_stream(stream);
   const int AA = A * A;
   int rc = lfsr_pack_conv_weight_m(w0, t.w0p, 16, 64, AA, 0, 0, 0, stream);
@@ -227,9 +213,10 @@ int lfsr_angconv_bwd(const float* dy, int dy_stride, int dy_choff, const float* 
 
 size_t lfsr_epiconv_hv_bwd_workspace_floats(int B, int A, int h, int w) {
   if (B <= 0 || A <= 0 || A > 15 || h <= 0 || w <= 0) return 0;
+  LfsrArena ws;
   EpiWs t;
-  epi_layout(B, A, h, w, nullptr, t);
-  return t.total;
+  epi_layout(B, A, h, w, ws, t);
+  return ws.floats;
 }
 
 int lfsr_epiconv_hv_bwd(const float* dy, int dy_stride, int choff_h, int choff_v, const float* y, int y_stride, int y_choff_h, int y_choff_v,
@@ -238,9 +225,10 @@ int lfsr_epiconv_hv_bwd(const float* dy, int dy_stride, int choff_h, int choff_v
   if (!dy || !x || !e_h || !e_v || !w0 || !w2 || !dx || !dw0 || !dw2 || !workspace || B <= 0 || A <= 0 || A > 15 || !(A & 1) || h <= 0 || w <= 0) return LFSR_E_ARG;
   if (dy_stride < choff_h + 32 || dy_stride < choff_v + 32 || (y && (y_stride < y_choff_h + 32 || y_stride < y_choff_v + 32)) || ((uintptr_t)workspace & 15)) return LFSR_E_ARG;
   if ((long long)B * A * A * h * w >= (1LL << 31) / 144) return LFSR_E_ARG;
+  LfsrArena ws(workspace);
   EpiWs t;
-  epi_layout(B, A, h, w, workspace, t);
-  if (workspace_floats < t.total) return LFSR_E_WS;
+  epi_layout(B, A, h, w, ws, t);
+  if (workspace_floats < ws.floats) return LFSR_E_WS;
   hipStream_t st = lfsr_stream(stream);
   const int AA = A * A;
   int rc = lfsr_pack_conv_weight_m(w0, t.w0p, 32, 64, AA, 0, 0, 0, stream);

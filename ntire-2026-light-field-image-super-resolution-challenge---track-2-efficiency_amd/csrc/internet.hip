@@ -112,15 +112,13 @@ int lfsr_internet_create(lfsr_internet** out, int A, int scale, int n_groups, in
 }
 
 void lfsr_internet_destroy(lfsr_internet* c) { delete c; }
-size_t lfsr_internet_packed_bytes(const lfsr_internet* c) { return c ? c->P.packed_floats * sizeof(float) : 0; }
-int lfsr_internet_set_packed(lfsr_internet* c, void* packed, size_t bytes) { if (!c) return LFSR_E_ARG; c->finalized = false; return c->P.set_packed(packed, bytes); }
+size_t lfsr_internet_packed_bytes(const lfsr_internet* c) { return c ? c->packed_bytes() : 0; }
+int lfsr_internet_set_packed(lfsr_internet* c, void* packed, size_t bytes) { return c ? c->set_packed(packed, bytes) : LFSR_E_ARG; }
 int lfsr_internet_load_param(lfsr_internet* c, const char* key, const float* data, size_t numel, void* stream) {
-  if (!c) return LFSR_E_ARG;
-  c->finalized = false;
-  return c->P.load(key, data, numel, stream);
+  return c ? c->load_param(key, data, numel, stream) : LFSR_E_ARG;
 }
 int lfsr_internet_finalize(lfsr_internet* c, void* stream) {
-  if (!c || !c->P.packed || !c->P.all_loaded()) return LFSR_E_ARG;
+  if (!c || !c->all_loaded()) return LFSR_E_ARG;
   hipLaunchKernelGGL(k_fold_recon, dim3((9 * 32 * 64 + 255) / 256), dim3(256), 0, lfsr_stream(stream), c->P.w("ReconBlock.PreConv.weight"),
                      c->P.w("ReconBlock.FinalConv.weight"), c->P.packed + c->off_wf, c->s * c->s);
   LFSR_CHECK_LAUNCH();
@@ -128,41 +126,37 @@ int lfsr_internet_finalize(lfsr_internet* c, void* stream) {
   return LFSR_OK;
 }
 
-static void internet_layout(const lfsr_internet* c, int B, int h, int w, size_t off[8], size_t* total) {
+static void internet_layout(const lfsr_internet* c, int B, int h, int w, LfsrArena& ws, float* buf[8]) {
   const size_t npix = (size_t)B * c->A * c->A * h * w, nlr = (size_t)B * h * w;
-  size_t o = 0;
-  auto take = [&](size_t f) { size_t r = o; o += LfsrParamTable::align64(f); return r; };
-  off[0] = take(npix * 64);                         // XS0: SpaFE output (final skip)
-  off[1] = take(npix * 128); off[2] = take(npix * 128);   // spatial rows, ping-pong
-  off[3] = take(nlr * 128); off[4] = take(nlr * 128);     // angular rows, ping-pong
-  off[5] = take(npix * 64 * (c->ngroups + 1));      // collected spatial outputs + BottleNeck's Ang2Spa slice
-  off[6] = take(nlr * 64 * c->ngroups);             // collected angular outputs
-  off[7] = take(npix * 64);                         // BottleNeck output
-  *total = o;
+  buf[0] = ws.take(npix * 64);                              // XS0: SpaFE output (final skip)
+  buf[1] = ws.take(npix * 128); buf[2] = ws.take(npix * 128);   // spatial rows, ping-pong
+  buf[3] = ws.take(nlr * 128); buf[4] = ws.take(nlr * 128);     // angular rows, ping-pong
+  buf[5] = ws.take(npix * 64 * (c->ngroups + 1));           // collected spatial outputs + BottleNeck's Ang2Spa slice
+  buf[6] = ws.take(nlr * 64 * c->ngroups);                  // collected angular outputs
+  buf[7] = ws.take(npix * 64);                              // BottleNeck output
 }
 
 size_t lfsr_internet_workspace_bytes(const lfsr_internet* c, int B, int h, int w) {
   if (!c || B <= 0 || h <= 0 || w <= 0) return 0;
-  size_t off[8], tot;
-  internet_layout(c, B, h, w, off, &tot);
-  return tot * sizeof(float);
+  LfsrArena ws;
+  float* buf[8];
+  internet_layout(c, B, h, w, ws, buf);
+  return ws.bytes();
 }
 
 int lfsr_internet_forward(lfsr_internet* c, const float* x, float* out, int B, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!c || !x || !out || !workspace || B <= 0 || h <= 0 || w <= 0 || !c->finalized || ((uintptr_t)workspace & 15)) return LFSR_E_ARG;
-  size_t off[8], tot;
-  internet_layout(c, B, h, w, off, &tot);
-  if (workspace_bytes < tot * sizeof(float)) return LFSR_E_WS;
+  if (!c || !c->run_args_ok(x, out, B, h, w, workspace)) return LFSR_E_ARG;
+  LfsrArena ws(workspace);
+  float* buf[8];
+  internet_layout(c, B, h, w, ws, buf);
+  if (workspace_bytes < ws.bytes()) return LFSR_E_WS;
   const int A = c->A, AA = A * A, nimg = B * AA, G = c->ngroups;
   const long long npix = (long long)nimg * h * w, nlr = (long long)B * h * w;
   if (npix >= (1LL << 31) / (64 * (G + 1))) return LFSR_E_ARG;
-  float* ws = (float*)workspace;
-  float *XS0 = ws + off[0], *S[2] = {ws + off[1], ws + off[2]}, *Ar[2] = {ws + off[3], ws + off[4]}, *CS = ws + off[5], *CA = ws + off[6], *BO = ws + off[7];
+  float *XS0 = buf[0], *S[2] = {buf[1], buf[2]}, *Ar[2] = {buf[3], buf[4]}, *CS = buf[5], *CA = buf[6], *BO = buf[7];
   const LfsrParamTable& P = c->P;
   hipStream_t st = lfsr_stream(stream);
   const int cs_stride = 64 * (G + 1), ca_stride = 64 * G;
-  int rc;
-#define RC(call) do { rc = (call); if (rc) return rc; } while (0)
   auto gemm = [&](auto launcher, const float* X, int xs, int xo, const float* Wp, float* Y, int ys, int yo, const float* R1, int r1s, int r1o,
                   int M, int N, int ntaps, int CH, float slope) -> int {
     GemmArgs p{};
@@ -173,7 +167,7 @@ int lfsr_internet_forward(lfsr_internet* c, const float* x, float* out, int B, i
   // feature extraction (LF_InterNet.py:35-36)
   hipLaunchKernelGGL(k_angfe, dim3(cap_grid(nlr * 16)), dim3(256), 64 * AA * sizeof(float), st, x, P.w("AngFE.0.weight"), Ar[0], 128, 0, B, A, h, w);
   LFSR_CHECK_LAUNCH();
-  RC(lfsr_initconv_fwd(x, P.w("SpaFE.0.weight"), S[0], 128, 0, B, A, h, w, stream));
+  LFSR_RC(lfsr_initconv_fwd(x, P.w("SpaFE.0.weight"), S[0], 128, 0, B, A, h, w, stream));
   hipLaunchKernelGGL(k_copy64, dim3(cap_grid(npix * 16)), dim3(256), 0, st, S[0], 128, 0, XS0, 64, 0, npix);
   LFSR_CHECK_LAUNCH();
   int cur = 0;
@@ -182,12 +176,12 @@ int lfsr_internet_forward(lfsr_internet* c, const float* x, float* out, int B, i
       std::string p = "CascadeInterBlock.body." + std::to_string(g) + ".chained_layers." + std::to_string(l) + ".";
       const int nxt = cur ^ 1;
       // buffer_ang2 = ReLU(Spa2Ang(xs)) -> angular rows [64:128]
-      RC(gemm(launch_gemm<IN_ANG, OUT_SAME, 64, 2>, S[cur], 128, 0, P.w(p + "Spa2Ang.weight"), Ar[cur], 128, 64, nullptr, 0, 0, (int)nlr, 64, AA, 64, 0.0f));
+      LFSR_RC(gemm(launch_gemm<IN_ANG, OUT_SAME, 64, 2>, S[cur], 128, 0, P.w(p + "Spa2Ang.weight"), Ar[cur], 128, 64, nullptr, 0, 0, (int)nlr, 64, AA, 64, 0.0f));
       // buffer_spa2 = PixelShuffle(Ang2Spa(xa)) -> spatial rows [64:128] of every view
-      RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, Ar[cur], 128, 0, P.w(p + "Ang2Spa.0.weight"), S[cur], 128, 64, nullptr, 0, 0, (int)nlr, AA * 64, 1, 64, 1.0f));
+      LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, Ar[cur], 128, 0, P.w(p + "Ang2Spa.0.weight"), S[cur], 128, 64, nullptr, 0, 0, (int)nlr, AA * 64, 1, 64, 1.0f));
       // out_a = ReLU(AngConvSq(cat(xa, ang2))) + xa ; out_s = ReLU(SpaConvSq(cat(xs, spa2))) + xs
-      RC(lfsr_linear_fwd(Ar[cur], 128, 0, 128, P.w(p + "AngConvSq.weight"), nullptr, Ar[cur], 128, 0, Ar[nxt], 128, 0, nlr, 64, 0.0f, stream));
-      RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 128, 2>, S[cur], 128, 0, P.w(p + "SpaConvSq.weight"), S[nxt], 128, 0, S[cur], 128, 0, (int)npix, 64, 9, 64, 0.0f));
+      LFSR_RC(lfsr_linear_fwd(Ar[cur], 128, 0, 128, P.w(p + "AngConvSq.weight"), nullptr, Ar[cur], 128, 0, Ar[nxt], 128, 0, nlr, 64, 0.0f, stream));
+      LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 128, 2>, S[cur], 128, 0, P.w(p + "SpaConvSq.weight"), S[nxt], 128, 0, S[cur], 128, 0, (int)npix, 64, 9, 64, 0.0f));
       cur = nxt;
     }
     hipLaunchKernelGGL(k_copy64, dim3(cap_grid(nlr * 16)), dim3(256), 0, st, Ar[cur], 128, 0, CA, ca_stride, 64 * g, nlr);
@@ -196,13 +190,12 @@ int lfsr_internet_forward(lfsr_internet* c, const float* x, float* out, int B, i
     LFSR_CHECK_LAUNCH();
   }
   // BottleNeck (LF_InterNet.py:119-124)
-  RC(lfsr_linear_fwd(CA, ca_stride, 0, 64 * G, P.w("BottleNeck.AngBottle.weight"), nullptr, nullptr, 0, 0, Ar[0], 128, 0, nlr, 64, 0.0f, stream));
-  RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, Ar[0], 128, 0, P.w("BottleNeck.Ang2Spa.0.weight"), CS, cs_stride, 64 * G, nullptr, 0, 0, (int)nlr, AA * 64, 1, 64, 1.0f));
+  LFSR_RC(lfsr_linear_fwd(CA, ca_stride, 0, 64 * G, P.w("BottleNeck.AngBottle.weight"), nullptr, nullptr, 0, 0, Ar[0], 128, 0, nlr, 64, 0.0f, stream));
+  LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, Ar[0], 128, 0, P.w("BottleNeck.Ang2Spa.0.weight"), CS, cs_stride, 64 * G, nullptr, 0, 0, (int)nlr, AA * 64, 1, 64, 1.0f));
   if (G != 4) return LFSR_E_ARG;   // SpaBottle instantiated for 5 x 64 input channels
-  RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 320, 2>, CS, cs_stride, 0, P.w("BottleNeck.SpaBottle.weight"), BO, 64, 0, XS0, 64, 0, (int)npix, 64, 9, 64, 0.0f));
+  LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 320, 2>, CS, cs_stride, 0, P.w("BottleNeck.SpaBottle.weight"), BO, 64, 0, XS0, 64, 0, (int)npix, 64, 9, 64, 0.0f));
   // ReconBlock (LF_InterNet.py:136-141), folded: 3x3 conv 64 -> s^2, epilogue = MacPI2SAI + PixelShuffle(s)
-  RC(gemm(launch_gemm<IN_CONV3, OUT_PS_HR, 64, 1>, BO, 64, 0, P.packed + c->off_wf, out, 1, 0, nullptr, 0, 0, (int)npix, c->s * c->s, 9, 1, 1.0f));
-#undef RC
+  LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_PS_HR, 64, 1>, BO, 64, 0, P.packed + c->off_wf, out, 1, 0, nullptr, 0, 0, (int)npix, c->s * c->s, 9, 1, 1.0f));
   return LFSR_OK;
 }
 

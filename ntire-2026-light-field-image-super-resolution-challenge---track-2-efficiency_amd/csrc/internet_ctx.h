@@ -2,11 +2,9 @@
 #pragma once
 #include "param_table.h"
 
-struct lfsr_internet {
-  int A, s, ngroups, nlayers;
-  LfsrParamTable P;
+struct lfsr_internet : LfsrModel {
+  int ngroups = 0, nlayers = 0;
   size_t off_wf = 0;
-  bool finalized = false;
 };
 
 // internet.hip: the forward's AngFE and 64-channel slice copy as host launches

@@ -11,7 +11,6 @@
 // (on the 64-channel input slices of SpaConvSq / SpaBottle); every weight gradient is the two-pass partial-slab reduction of wgrad.hip
 // (no float atomics: bitwise reproducible).  ReconBlock's folded conv is differentiated through the fold (k_fold_bwd).
 #include <string>
-#include <utility>
 #include <vector>
 
 #include "gemm_gather_kernel.h"
@@ -140,7 +139,6 @@ int ew64(const float* a, int as, int ao, const float* b, int bs, int bo, const f
 
 // ---- workspace --------------------------------------------------------------------------------------------------------------
 constexpr int NG = 4, NL = 4, NLAYER = NG * NL;
-inline size_t al64(size_t f) { return (f + 63) / 64 * 64; }
 inline int angfe_kpad(int A) { return (A * A + 3) / 4 * 4; }
 inline size_t tr3_floats() { return lfsr_packed_weight_tr_floats(64, 64, 9); }
 
@@ -155,7 +153,6 @@ struct InterTrainWs {
   float *SbT[NG + 1], *AbT, *BA2sT, *FoldT;
   // backward scratch
   float *G16, *dBO, *dZ, *dCS, *dOs[2], *dSP, *dOa[2], *dzA, *dG2, *dCA, *dZa, *XG9, *XA, *P, *dWf;
-  size_t total;
 };
 
 size_t partial_floats(int A, int B, int h, int w) {
@@ -173,26 +170,23 @@ size_t partial_floats(int A, int B, int h, int w) {
   return m;
 }
 
-void train_layout(const lfsr_internet* c, int B, int h, int w, float* base, InterTrainWs& t) {
+void train_layout(const lfsr_internet* c, int B, int h, int w, LfsrArena& ws, InterTrainWs& t) {
   const int A = c->A, AA = A * A;
   const size_t npix = (size_t)B * AA * h * w, nlr = (size_t)B * h * w;
-  size_t o = 0;
-  auto take = [&](size_t f) { float* p = base ? base + o : nullptr; o += al64(f); return p; };
-  for (int l = 0; l <= NLAYER; ++l) { t.S[l] = take(npix * 128); t.Ar[l] = take(nlr * 128); }
-  for (int l = 0; l < NLAYER; ++l) { t.RS[l] = take(npix * 64); t.RA[l] = take(nlr * 64); }
-  t.CS = take(npix * 64 * (NG + 1)); t.CA = take(nlr * 64 * NG); t.BA = take(nlr * 64); t.RB = take(npix * 64); t.BO = take(npix * 64);
+  for (int l = 0; l <= NLAYER; ++l) { t.S[l] = ws.take(npix * 128); t.Ar[l] = ws.take(nlr * 128); }
+  for (int l = 0; l < NLAYER; ++l) { t.RS[l] = ws.take(npix * 64); t.RA[l] = ws.take(nlr * 64); }
+  t.CS = ws.take(npix * 64 * (NG + 1)); t.CA = ws.take(nlr * 64 * NG); t.BA = ws.take(nlr * 64); t.RB = ws.take(npix * 64); t.BO = ws.take(npix * 64);
   for (int l = 0; l < NLAYER; ++l) {
-    t.ScLo[l] = take(tr3_floats()); t.ScHi[l] = take(tr3_floats()); t.AcT[l] = take(128 * 64);
-    t.A2sT[l] = take((size_t)AA * 64 * 64); t.S2aT[l] = take((size_t)AA * 64 * 64);
+    t.ScLo[l] = ws.take(tr3_floats()); t.ScHi[l] = ws.take(tr3_floats()); t.AcT[l] = ws.take(128 * 64);
+    t.A2sT[l] = ws.take((size_t)AA * 64 * 64); t.S2aT[l] = ws.take((size_t)AA * 64 * 64);
   }
-  for (int j = 0; j <= NG; ++j) t.SbT[j] = take(tr3_floats());
-  t.AbT = take(64 * NG * 64); t.BA2sT = take((size_t)AA * 64 * 64); t.FoldT = take(9 * 64 * 16);
-  t.G16 = take(npix * 16); t.dBO = take(npix * 64); t.dZ = take(npix * 64); t.dCS = take(npix * 64 * (NG + 1));
-  t.dOs[0] = take(npix * 64); t.dOs[1] = take(npix * 64); t.dSP = take(npix * 64);
-  t.dOa[0] = take(nlr * 64); t.dOa[1] = take(nlr * 64); t.dzA = take(nlr * 64); t.dG2 = take(nlr * 64); t.dCA = take(nlr * 64 * NG); t.dZa = take(nlr * 64);
-  t.XG9 = take(npix * 16); t.XA = take(nlr * angfe_kpad(A));
-  t.P = take(partial_floats(A, B, h, w)); t.dWf = take(16 * 64 * 9);
-  t.total = o;
+  for (int j = 0; j <= NG; ++j) t.SbT[j] = ws.take(tr3_floats());
+  t.AbT = ws.take(64 * NG * 64); t.BA2sT = ws.take((size_t)AA * 64 * 64); t.FoldT = ws.take(9 * 64 * 16);
+  t.G16 = ws.take(npix * 16); t.dBO = ws.take(npix * 64); t.dZ = ws.take(npix * 64); t.dCS = ws.take(npix * 64 * (NG + 1));
+  t.dOs[0] = ws.take(npix * 64); t.dOs[1] = ws.take(npix * 64); t.dSP = ws.take(npix * 64);
+  t.dOa[0] = ws.take(nlr * 64); t.dOa[1] = ws.take(nlr * 64); t.dzA = ws.take(nlr * 64); t.dG2 = ws.take(nlr * 64); t.dCA = ws.take(nlr * 64 * NG); t.dZa = ws.take(nlr * 64);
+  t.XG9 = ws.take(npix * 16); t.XA = ws.take(nlr * angfe_kpad(A));
+  t.P = ws.take(partial_floats(A, B, h, w)); t.dWf = ws.take(16 * 64 * 9);
 }
 
 // geometry the training path covers: the forward's per-tensor bound (the widest tensor, the 320-channel concat, below 2^31 floats), the
@@ -207,20 +201,6 @@ std::string chain_key(int g, int l, const char* leaf) {
   return "CascadeInterBlock.body." + std::to_string(g) + ".chained_layers." + std::to_string(l) + "." + leaf;
 }
 
-// state_dict order (LF_InterNet.py module creation order) -> (key, numel); the gradient bucket follows it
-std::vector<std::pair<std::string, size_t>> bucket_order(const lfsr_internet* c) {
-  std::vector<std::string> keys = {"AngFE.0.weight", "SpaFE.0.weight"};
-  for (int g = 0; g < c->ngroups; ++g)
-    for (int l = 0; l < c->nlayers; ++l)
-      for (const char* leaf : {"Spa2Ang.weight", "Ang2Spa.0.weight", "AngConvSq.weight", "SpaConvSq.weight"}) keys.push_back(chain_key(g, l, leaf));
-  for (const char* k : {"BottleNeck.AngBottle.weight", "BottleNeck.Ang2Spa.0.weight", "BottleNeck.SpaBottle.weight", "ReconBlock.PreConv.weight",
-                        "ReconBlock.FinalConv.weight"})
-    keys.push_back(k);
-  std::vector<std::pair<std::string, size_t>> out;
-  for (auto& k : keys) out.emplace_back(k, c->P.slots.at(k).numel);
-  return out;
-}
-
 }  // namespace
 
 int lfsr_pack_T_from_fwd(const float* Wp, float* out, int T, int Npad_in, int C, int O, int k0, int Kc, int flip, hipStream_t st) {
@@ -231,41 +211,27 @@ int lfsr_pack_T_from_fwd(const float* Wp, float* out, int T, int Npad_in, int C,
 
 extern "C" {
 
-size_t lfsr_internet_num_params(const lfsr_internet* c) {
-  if (!c) return 0;
-  size_t n = 0;
-  for (auto& kv : bucket_order(c)) n += kv.second;
-  return n;
-}
+size_t lfsr_internet_num_params(const lfsr_internet* c) { return c ? c->P.num_params() : 0; }
 
 int lfsr_internet_param_offset(const lfsr_internet* c, const char* key, size_t* off, size_t* numel) {
-  if (!c || !key) return LFSR_E_ARG;
-  size_t o = 0;
-  for (auto& kv : bucket_order(c)) {
-    if (kv.first == key) {
-      if (off) *off = o;
-      if (numel) *numel = kv.second;
-      return LFSR_OK;
-    }
-    o += kv.second;
-  }
-  return LFSR_E_ARG;
+  return c ? c->P.param_offset(key, off, numel) : LFSR_E_ARG;
 }
 
 size_t lfsr_internet_train_workspace_bytes(const lfsr_internet* c, int B, int h, int w) {
   if (!train_geometry_ok(c, B, h, w)) return 0;
+  LfsrArena ws;
   InterTrainWs t;
-  train_layout(c, B, h, w, nullptr, t);
-  return t.total * sizeof(float);
+  train_layout(c, B, h, w, ws, t);
+  return ws.bytes();
 }
 
 // which: 0 S (layer input rows [xs | spa2], VCL, 128), 1 Ar (layer input rows [xa | ang2], LR, 128), 2 ReLU(SpaConvSq) (VCL, 64),
 // 3 ReLU(AngConvSq) (LR, 64), 4 ReLU(SpaBottle) (VCL, 64), 5 ReLU(AngBottle) (LR, 64); index = chain layer g * n_layers + l (0 for 4 / 5)
 int lfsr_internet_train_saved(const lfsr_internet* c, int B, int h, int w, int which, int index, size_t* offset_floats, size_t* numel) {
   if (!train_geometry_ok(c, B, h, w) || !offset_floats || !numel || index < 0 || index >= (which <= 3 ? NLAYER : 1)) return LFSR_E_ARG;
+  LfsrArena ws = LfsrArena::offsets();
   InterTrainWs t;
-  float* const base = reinterpret_cast<float*>(uintptr_t(4096));   // any non-null base: only differences are used
-  train_layout(c, B, h, w, base, t);
+  train_layout(c, B, h, w, ws, t);
   const size_t npix = (size_t)B * c->A * c->A * h * w, nlr = (size_t)B * h * w;
   const float* p = nullptr;
   size_t n = 0;
@@ -278,23 +244,22 @@ int lfsr_internet_train_saved(const lfsr_internet* c, int B, int h, int w, int w
     case 5: p = t.BA; n = nlr * 64; break;
     default: return LFSR_E_ARG;
   }
-  *offset_floats = (size_t)(p - base);
+  *offset_floats = ws.offset(p);
   *numel = n;
   return LFSR_OK;
 }
 
 int lfsr_internet_forward_train(lfsr_internet* c, const float* x, float* out, int B, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!c || !x || !out || !workspace || !c->finalized || ((uintptr_t)workspace & 15) || !train_geometry_ok(c, B, h, w)) return LFSR_E_ARG;
+  if (!c || !c->run_args_ok(x, out, B, h, w, workspace) || !train_geometry_ok(c, B, h, w)) return LFSR_E_ARG;
+  LfsrArena ws(workspace);
   InterTrainWs t;
-  train_layout(c, B, h, w, (float*)workspace, t);
-  if (workspace_bytes < t.total * sizeof(float)) return LFSR_E_WS;
+  train_layout(c, B, h, w, ws, t);
+  if (workspace_bytes < ws.bytes()) return LFSR_E_WS;
   const int A = c->A, AA = A * A;
   const long long npix = (long long)B * AA * h * w, nlr = (long long)B * h * w;
   const LfsrParamTable& P = c->P;
   hipStream_t st = lfsr_stream(stream);
   const int cs_stride = 64 * (NG + 1), ca_stride = 64 * NG;
-  int rc;
-#define RC(call) do { rc = (call); if (rc) return rc; } while (0)
   auto gemm = [&](auto launcher, const float* X, int xs, int xo, const float* Wp, float* Y, int ys, int yo, const float* R1, int r1s, int r1o,
                   int M, int N, int ntaps, int CH, float slope) -> int {
     GemmArgs p{};
@@ -312,63 +277,55 @@ int lfsr_internet_forward_train(lfsr_internet* c, const float* x, float* out, in
   for (int g = 0; g < NG; ++g)
     for (int l = 0; l < NL; ++l) {
       const int i = g * NL + l;
-      RC(packT(chain_key(g, l, "SpaConvSq.weight"), t.ScLo[i], 9, 64, 128, 64, 0, 64, 1));
-      RC(packT(chain_key(g, l, "SpaConvSq.weight"), t.ScHi[i], 9, 64, 128, 64, 64, 64, 1));
-      RC(packT(chain_key(g, l, "AngConvSq.weight"), t.AcT[i], 1, 64, 128, 64, 0, 128, 0));
-      RC(packT(chain_key(g, l, "Ang2Spa.0.weight"), t.A2sT[i], AA, 64, 64, 64, 0, 64, 0));
-      RC(packT(chain_key(g, l, "Spa2Ang.weight"), t.S2aT[i], AA, 64, 64, 64, 0, 64, 0));
+      LFSR_RC(packT(chain_key(g, l, "SpaConvSq.weight"), t.ScLo[i], 9, 64, 128, 64, 0, 64, 1));
+      LFSR_RC(packT(chain_key(g, l, "SpaConvSq.weight"), t.ScHi[i], 9, 64, 128, 64, 64, 64, 1));
+      LFSR_RC(packT(chain_key(g, l, "AngConvSq.weight"), t.AcT[i], 1, 64, 128, 64, 0, 128, 0));
+      LFSR_RC(packT(chain_key(g, l, "Ang2Spa.0.weight"), t.A2sT[i], AA, 64, 64, 64, 0, 64, 0));
+      LFSR_RC(packT(chain_key(g, l, "Spa2Ang.weight"), t.S2aT[i], AA, 64, 64, 64, 0, 64, 0));
     }
-  for (int j = 0; j <= NG; ++j) RC(packT("BottleNeck.SpaBottle.weight", t.SbT[j], 9, 64, 64 * (NG + 1), 64, 64 * j, 64, 1));
-  RC(packT("BottleNeck.AngBottle.weight", t.AbT, 1, 64, 64 * NG, 64, 0, 64 * NG, 0));
-  RC(packT("BottleNeck.Ang2Spa.0.weight", t.BA2sT, AA, 64, 64, 64, 0, 64, 0));
+  for (int j = 0; j <= NG; ++j) LFSR_RC(packT("BottleNeck.SpaBottle.weight", t.SbT[j], 9, 64, 64 * (NG + 1), 64, 64 * j, 64, 1));
+  LFSR_RC(packT("BottleNeck.AngBottle.weight", t.AbT, 1, 64, 64 * NG, 64, 0, 64 * NG, 0));
+  LFSR_RC(packT("BottleNeck.Ang2Spa.0.weight", t.BA2sT, AA, 64, 64, 64, 0, 64, 0));
   hipLaunchKernelGGL(k_pack_fold_T, dim3((9 * 64 * 16 + 255) / 256), dim3(256), 0, st, P.packed + c->off_wf, t.FoldT, c->s * c->s);
   LFSR_CHECK_LAUNCH();
 
   // ---- the forward's launches (internet.hip), every layer into its own buffers
-  RC(lfsr_internet_angfe(x, P.w("AngFE.0.weight"), t.Ar[0], 128, 0, B, A, h, w, st));
-  RC(lfsr_initconv_fwd(x, P.w("SpaFE.0.weight"), t.S[0], 128, 0, B, A, h, w, stream));
+  LFSR_RC(lfsr_internet_angfe(x, P.w("AngFE.0.weight"), t.Ar[0], 128, 0, B, A, h, w, st));
+  LFSR_RC(lfsr_initconv_fwd(x, P.w("SpaFE.0.weight"), t.S[0], 128, 0, B, A, h, w, stream));
   for (int g = 0; g < NG; ++g) {
     for (int l = 0; l < NL; ++l) {
       const int i = g * NL + l;
-      RC(gemm(launch_gemm<IN_ANG, OUT_SAME, 64, 2>, t.S[i], 128, 0, P.w(chain_key(g, l, "Spa2Ang.weight")), t.Ar[i], 128, 64, nullptr, 0, 0, (int)nlr, 64, AA, 64, 0.0f));
-      RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, t.Ar[i], 128, 0, P.w(chain_key(g, l, "Ang2Spa.0.weight")), t.S[i], 128, 64, nullptr, 0, 0, (int)nlr, AA * 64, 1, 64, 1.0f));
-      RC(lfsr_linear_fwd(t.Ar[i], 128, 0, 128, P.w(chain_key(g, l, "AngConvSq.weight")), nullptr, t.Ar[i], 128, 0, t.Ar[i + 1], 128, 0, nlr, 64, 0.0f, stream));
-      RC(lfsr_linear_fwd(t.Ar[i], 128, 0, 128, P.w(chain_key(g, l, "AngConvSq.weight")), nullptr, nullptr, 0, 0, t.RA[i], 64, 0, nlr, 64, 0.0f, stream));
-      RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 128, 2>, t.S[i], 128, 0, P.w(chain_key(g, l, "SpaConvSq.weight")), t.RS[i], 64, 0, nullptr, 0, 0, (int)npix, 64, 9, 64, 0.0f));
-      RC(ew64(t.RS[i], 64, 0, t.S[i], 128, 0, nullptr, 0, 0, t.S[i + 1], 128, 0, npix, st));
+      LFSR_RC(gemm(launch_gemm<IN_ANG, OUT_SAME, 64, 2>, t.S[i], 128, 0, P.w(chain_key(g, l, "Spa2Ang.weight")), t.Ar[i], 128, 64, nullptr, 0, 0, (int)nlr, 64, AA, 64, 0.0f));
+      LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, t.Ar[i], 128, 0, P.w(chain_key(g, l, "Ang2Spa.0.weight")), t.S[i], 128, 64, nullptr, 0, 0, (int)nlr, AA * 64, 1, 64, 1.0f));
+      LFSR_RC(lfsr_linear_fwd(t.Ar[i], 128, 0, 128, P.w(chain_key(g, l, "AngConvSq.weight")), nullptr, t.Ar[i], 128, 0, t.Ar[i + 1], 128, 0, nlr, 64, 0.0f, stream));
+      LFSR_RC(lfsr_linear_fwd(t.Ar[i], 128, 0, 128, P.w(chain_key(g, l, "AngConvSq.weight")), nullptr, nullptr, 0, 0, t.RA[i], 64, 0, nlr, 64, 0.0f, stream));
+      LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 128, 2>, t.S[i], 128, 0, P.w(chain_key(g, l, "SpaConvSq.weight")), t.RS[i], 64, 0, nullptr, 0, 0, (int)npix, 64, 9, 64, 0.0f));
+      LFSR_RC(ew64(t.RS[i], 64, 0, t.S[i], 128, 0, nullptr, 0, 0, t.S[i + 1], 128, 0, npix, st));
     }
-    RC(lfsr_internet_copy64(t.Ar[(g + 1) * NL], 128, 0, t.CA, ca_stride, 64 * g, nlr, st));
-    RC(lfsr_internet_copy64(t.S[(g + 1) * NL], 128, 0, t.CS, cs_stride, 64 * g, npix, st));
+    LFSR_RC(lfsr_internet_copy64(t.Ar[(g + 1) * NL], 128, 0, t.CA, ca_stride, 64 * g, nlr, st));
+    LFSR_RC(lfsr_internet_copy64(t.S[(g + 1) * NL], 128, 0, t.CS, cs_stride, 64 * g, npix, st));
   }
-  RC(lfsr_linear_fwd(t.CA, ca_stride, 0, 64 * NG, P.w("BottleNeck.AngBottle.weight"), nullptr, nullptr, 0, 0, t.BA, 64, 0, nlr, 64, 0.0f, stream));
-  RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, t.BA, 64, 0, P.w("BottleNeck.Ang2Spa.0.weight"), t.CS, cs_stride, 64 * NG, nullptr, 0, 0, (int)nlr, AA * 64, 1, 64, 1.0f));
-  RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 320, 2>, t.CS, cs_stride, 0, P.w("BottleNeck.SpaBottle.weight"), t.RB, 64, 0, nullptr, 0, 0, (int)npix, 64, 9, 64, 0.0f));
-  RC(ew64(t.RB, 64, 0, t.S[0], 128, 0, nullptr, 0, 0, t.BO, 64, 0, npix, st));
-  RC(gemm(launch_gemm<IN_CONV3, OUT_PS_HR, 64, 1>, t.BO, 64, 0, P.packed + c->off_wf, out, 1, 0, nullptr, 0, 0, (int)npix, c->s * c->s, 9, 1, 1.0f));
-#undef RC
+  LFSR_RC(lfsr_linear_fwd(t.CA, ca_stride, 0, 64 * NG, P.w("BottleNeck.AngBottle.weight"), nullptr, nullptr, 0, 0, t.BA, 64, 0, nlr, 64, 0.0f, stream));
+  LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, t.BA, 64, 0, P.w("BottleNeck.Ang2Spa.0.weight"), t.CS, cs_stride, 64 * NG, nullptr, 0, 0, (int)nlr, AA * 64, 1, 64, 1.0f));
+  LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 320, 2>, t.CS, cs_stride, 0, P.w("BottleNeck.SpaBottle.weight"), t.RB, 64, 0, nullptr, 0, 0, (int)npix, 64, 9, 64, 0.0f));
+  LFSR_RC(ew64(t.RB, 64, 0, t.S[0], 128, 0, nullptr, 0, 0, t.BO, 64, 0, npix, st));
+  LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_PS_HR, 64, 1>, t.BO, 64, 0, P.packed + c->off_wf, out, 1, 0, nullptr, 0, 0, (int)npix, c->s * c->s, 9, 1, 1.0f));
   return LFSR_OK;
 }
 
 int lfsr_internet_backward(lfsr_internet* c, const float* x, const float* dout, int B, int h, int w, void* workspace, size_t workspace_bytes,
                            float* grads, size_t n_grads, void* stream) {
-  if (!c || !x || !dout || !workspace || !grads || !c->finalized || ((uintptr_t)workspace & 15) || !train_geometry_ok(c, B, h, w)) return LFSR_E_ARG;
-  if (n_grads != lfsr_internet_num_params(c)) return LFSR_E_ARG;
+  if (!c || !c->run_args_ok(x, dout, B, h, w, workspace) || !grads || !train_geometry_ok(c, B, h, w) || n_grads != c->P.num_params()) return LFSR_E_ARG;
+  LfsrArena ws(workspace);
   InterTrainWs t;
-  train_layout(c, B, h, w, (float*)workspace, t);
-  if (workspace_bytes < t.total * sizeof(float)) return LFSR_E_WS;
+  train_layout(c, B, h, w, ws, t);
+  if (workspace_bytes < ws.bytes()) return LFSR_E_WS;
   const int A = c->A, AA = A * A, s2 = c->s * c->s, nimg = B * AA;
   const int npix = nimg * h * w, nlr = B * h * w;
   const int cs_stride = 64 * (NG + 1), ca_stride = 64 * NG;
   const LfsrParamTable& P = c->P;
   hipStream_t st = lfsr_stream(stream);
-  std::vector<std::pair<std::string, size_t>> order = bucket_order(c);
-  auto G = [&](const std::string& k) -> float* {
-    size_t o = 0;
-    for (auto& kv : order) { if (kv.first == k) return grads + o; o += kv.second; }
-    return nullptr;
-  };
-  int rc;
-#define RC(call) do { rc = (call); if (rc) return rc; } while (0)
+  auto G = [&](const std::string& k) -> float* { return grads + P.grad_off(k); };
   // gather-GEMM data gradient: identity epilogue, optional R1 (may alias Y: in-place accumulate) and ReLU' mask Mk (> 0 keeps)
   auto gemm = [&](auto launcher, const float* X, int xs, int xo, const float* Wp, float* Y, int ys, int yo, const float* R1, int r1s, int r1o,
                   const float* Mk, int mks, int mko, int M, int N, int ntaps, int CH) -> int {
@@ -392,65 +349,64 @@ int lfsr_internet_backward(lfsr_internet* c, const float* x, const float* dout, 
   // ---- ReconBlock (folded 3x3 conv 64 -> s^2 + MacPI2SAI + PixelShuffle(s)) ----------------------------------------------------------
   hipLaunchKernelGGL(k_unshuffle_hr, dim3(cap_grid((long long)npix * 16)), dim3(256), 0, st, dout, t.G16, B, A, h, w, c->s);
   LFSR_CHECK_LAUNCH();
-  RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 16, 2>, t.G16, 16, 0, t.FoldT, t.dBO, 64, 0, nullptr, 0, 0, nullptr, 0, 0, npix, 64, 9, 64));
-  RC(wgrad(LFSR_IN_SAME, LFSR_IN_CONV3, t.G16, 16, 0, t.BO, 64, 0, npix, 16, 64, 9, t.dWf, 16, 64, 9, 0, 0, 0, 0));
+  LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 16, 2>, t.G16, 16, 0, t.FoldT, t.dBO, 64, 0, nullptr, 0, 0, nullptr, 0, 0, npix, 64, 9, 64));
+  LFSR_RC(wgrad(LFSR_IN_SAME, LFSR_IN_CONV3, t.G16, 16, 0, t.BO, 64, 0, npix, 16, 64, 9, t.dWf, 16, 64, 9, 0, 0, 0, 0));
   hipLaunchKernelGGL(k_fold_bwd, dim3(64), dim3(256), 0, st, t.dWf, P.w("ReconBlock.PreConv.weight"), P.w("ReconBlock.FinalConv.weight"),
                      G("ReconBlock.PreConv.weight"), G("ReconBlock.FinalConv.weight"), s2);
   LFSR_CHECK_LAUNCH();
 
   // ---- BottleNeck: BO = ReLU(SpaBottle(CS)) + xs, CS[:, 256:320] = PS(Ang2Spa(a)), a = ReLU(AngBottle(CA)) --------------------------------
-  RC(ew64(t.dBO, 64, 0, nullptr, 0, 0, t.RB, 64, 0, t.dZ, 64, 0, npix, st));
-  RC(wgrad(LFSR_IN_SAME, LFSR_IN_CONV3, t.dZ, 64, 0, t.CS, cs_stride, 0, npix, 64, cs_stride, 9, G("BottleNeck.SpaBottle.weight"), 64, cs_stride, 9, 0, 0, 0, 0));
-  for (int j = 0; j <= NG; ++j) RC(dgrad3(t.dZ, t.SbT[j], t.dCS, cs_stride, 64 * j, nullptr));
-  RC(gemm(launch_gemm<IN_ANG, OUT_SAME, 64, 2>, t.dCS, cs_stride, 64 * NG, t.BA2sT, t.dZa, 64, 0, nullptr, 0, 0, t.BA, 64, 0, nlr, 64, AA, 64));
-  RC(wgrad(LFSR_IN_ANG, LFSR_IN_SAME, t.dCS, cs_stride, 64 * NG, t.BA, 64, 0, nlr, 64, 64, AA, G("BottleNeck.Ang2Spa.0.weight"), AA * 64, 64, AA, 1, 64, 0, 1));
-  RC(gemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dZa, 64, 0, t.AbT, t.dCA, ca_stride, 0, nullptr, 0, 0, nullptr, 0, 0, nlr, ca_stride, 1, ca_stride));
-  RC(wgrad(LFSR_IN_SAME, LFSR_IN_SAME, t.dZa, 64, 0, t.CA, ca_stride, 0, nlr, 64, ca_stride, 1, G("BottleNeck.AngBottle.weight"), 64, ca_stride, 1, 0, 0, 0, 0));
+  LFSR_RC(ew64(t.dBO, 64, 0, nullptr, 0, 0, t.RB, 64, 0, t.dZ, 64, 0, npix, st));
+  LFSR_RC(wgrad(LFSR_IN_SAME, LFSR_IN_CONV3, t.dZ, 64, 0, t.CS, cs_stride, 0, npix, 64, cs_stride, 9, G("BottleNeck.SpaBottle.weight"), 64, cs_stride, 9, 0, 0, 0, 0));
+  for (int j = 0; j <= NG; ++j) LFSR_RC(dgrad3(t.dZ, t.SbT[j], t.dCS, cs_stride, 64 * j, nullptr));
+  LFSR_RC(gemm(launch_gemm<IN_ANG, OUT_SAME, 64, 2>, t.dCS, cs_stride, 64 * NG, t.BA2sT, t.dZa, 64, 0, nullptr, 0, 0, t.BA, 64, 0, nlr, 64, AA, 64));
+  LFSR_RC(wgrad(LFSR_IN_ANG, LFSR_IN_SAME, t.dCS, cs_stride, 64 * NG, t.BA, 64, 0, nlr, 64, 64, AA, G("BottleNeck.Ang2Spa.0.weight"), AA * 64, 64, AA, 1, 64, 0, 1));
+  LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dZa, 64, 0, t.AbT, t.dCA, ca_stride, 0, nullptr, 0, 0, nullptr, 0, 0, nlr, ca_stride, 1, ca_stride));
+  LFSR_RC(wgrad(LFSR_IN_SAME, LFSR_IN_SAME, t.dZa, 64, 0, t.CA, ca_stride, 0, nlr, 64, ca_stride, 1, G("BottleNeck.AngBottle.weight"), 64, ca_stride, 1, 0, 0, 0, 0));
 
   // ---- cascade, reversed.  dOs / dOa: the gradient at the current layer's outputs out_s (VCL, 64) and out_a (LR, 64) ------------------------
   int cur = 0;
   for (int g = NG - 1; g >= 0; --g) {
     // the group's output also went into the concat buffers
     if (g == NG - 1) {
-      RC(ew64(t.dCS, cs_stride, 64 * g, nullptr, 0, 0, nullptr, 0, 0, t.dOs[cur], 64, 0, npix, st));
-      RC(ew64(t.dCA, ca_stride, 64 * g, nullptr, 0, 0, nullptr, 0, 0, t.dOa[cur], 64, 0, nlr, st));
+      LFSR_RC(ew64(t.dCS, cs_stride, 64 * g, nullptr, 0, 0, nullptr, 0, 0, t.dOs[cur], 64, 0, npix, st));
+      LFSR_RC(ew64(t.dCA, ca_stride, 64 * g, nullptr, 0, 0, nullptr, 0, 0, t.dOa[cur], 64, 0, nlr, st));
     } else {
-      RC(ew64(t.dOs[cur], 64, 0, t.dCS, cs_stride, 64 * g, nullptr, 0, 0, t.dOs[cur], 64, 0, npix, st));
-      RC(ew64(t.dOa[cur], 64, 0, t.dCA, ca_stride, 64 * g, nullptr, 0, 0, t.dOa[cur], 64, 0, nlr, st));
+      LFSR_RC(ew64(t.dOs[cur], 64, 0, t.dCS, cs_stride, 64 * g, nullptr, 0, 0, t.dOs[cur], 64, 0, npix, st));
+      LFSR_RC(ew64(t.dOa[cur], 64, 0, t.dCA, ca_stride, 64 * g, nullptr, 0, 0, t.dOa[cur], 64, 0, nlr, st));
     }
     for (int l = NL - 1; l >= 0; --l) {
       const int i = g * NL + l, nxt = cur ^ 1;
       float *dOs = t.dOs[cur], *dOa = t.dOa[cur], *dxs = t.dOs[nxt], *dxa = t.dOa[nxt];
       // out_s = ReLU(SpaConvSq([xs | spa2])) + xs ; out_a = ReLU(AngConvSq([xa | ang2])) + xa
-      RC(ew64(dOs, 64, 0, nullptr, 0, 0, t.RS[i], 64, 0, t.dZ, 64, 0, npix, st));
-      RC(ew64(dOa, 64, 0, nullptr, 0, 0, t.RA[i], 64, 0, t.dzA, 64, 0, nlr, st));
+      LFSR_RC(ew64(dOs, 64, 0, nullptr, 0, 0, t.RS[i], 64, 0, t.dZ, 64, 0, npix, st));
+      LFSR_RC(ew64(dOa, 64, 0, nullptr, 0, 0, t.RA[i], 64, 0, t.dzA, 64, 0, nlr, st));
       // AngConvSq: dxa = dzA W[:, :64]^T + dOa ; dang2 = (dzA W[:, 64:]^T) * [ang2 > 0]
-      RC(wgrad(LFSR_IN_SAME, LFSR_IN_SAME, t.dzA, 64, 0, t.Ar[i], 128, 0, nlr, 64, 128, 1, G(chain_key(g, l, "AngConvSq.weight")), 64, 128, 1, 0, 0, 0, 0));
-      RC(gemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dzA, 64, 0, t.AcT[i], dxa, 64, 0, dOa, 64, 0, nullptr, 0, 0, nlr, 64, 1, 64));
-      RC(gemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dzA, 64, 0, t.AcT[i] + 64 * 64, t.dG2, 64, 0, nullptr, 0, 0, t.Ar[i], 128, 64, nlr, 64, 1, 64));
+      LFSR_RC(wgrad(LFSR_IN_SAME, LFSR_IN_SAME, t.dzA, 64, 0, t.Ar[i], 128, 0, nlr, 64, 128, 1, G(chain_key(g, l, "AngConvSq.weight")), 64, 128, 1, 0, 0, 0, 0));
+      LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dzA, 64, 0, t.AcT[i], dxa, 64, 0, dOa, 64, 0, nullptr, 0, 0, nlr, 64, 1, 64));
+      LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dzA, 64, 0, t.AcT[i] + 64 * 64, t.dG2, 64, 0, nullptr, 0, 0, t.Ar[i], 128, 64, nlr, 64, 1, 64));
       // SpaConvSq: dxs = conv3^T(dzS; W[:, :64]) + dOs ; dspa2 = conv3^T(dzS; W[:, 64:])
-      RC(wgrad(LFSR_IN_SAME, LFSR_IN_CONV3, t.dZ, 64, 0, t.S[i], 128, 0, npix, 64, 128, 9, G(chain_key(g, l, "SpaConvSq.weight")), 64, 128, 9, 0, 0, 0, 0));
-      RC(dgrad3(t.dZ, t.ScLo[i], dxs, 64, 0, dOs));
-      RC(dgrad3(t.dZ, t.ScHi[i], t.dSP, 64, 0, nullptr));
+      LFSR_RC(wgrad(LFSR_IN_SAME, LFSR_IN_CONV3, t.dZ, 64, 0, t.S[i], 128, 0, npix, 64, 128, 9, G(chain_key(g, l, "SpaConvSq.weight")), 64, 128, 9, 0, 0, 0, 0));
+      LFSR_RC(dgrad3(t.dZ, t.ScLo[i], dxs, 64, 0, dOs));
+      LFSR_RC(dgrad3(t.dZ, t.ScHi[i], t.dSP, 64, 0, nullptr));
       // Ang2Spa: spa2 = PS(W xa) -> dxa += sum over the views (IN_ANG gather of dspa2)
-      RC(gemm(launch_gemm<IN_ANG, OUT_SAME, 64, 2>, t.dSP, 64, 0, t.A2sT[i], dxa, 64, 0, dxa, 64, 0, nullptr, 0, 0, nlr, 64, AA, 64));
-      RC(wgrad(LFSR_IN_ANG, LFSR_IN_SAME, t.dSP, 64, 0, t.Ar[i], 128, 0, nlr, 64, 64, AA, G(chain_key(g, l, "Ang2Spa.0.weight")), AA * 64, 64, AA, 1, 64, 0, 1));
+      LFSR_RC(gemm(launch_gemm<IN_ANG, OUT_SAME, 64, 2>, t.dSP, 64, 0, t.A2sT[i], dxa, 64, 0, dxa, 64, 0, nullptr, 0, 0, nlr, 64, AA, 64));
+      LFSR_RC(wgrad(LFSR_IN_ANG, LFSR_IN_SAME, t.dSP, 64, 0, t.Ar[i], 128, 0, nlr, 64, 64, AA, G(chain_key(g, l, "Ang2Spa.0.weight")), AA * 64, 64, AA, 1, 64, 0, 1));
       // Spa2Ang: ang2 = ReLU(convAxA(xs)) -> dxs += the OUT_VIEWS scatter of the masked dang2 (each view pixel has one LR pixel: no atomics)
-      RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, t.dG2, 64, 0, t.S2aT[i], dxs, 64, 0, dxs, 64, 0, nullptr, 0, 0, nlr, AA * 64, 1, 64));
-      RC(wgrad(LFSR_IN_SAME, LFSR_IN_ANG, t.dG2, 64, 0, t.S[i], 128, 0, nlr, 64, 64, AA, G(chain_key(g, l, "Spa2Ang.weight")), 64, 64, AA, 0, 0, 0, 0));
+      LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, t.dG2, 64, 0, t.S2aT[i], dxs, 64, 0, dxs, 64, 0, nullptr, 0, 0, nlr, AA * 64, 1, 64));
+      LFSR_RC(wgrad(LFSR_IN_SAME, LFSR_IN_ANG, t.dG2, 64, 0, t.S[i], 128, 0, nlr, 64, 64, AA, G(chain_key(g, l, "Spa2Ang.weight")), 64, 64, AA, 0, 0, 0, 0));
       cur = nxt;
     }
   }
 
   // ---- feature extraction: xs = SpaFE(x) (also the BottleNeck skip), xa = AngFE(x) ----------------------------------------------------
-  RC(ew64(t.dOs[cur], 64, 0, t.dBO, 64, 0, nullptr, 0, 0, t.dOs[cur], 64, 0, npix, st));
-  RC(lfsr_init_gather9(x, t.XG9, B, A, h, w, st));
-  RC(wgrad(LFSR_IN_SAME, LFSR_IN_SAME, t.dOs[cur], 64, 0, t.XG9, 16, 0, npix, 64, 16, 1, G("SpaFE.0.weight"), 64, 16, 1, 0, 0, 9, 0));
+  LFSR_RC(ew64(t.dOs[cur], 64, 0, t.dBO, 64, 0, nullptr, 0, 0, t.dOs[cur], 64, 0, npix, st));
+  LFSR_RC(lfsr_init_gather9(x, t.XG9, B, A, h, w, st));
+  LFSR_RC(wgrad(LFSR_IN_SAME, LFSR_IN_SAME, t.dOs[cur], 64, 0, t.XG9, 16, 0, npix, 64, 16, 1, G("SpaFE.0.weight"), 64, 16, 1, 0, 0, 9, 0));
   const int kp = angfe_kpad(A);
   hipLaunchKernelGGL(k_angfe_gather, dim3(cap_grid((long long)nlr * kp)), dim3(256), 0, st, x, t.XA, B, A, h, w, kp);
   LFSR_CHECK_LAUNCH();
-  RC(wgrad(LFSR_IN_SAME, LFSR_IN_SAME, t.dOa[cur], 64, 0, t.XA, kp, 0, nlr, 64, kp, 1, G("AngFE.0.weight"), 64, kp, 1, 0, 0, AA, 0));
-#undef RC
+  LFSR_RC(wgrad(LFSR_IN_SAME, LFSR_IN_SAME, t.dOa[cur], 64, 0, t.XA, kp, 0, nlr, 64, kp, 1, G("AngFE.0.weight"), 64, kp, 1, 0, 0, AA, 0));
   return LFSR_OK;
 }
 

@@ -11,6 +11,12 @@
     hipError_t e__ = hipGetLastError();                       \
     if (e__ != hipSuccess) return LFSR_HIP_ERR(e__);          \
   } while (0)
+// early return of a failed step: LFSR_RC(lfsr_...(...)) returns its nonzero status from the enclosing function
+#define LFSR_RC(call)                                         \
+  do {                                                        \
+    const int rc__ = (call);                                  \
+    if (rc__) return rc__;                                    \
+  } while (0)
 
 static inline hipStream_t lfsr_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 // A/B ("lab") selectors: LFSR_* environment variables that pick an alternative kernel form of an operator for measurements and parity tests.  They are consulted
@@ -22,6 +28,24 @@ static inline unsigned lfsr_blocks(long long n, int per) {
   long long b = (n + per - 1) / per;
   return (unsigned)(b < 1 ? 1 : b);
 }
+
+// Host-side layout of a workspace: buffers one after another in 64-float (256-B) granules.  A null base is the sizing pass (every pointer
+// null, `floats` exact); offsets() lays out on a stand-in base that is never dereferenced, so that offset(p) tells where a buffer lies.
+struct LfsrArena {
+  float* base;
+  size_t floats = 0;
+  explicit LfsrArena(void* b = nullptr) : base(static_cast<float*>(b)) {}
+  static LfsrArena offsets() { return LfsrArena(reinterpret_cast<void*>(uintptr_t(256))); }
+  static size_t granules(size_t f) { return (f + 63) / 64 * 64; }
+  float* take(size_t f) {
+    float* p = base ? base + floats : nullptr;
+    floats += granules(f);
+    return p;
+  }
+  size_t bytes() const { return floats * sizeof(float); }
+  size_t offset(const float* p) const { return (size_t)(p - base); }
+};
+
 // Non-temporal hint on result stores.  Measured on one MI355X (two runs each per call): on the 3x3 conv's output stores alone (buffer_store ... nt,
 // W4_STPOL in conv3x3_wino4.hip) the DistgSSR forward goes 1678.7 -> 1718 patches/s (profiles/r02_logs/ab_bench_lines.json: bench13_*.json); on the EPI / angular / row-GEMM
 // kernels' stores as well (global_store ... nt through lfsr_store_stream) it FALLS to 1444 (EPIT 668 -> 539, LFT 1331 -> 982 patches/s,

@@ -1,5 +1,7 @@
 // Internal (non-ABI) entry points shared between the translation units of liblfsr_hip.so.
 #pragma once
+#include <string>
+
 #include "lfsr_common.h"
 
 // gather modes (values match gemm_gather_kernel.h)
@@ -235,3 +237,29 @@ int lfsr_epi_branch_bwd_p1(const float* dcat, int dc_stride, int choff_h, int ch
                            float* dEh, float* dEv, float* const P[4], int B, int A, int h, int w, float slope, hipStream_t st);
 int lfsr_epi_branch_bwd_p2d(const float* dEh, const float* dEv, const float* w0_packed, const float* w0T_packed, float* dx, int B, int A, int h, int w, hipStream_t st);
 int lfsr_epi_branch_bwd_p2w(const float* dEh, const float* dEv, const float* xin, float* dw0, float* const P[4], int B, int A, int h, int w, hipStream_t st);
+
+// transformer.hip: what the EPIT and LFT forwards share, on their packed tables (param_table.h; `pre` = the key prefix of a sublayer)
+struct LfsrParamTable;
+// the lab selectors of those forwards (LFSR_LN_FUSE, LFSR_ROWGEMM, LFSR_NO_FFN_FUSED, LFSR_FFN_PRESPLIT, LFSR_NO_UPTAIL), read once per forward
+struct LfsrTransSel {
+  bool ln_fuse;       // LayerNorms formed inside the consuming kernel
+  bool ln_fuse_qkv;   // ... the attention norm too, inside the q | k | v projection
+  bool ffn_fused;     // the one-launch feed-forward (else two linears through HBM)
+  bool presplit;      // the fused feed-forward reads the weights' pre-split image
+  bool up_tail;       // the fused up-sampling tail at scales 2 and 4
+};
+LfsrTransSel lfsr_trans_sel();
+// conv_init0 and the conv_init stack: buf0 = lrelu(conv_init.4(c2)) + f0
+int lfsr_trans_head(const LfsrParamTable& P, const float* x, float* f0, float* c1, float* c2, float* buf0, int B, int A, int h, int w, void* stream);
+// q | k = LayerNorm(x + pe) W[0:2E]^T, v = x W[2E:3E]^T (norm.*, attention.in_proj_weight): one launch, else LayerNorm into tn and two linears
+int lfsr_trans_qkv(const LfsrTransSel& sel, const LfsrParamTable& P, const std::string& pre, const float* x, int E, const float* pe, long long pe_rows,
+                   long long pe_div, float* qk, float* v, float* tn, long long M, void* stream);
+// y = x + FFN(LayerNorm(x)), E -> 2E -> E (feed_forward.*): LayerNorm inside the fused feed-forward, else LayerNorm into lnx and the fused
+// feed-forward, else two linears through hid; split_off = the pre-split image of the weights (lfsr_trans_ffn_reserve / _presplit)
+int lfsr_trans_ffn(const LfsrTransSel& sel, const LfsrParamTable& P, const std::string& pre, const float* x, int E, size_t split_off, float* y, float* lnx,
+                   float* hid, long long M, void* stream);
+size_t lfsr_trans_ffn_reserve(LfsrParamTable& P, int E);
+int lfsr_trans_ffn_presplit(const LfsrParamTable& P, const std::string& pre, int E, size_t split_off, void* stream);
+// upsampling.0 / .3 and the bicubic skip: the fused tail at scales 2 and 4, else the HR map in hr and the two-kernel tail
+int lfsr_trans_tail(const LfsrTransSel& sel, const LfsrParamTable& P, const float* f, const float* x, float* out, float* hr, int B, int A, int h, int w, int s,
+                    void* stream);

@@ -2,11 +2,9 @@
 #pragma once
 #include "param_table.h"
 
-struct lfsr_lft {
-  int A, s, nlayer;
-  LfsrParamTable P;
+struct lfsr_lft : LfsrModel {
+  int nlayer = 0;
   std::vector<size_t> ffn_split_spa, ffn_split_ang;   // per layer: offsets (floats) of the feed-forward weights' pre-split bf16 images (ffn_b3.hip)
-  bool finalized = false;
 };
 
 // Where the forward body reads and writes.  The inference forward aliases these onto a few ping-pong buffers (lft.cpp); the training

@@ -10,7 +10,6 @@
 // per query and one per key: no float atomics), the LayerNorm backward with the position embedding added to its input, the tail's
 // LeakyReLU / 3x3 conv backward with the HR -> LR un-shuffle, and small fixed-order reductions.  Buckets are bitwise reproducible.
 #include <string>
-#include <utility>
 #include <vector>
 
 #include "gemm_gather_kernel.h"
@@ -331,7 +330,6 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnBwdArgs p) {
 }
 
 // ---- workspace ------------------------------------------------------------------------------------------------------------------
-inline size_t al64(size_t f) { return (f + 63) / 64 * 64; }
 inline size_t tr3_floats() { return lfsr_packed_weight_tr_floats(64, 64, 9); }
 
 struct LftTrainWs {
@@ -345,7 +343,6 @@ struct LftTrainWs {
   float *up0T, *initT[3];
   std::vector<float*> mloT, mhiT;
   float* lin[11];                     // one layer's 1x1 dgrad packs (rebuilt for every layer): see the backward
-  size_t total;
 };
 
 size_t wgrad_partial_max(int B, int A, int h, int w) {
@@ -367,92 +364,54 @@ bool train_geometry_ok(const lfsr_lft* c, int B, int h, int w) {
   return npix * widest * 4 < (1LL << 31);
 }
 
-void train_layout(const lfsr_lft* c, int B, int h, int w, float* base, LftTrainWs& t) {
+void train_layout(const lfsr_lft* c, int B, int h, int w, LfsrArena& ws, LftTrainWs& t) {
   const int nl = c->nlayer, s2 = c->s * c->s;
   const size_t npix = (size_t)B * c->A * c->A * h * w, HW = (size_t)h * w;
-  size_t o = 0;
-  auto take = [&](size_t f) { float* p = base ? base + o : nullptr; o += al64(f); return p; };
   LftFwdBufs& f = t.f;
-  f.f0 = take(npix * 64); f.c1 = take(npix * 64); f.c2 = take(npix * 64); f.buf0 = take(npix * 64);
-  f.spos = take(HW * 64); f.ape = take((size_t)c->A * c->A * 64);
+  f.f0 = ws.take(npix * 64); f.c1 = ws.take(npix * 64); f.c2 = ws.take(npix * 64); f.buf0 = ws.take(npix * 64);
+  f.spos = ws.take(HW * 64); f.ape = ws.take((size_t)c->A * c->A * 64);
   f.x.assign(nl + 1, nullptr);
   f.x[0] = f.buf0;
   for (int b = 0; b < nl; ++b) {
-    f.aqk.push_back(take(npix * 128)); f.av.push_back(take(npix * 64)); f.ao.push_back(take(npix * 64)); f.am.push_back(take(npix * 64));
-    f.ay.push_back(take(npix * 64));
-    f.st.push_back(take(npix * 128)); f.spe.push_back(take(HW * 128)); f.sqk.push_back(take(npix * 256)); f.sv.push_back(take(npix * 128));
-    f.so.push_back(take(npix * 128)); f.sm.push_back(take(npix * 128)); f.sf.push_back(take(npix * 128));
-    f.x[b + 1] = take(npix * 64);
+    f.aqk.push_back(ws.take(npix * 128)); f.av.push_back(ws.take(npix * 64)); f.ao.push_back(ws.take(npix * 64)); f.am.push_back(ws.take(npix * 64));
+    f.ay.push_back(ws.take(npix * 64));
+    f.st.push_back(ws.take(npix * 128)); f.spe.push_back(ws.take(HW * 128)); f.sqk.push_back(ws.take(npix * 256)); f.sv.push_back(ws.take(npix * 128));
+    f.so.push_back(ws.take(npix * 128)); f.sm.push_back(ws.take(npix * 128)); f.sf.push_back(ws.take(npix * 128));
+    f.x[b + 1] = ws.take(npix * 64);
   }
-  t.hr = take(npix * 64 * s2); t.du = take(npix * 64 * s2);
-  t.dx[0] = take(npix * 64); t.dx[1] = take(npix * 64); t.dbuf0 = take(npix * 64);
-  t.dsf = take(npix * 128); t.dh = take(npix * 256); t.dln = take(npix * 128); t.dln2 = take(npix * 128); t.dsm = take(npix * 128);
-  t.dso = take(npix * 128); t.dqk = take(npix * 256); t.dv = take(npix * 128); t.dst = take(npix * 128); t.lnt = take(npix * 128);
-  t.hid = take(npix * 256); t.r4 = take(npix * 64); t.d64 = take(npix * 64); t.t64 = take(npix * 64); t.dspe = take(HW * 128); t.xg9 = take(npix * 16);
-  t.stats = reinterpret_cast<float4*>(take(npix * 8 * 4));
+  t.hr = ws.take(npix * 64 * s2); t.du = ws.take(npix * 64 * s2);
+  t.dx[0] = ws.take(npix * 64); t.dx[1] = ws.take(npix * 64); t.dbuf0 = ws.take(npix * 64);
+  t.dsf = ws.take(npix * 128); t.dh = ws.take(npix * 256); t.dln = ws.take(npix * 128); t.dln2 = ws.take(npix * 128); t.dsm = ws.take(npix * 128);
+  t.dso = ws.take(npix * 128); t.dqk = ws.take(npix * 256); t.dv = ws.take(npix * 128); t.dst = ws.take(npix * 128); t.lnt = ws.take(npix * 128);
+  t.hid = ws.take(npix * 256); t.r4 = ws.take(npix * 64); t.d64 = ws.take(npix * 64); t.t64 = ws.take(npix * 64); t.dspe = ws.take(HW * 128); t.xg9 = ws.take(npix * 16);
+  t.stats = reinterpret_cast<float4*>(ws.take(npix * 8 * 4));
   t.hid_a.clear(); t.hid_s.clear();
-  for (int b = 0; b < nl; ++b) { t.hid_a.push_back(take(npix * 128)); t.hid_s.push_back(take(npix * 256)); }
-  t.part = take(wgrad_partial_max(B, c->A, h, w)); t.pln = take((size_t)RED_BLOCKS * 256); t.ptail = take((size_t)RED_BLOCKS * 9 * 64);
+  for (int b = 0; b < nl; ++b) { t.hid_a.push_back(ws.take(npix * 128)); t.hid_s.push_back(ws.take(npix * 256)); }
+  t.part = ws.take(wgrad_partial_max(B, c->A, h, w)); t.pln = ws.take((size_t)RED_BLOCKS * 256); t.ptail = ws.take((size_t)RED_BLOCKS * 9 * 64);
   // the forward body's scratch (unfused LayerNorm outputs, two-launch feed-forward hidden rows, the unfused tail's HR map)
   f.n64 = t.t64; f.tn = t.lnt; f.lnf = t.dln2; f.ha = t.dh; f.hs = t.hid; f.hr = t.hr;
-  t.up0T = take((size_t)64 * 64 * s2);
-  for (int i = 0; i < 3; ++i) t.initT[i] = take(tr3_floats());
+  t.up0T = ws.take((size_t)64 * 64 * s2);
+  for (int i = 0; i < 3; ++i) t.initT[i] = ws.take(tr3_floats());
   t.mloT.clear(); t.mhiT.clear();
-  for (int b = 0; b < nl; ++b) { t.mloT.push_back(take(tr3_floats())); t.mhiT.push_back(take(tr3_floats())); }
-  for (float*& l : t.lin) l = take(256 * 128);       // the largest: [128][256]
-  t.total = o;
-}
-
-// state_dict order (LFT.py module creation order; AltFilter creates spa_trans before ang_trans) -> (key, numel); the gradient bucket follows it.
-// The packed table's internal entries (MLP.weight#lo / #hi, the feed-forward pre-split images) are not parameters.
-std::vector<std::pair<std::string, size_t>> bucket_order(const lfsr_lft* c) {
-  std::vector<std::string> keys = {"conv_init0.0.weight", "conv_init.0.weight", "conv_init.2.weight", "conv_init.4.weight"};
-  for (int b = 0; b < c->nlayer; ++b) {
-    const std::string sp = "altblock." + std::to_string(b) + ".spa_trans.", an = "altblock." + std::to_string(b) + ".ang_trans.";
-    for (const char* k : {"MLP.weight", "norm.weight", "norm.bias", "attention.in_proj_weight", "attention.out_proj.weight", "feed_forward.0.weight",
-                          "feed_forward.0.bias", "feed_forward.1.weight", "feed_forward.4.weight", "linear.0.weight"})
-      keys.push_back(sp + k);
-    for (const char* k : {"norm.weight", "norm.bias", "attention.in_proj_weight", "attention.out_proj.weight", "feed_forward.0.weight", "feed_forward.0.bias",
-                          "feed_forward.1.weight", "feed_forward.4.weight"})
-      keys.push_back(an + k);
-  }
-  keys.push_back("upsampling.0.weight");
-  keys.push_back("upsampling.3.weight");
-  std::vector<std::pair<std::string, size_t>> out;
-  for (auto& k : keys) out.emplace_back(k, c->P.slots.at(k).numel);
-  return out;
+  for (int b = 0; b < nl; ++b) { t.mloT.push_back(ws.take(tr3_floats())); t.mhiT.push_back(ws.take(tr3_floats())); }
+  for (float*& l : t.lin) l = ws.take(256 * 128);       // the largest: [128][256]
 }
 
 }  // namespace
 
 extern "C" {
 
-size_t lfsr_lft_num_params(const lfsr_lft* c) {
-  if (!c) return 0;
-  size_t n = 0;
-  for (auto& kv : bucket_order(c)) n += kv.second;
-  return n;
-}
+// the gradient bucket: state_dict order (LFT.py module creation order; AltFilter creates spa_trans before ang_trans); MLP.weight#lo / #hi are internal
+size_t lfsr_lft_num_params(const lfsr_lft* c) { return c ? c->P.num_params() : 0; }
 
-int lfsr_lft_param_offset(const lfsr_lft* c, const char* key, size_t* off, size_t* numel) {
-  if (!c || !key) return LFSR_E_ARG;
-  size_t o = 0;
-  for (auto& kv : bucket_order(c)) {
-    if (kv.first == key) {
-      if (off) *off = o;
-      if (numel) *numel = kv.second;
-      return LFSR_OK;
-    }
-    o += kv.second;
-  }
-  return LFSR_E_ARG;
-}
+int lfsr_lft_param_offset(const lfsr_lft* c, const char* key, size_t* off, size_t* numel) { return c ? c->P.param_offset(key, off, numel) : LFSR_E_ARG; }
 
 size_t lfsr_lft_train_workspace_bytes(const lfsr_lft* c, int B, int h, int w) {
   if (!train_geometry_ok(c, B, h, w)) return 0;
+  LfsrArena ws;
   LftTrainWs t;
-  train_layout(c, B, h, w, nullptr, t);
-  return t.total * sizeof(float);
+  train_layout(c, B, h, w, ws, t);
+  return ws.bytes();
 }
 
 // which: 0 the input of AltFilter `index` (index = n_layer: the altblock output plus its skip, the tail's input), 1 the angular feed-forward
@@ -465,9 +424,9 @@ int lfsr_lft_train_saved(const lfsr_lft* c, int B, int h, int w, int which, int 
   if (!train_geometry_ok(c, B, h, w) || !offset_floats || !numel || index < 0) return LFSR_E_ARG;
   const int nl = c->nlayer;
   if (index >= (which == 0 ? nl + 1 : which == 5 ? 2 : which >= 8 ? 1 : nl)) return LFSR_E_ARG;
+  LfsrArena ws = LfsrArena::offsets();
   LftTrainWs t;
-  float* const base = reinterpret_cast<float*>(uintptr_t(4096));   // any non-null base: only differences are used
-  train_layout(c, B, h, w, base, t);
+  train_layout(c, B, h, w, ws, t);
   const size_t npix = (size_t)B * c->A * c->A * h * w;
   const float* p = nullptr;
   size_t n = npix * 128;
@@ -484,40 +443,34 @@ int lfsr_lft_train_saved(const lfsr_lft* c, int B, int h, int w, int which, int 
     case 9: p = t.hr; n = npix * 64 * c->s * c->s; break;
     default: return LFSR_E_ARG;
   }
-  *offset_floats = (size_t)(p - base);
+  *offset_floats = ws.offset(p);
   *numel = n;
   return LFSR_OK;
 }
 
 int lfsr_lft_forward_train(lfsr_lft* c, const float* x, float* out, int B, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!c || !x || !out || !workspace || !c->finalized || ((uintptr_t)workspace & 15) || !train_geometry_ok(c, B, h, w)) return LFSR_E_ARG;
+  if (!c || !c->run_args_ok(x, out, B, h, w, workspace) || !train_geometry_ok(c, B, h, w)) return LFSR_E_ARG;
+  LfsrArena ws(workspace);
   LftTrainWs t;
-  train_layout(c, B, h, w, (float*)workspace, t);
-  if (workspace_bytes < t.total * sizeof(float)) return LFSR_E_WS;
+  train_layout(c, B, h, w, ws, t);
+  if (workspace_bytes < ws.bytes()) return LFSR_E_WS;
   return lfsr_lft_forward_body(c, x, out, B, h, w, t.f, stream);
 }
 
 int lfsr_lft_backward(lfsr_lft* c, const float* x, const float* dout, int B, int h, int w, void* workspace, size_t workspace_bytes,
                       float* grads, size_t n_grads, void* stream) {
-  if (!c || !x || !dout || !workspace || !grads || !c->finalized || ((uintptr_t)workspace & 15) || !train_geometry_ok(c, B, h, w)) return LFSR_E_ARG;
-  if (n_grads != lfsr_lft_num_params(c)) return LFSR_E_ARG;
+  if (!c || !c->run_args_ok(x, dout, B, h, w, workspace) || !grads || !train_geometry_ok(c, B, h, w) || n_grads != c->P.num_params()) return LFSR_E_ARG;
+  LfsrArena ws(workspace);
   LftTrainWs t;
-  train_layout(c, B, h, w, (float*)workspace, t);
-  if (workspace_bytes < t.total * sizeof(float)) return LFSR_E_WS;
+  train_layout(c, B, h, w, ws, t);
+  if (workspace_bytes < ws.bytes()) return LFSR_E_WS;
   const int A = c->A, AA = A * A, S = c->s, s2 = S * S, nimg = B * AA, HW = h * w, nl = c->nlayer;
   const int npix = nimg * HW;
   const float L = 0.2f;
   const LfsrParamTable& P = c->P;
   const LftFwdBufs& f = t.f;
   hipStream_t st = lfsr_stream(stream);
-  std::vector<std::pair<std::string, size_t>> order = bucket_order(c);
-  auto G = [&](const std::string& k) -> float* {
-    size_t o = 0;
-    for (auto& kv : order) { if (kv.first == k) return grads + o; o += kv.second; }
-    return nullptr;
-  };
-  int rc;
-#define RC(call) do { rc = (call); if (rc) return rc; } while (0)
+  auto G = [&](const std::string& k) -> float* { return grads + P.grad_off(k); };
   auto launched = [&]() -> int { LFSR_CHECK_LAUNCH(); return LFSR_OK; };
   // 1x1 data gradient Y (N columns) = X (CIN columns) . WT, then * (Mk > 0 ? 1 : 0) (ReLU'), then + R1 (may alias Y)
   auto dgemm = [&](auto launcher, const float* X, int xs, const float* WT, float* Y, int ys, const float* R1, int r1s, const float* Mk, int mks, int N) -> int {
@@ -555,9 +508,9 @@ int lfsr_lft_backward(lfsr_lft* c, const float* x, const float* dout, int B, int
       hipLaunchKernelGGL(k_ln_bwd<64>, dim3(nb), dim3(256), 0, st, X, 64, pe, 64, pe_rows, pe_div, P.w(gkey), dy, 64, r, 64, dxo, 64, t.pln, (long long)npix, 1e-5f);
     else
       hipLaunchKernelGGL(k_ln_bwd<128>, dim3(nb), dim3(256), 0, st, X, 128, pe, 128, pe_rows, pe_div, P.w(gkey), dy, 128, r, 128, dxo, 128, t.pln, (long long)npix, 1e-5f);
-    RC(launched());
+    LFSR_RC(launched());
     hipLaunchKernelGGL(k_colsum, dim3(C / 32), dim3(256), 0, st, t.pln, (int)nb, 2 * C, C, G(gkey));
-    RC(launched());
+    LFSR_RC(launched());
     hipLaunchKernelGGL(k_colsum, dim3(C / 32), dim3(256), 0, st, t.pln + C, (int)nb, 2 * C, C, G(bkey));
     return launched();
   };
@@ -574,7 +527,7 @@ int lfsr_lft_backward(lfsr_lft* c, const float* x, const float* dout, int B, int
     const unsigned grid = lfsr_blocks(p.total, 256);
     if (hd == 8) hipLaunchKernelGGL(k_attn_bwd_q<8>, dim3(grid), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(k_attn_bwd_q<16>, dim3(grid), dim3(256), 0, st, p);
-    RC(launched());
+    LFSR_RC(launched());
     if (hd == 8) hipLaunchKernelGGL(k_attn_bwd_kv<8>, dim3(grid), dim3(256), 0, st, p);
     else hipLaunchKernelGGL(k_attn_bwd_kv<16>, dim3(grid), dim3(256), 0, st, p);
     return launched();
@@ -585,122 +538,121 @@ int lfsr_lft_backward(lfsr_lft* c, const float* x, const float* dout, int B, int
   // 1x1 dgrad pack of rows [n0, n0 + O) of a (Npad_in, C) forward pack: [C][O]
   auto packT = [&](const float* Wp, int n0, int C, int O, float* o) -> int { return lfsr_pack_T_from_fwd(Wp + (size_t)n0 * C, o, 1, O, C, O, 0, C, 0, st); };
   auto pack3T = [&](const std::string& key, float* o) -> int {
-    RC(lfsr_pack_T_from_fwd(P.w(key), o, 9, 64, 64, 64, 0, 64, 1, st));
+    LFSR_RC(lfsr_pack_T_from_fwd(P.w(key), o, 9, 64, 64, 64, 0, 64, 1, st));
     return lfsr_pack_wino_m(o, o + LFSR_CONV3_DIRECT_FLOATS, LFSR_W_ALL, st);   // the 64 -> 64 3x3 data gradient's Winograd copies
   };
 
   // ---- tail: upsampling.0 (1x1 64 -> 64 s^2), PixelShuffle(s), LeakyReLU 0.2, 3x3 conv 64 -> 1, + bicubic skip (no parameters) ----------
-  RC(lfsr_upsample_ps_fwd(f.x[nl], 64, 0, P.w("upsampling.0.weight"), t.hr, B, A, h, w, S, stream));   // the HR pre-activation, rebuilt
+  LFSR_RC(lfsr_upsample_ps_fwd(f.x[nl], 64, 0, P.w("upsampling.0.weight"), t.hr, B, A, h, w, S, stream));   // the HR pre-activation, rebuilt
   {
     unsigned nb = lfsr_blocks(npix, 4);
     if (nb > RED_BLOCKS) nb = RED_BLOCKS;
     hipLaunchKernelGGL(k_tail_bwd, dim3(nb), dim3(256), 0, st, dout, P.w("upsampling.3.weight"), t.hr, t.du, t.ptail, B, A, h, w, S, L);
-    RC(launched());
+    LFSR_RC(launched());
     hipLaunchKernelGGL(k_colsum, dim3(9 * 64 / 32), dim3(256), 0, st, t.ptail, (int)nb, 9 * 64, 9 * 64, G("upsampling.3.weight"));
-    RC(launched());
+    LFSR_RC(launched());
   }
   hipLaunchKernelGGL(k_pack_up0_T, dim3((64 * 64 * s2 + 255) / 256), dim3(256), 0, st, P.w("upsampling.0.weight"), t.up0T, s2);
-  RC(launched());
+  LFSR_RC(launched());
   float* dX = t.dx[0];   // the gradient at the altblock output (+ its skip): dL/d x[nl]
-  if (s2 == 4) RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 256, 2>, t.du, 256, t.up0T, dX, 64, nullptr, 0, nullptr, 0, 64));
-  else if (s2 == 9) RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 576, 2>, t.du, 576, t.up0T, dX, 64, nullptr, 0, nullptr, 0, 64));
-  else RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 1024, 2>, t.du, 1024, t.up0T, dX, 64, nullptr, 0, nullptr, 0, 64));
-  RC(wgrad_lin(t.du, 64 * s2, 64 * s2, f.x[nl], 64, 64, G("upsampling.0.weight")));
+  if (s2 == 4) LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 256, 2>, t.du, 256, t.up0T, dX, 64, nullptr, 0, nullptr, 0, 64));
+  else if (s2 == 9) LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 576, 2>, t.du, 576, t.up0T, dX, 64, nullptr, 0, nullptr, 0, 64));
+  else LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 1024, 2>, t.du, 1024, t.up0T, dX, 64, nullptr, 0, nullptr, 0, 64));
+  LFSR_RC(wgrad_lin(t.du, 64 * s2, 64 * s2, f.x[nl], 64, 64, G("upsampling.0.weight")));
 
   // ---- altblock, reversed.  LFT.py:91 buffer = altblock(buffer) + buffer: dX also reaches buf0 directly ----------------------------------
-  RC(ew(dX, 64, nullptr, 0, nullptr, 0, 1.0f, t.dbuf0, 64, 64, npix));
+  LFSR_RC(ew(dX, 64, nullptr, 0, nullptr, 0, 1.0f, t.dbuf0, 64, 64, npix));
   for (int b = nl - 1; b >= 0; --b) {
     const std::string sp = "altblock." + std::to_string(b) + ".spa_trans.", an = "altblock." + std::to_string(b) + ".ang_trans.";
     float** lin = t.lin;
     // the layer's 1x1 dgrad packs: [C_in][O] of every linear weight (q | k and v as separate row ranges of in_proj)
-    RC(packT(P.w(sp + "linear.0.weight"), 0, 128, 64, lin[0]));
-    RC(packT(P.w(sp + "feed_forward.4.weight"), 0, 256, 128, lin[1]));
-    RC(packT(P.w(sp + "feed_forward.1.weight"), 0, 128, 256, lin[2]));
-    RC(packT(P.w(sp + "attention.out_proj.weight"), 0, 128, 128, lin[3]));
-    RC(packT(P.w(sp + "attention.in_proj_weight"), 0, 128, 256, lin[4]));
-    RC(packT(P.w(sp + "attention.in_proj_weight"), 256, 128, 128, lin[5]));
-    RC(packT(P.w(an + "feed_forward.4.weight"), 0, 128, 64, lin[6]));
-    RC(packT(P.w(an + "feed_forward.1.weight"), 0, 64, 128, lin[7]));
-    RC(packT(P.w(an + "attention.out_proj.weight"), 0, 64, 64, lin[8]));
-    RC(packT(P.w(an + "attention.in_proj_weight"), 0, 64, 128, lin[9]));
-    RC(packT(P.w(an + "attention.in_proj_weight"), 128, 64, 64, lin[10]));
-    RC(pack3T(sp + "MLP.weight#lo", t.mloT[b]));
-    RC(pack3T(sp + "MLP.weight#hi", t.mhiT[b]));
+    LFSR_RC(packT(P.w(sp + "linear.0.weight"), 0, 128, 64, lin[0]));
+    LFSR_RC(packT(P.w(sp + "feed_forward.4.weight"), 0, 256, 128, lin[1]));
+    LFSR_RC(packT(P.w(sp + "feed_forward.1.weight"), 0, 128, 256, lin[2]));
+    LFSR_RC(packT(P.w(sp + "attention.out_proj.weight"), 0, 128, 128, lin[3]));
+    LFSR_RC(packT(P.w(sp + "attention.in_proj_weight"), 0, 128, 256, lin[4]));
+    LFSR_RC(packT(P.w(sp + "attention.in_proj_weight"), 256, 128, 128, lin[5]));
+    LFSR_RC(packT(P.w(an + "feed_forward.4.weight"), 0, 128, 64, lin[6]));
+    LFSR_RC(packT(P.w(an + "feed_forward.1.weight"), 0, 64, 128, lin[7]));
+    LFSR_RC(packT(P.w(an + "attention.out_proj.weight"), 0, 64, 64, lin[8]));
+    LFSR_RC(packT(P.w(an + "attention.in_proj_weight"), 0, 64, 128, lin[9]));
+    LFSR_RC(packT(P.w(an + "attention.in_proj_weight"), 128, 64, 64, lin[10]));
+    LFSR_RC(pack3T(sp + "MLP.weight#lo", t.mloT[b]));
+    LFSR_RC(pack3T(sp + "MLP.weight#hi", t.mhiT[b]));
 
     // ---- SpaTrans (LFT.py:188-203): x[b+1] = linear.0(sf), sf = sm + FFN(LN(sm)), sm = out_proj(attn) + st ----------------------
-    RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, dX, 64, lin[0], t.dsf, 128, nullptr, 0, nullptr, 0, 128));
-    RC(wgrad_lin(dX, 64, 64, f.sf[b], 128, 128, G(sp + "linear.0.weight")));
-    RC(lfsr_layernorm_fwd(f.sm[b], 128, 0, nullptr, 0, 0, 1, P.w(sp + "feed_forward.0.weight"), P.w(sp + "feed_forward.0.bias"), t.lnt, 128, 0, npix, 128, 1e-5f, stream));
-    RC(lfsr_linear_fwd(t.lnt, 128, 0, 128, P.w(sp + "feed_forward.1.weight"), nullptr, nullptr, 0, 0, t.hid_s[b], 256, 0, npix, 256, 0.0f, stream));   // ReLU(hidden)
-    RC(wgrad_lin(t.dsf, 128, 128, t.hid_s[b], 256, 256, G(sp + "feed_forward.4.weight")));
-    RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dsf, 128, lin[1], t.dh, 256, nullptr, 0, t.hid_s[b], 256, 256));
-    RC(wgrad_lin(t.dh, 256, 256, t.lnt, 128, 128, G(sp + "feed_forward.1.weight")));
-    RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 256, 2>, t.dh, 256, lin[2], t.dln, 128, nullptr, 0, nullptr, 0, 128));
-    RC(ln_bwd(128, f.sm[b], nullptr, 1, 1, sp + "feed_forward.0.weight", sp + "feed_forward.0.bias", t.dln, t.dsf, t.dsm));
-    RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dsm, 128, lin[3], t.dso, 128, nullptr, 0, nullptr, 0, 128));
-    RC(wgrad_lin(t.dsm, 128, 128, f.so[b], 128, 128, G(sp + "attention.out_proj.weight")));
+    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, dX, 64, lin[0], t.dsf, 128, nullptr, 0, nullptr, 0, 128));
+    LFSR_RC(wgrad_lin(dX, 64, 64, f.sf[b], 128, 128, G(sp + "linear.0.weight")));
+    LFSR_RC(lfsr_layernorm_fwd(f.sm[b], 128, 0, nullptr, 0, 0, 1, P.w(sp + "feed_forward.0.weight"), P.w(sp + "feed_forward.0.bias"), t.lnt, 128, 0, npix, 128, 1e-5f, stream));
+    LFSR_RC(lfsr_linear_fwd(t.lnt, 128, 0, 128, P.w(sp + "feed_forward.1.weight"), nullptr, nullptr, 0, 0, t.hid_s[b], 256, 0, npix, 256, 0.0f, stream));   // ReLU(hidden)
+    LFSR_RC(wgrad_lin(t.dsf, 128, 128, t.hid_s[b], 256, 256, G(sp + "feed_forward.4.weight")));
+    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dsf, 128, lin[1], t.dh, 256, nullptr, 0, t.hid_s[b], 256, 256));
+    LFSR_RC(wgrad_lin(t.dh, 256, 256, t.lnt, 128, 128, G(sp + "feed_forward.1.weight")));
+    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 256, 2>, t.dh, 256, lin[2], t.dln, 128, nullptr, 0, nullptr, 0, 128));
+    LFSR_RC(ln_bwd(128, f.sm[b], nullptr, 1, 1, sp + "feed_forward.0.weight", sp + "feed_forward.0.bias", t.dln, t.dsf, t.dsm));
+    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dsm, 128, lin[3], t.dso, 128, nullptr, 0, nullptr, 0, 128));
+    LFSR_RC(wgrad_lin(t.dsm, 128, 128, f.so[b], 128, 128, G(sp + "attention.out_proj.weight")));
     // window [i-2, i+3) x [j-2, min(h, j+3)): the column clamp uses h (LFT.py:168), as the forward
-    RC(attn_bwd(16, f.sqk[b], 256, 128, f.sv[b], 128, f.so[b], t.dso, 128, t.dqk, t.dv, nimg, 1, 1, HW, 0, 0, h, w, w, 1, 2, 3, 2, 3, h));
+    LFSR_RC(attn_bwd(16, f.sqk[b], 256, 128, f.sv[b], 128, f.so[b], t.dso, 128, t.dqk, t.dv, nimg, 1, 1, HW, 0, 0, h, w, w, 1, 2, 3, 2, 3, h));
     // q | k = LN(st + spe) W[0:256]^T, v = st W[256:384]^T
-    RC(lfsr_layernorm_fwd(f.st[b], 128, 0, f.spe[b], 128, HW, 1, P.w(sp + "norm.weight"), P.w(sp + "norm.bias"), t.lnt, 128, 0, npix, 128, 1e-5f, stream));
+    LFSR_RC(lfsr_layernorm_fwd(f.st[b], 128, 0, f.spe[b], 128, HW, 1, P.w(sp + "norm.weight"), P.w(sp + "norm.bias"), t.lnt, 128, 0, npix, 128, 1e-5f, stream));
     float* dWin = G(sp + "attention.in_proj_weight");
-    RC(wgrad_lin(t.dqk, 256, 256, t.lnt, 128, 128, dWin));
-    RC(wgrad_lin(t.dv, 128, 128, f.st[b], 128, 128, dWin + 256 * 128));
-    RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 256, 2>, t.dqk, 256, lin[4], t.dln, 128, nullptr, 0, nullptr, 0, 128));
-    RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dv, 128, lin[5], t.dst, 128, t.dsm, 128, nullptr, 0, 128));
-    RC(ln_bwd(128, f.st[b], f.spe[b], HW, 1, sp + "norm.weight", sp + "norm.bias", t.dln, nullptr, t.dln2));
-    RC(ew(t.dst, 128, t.dln2, 128, nullptr, 0, 1.0f, t.dst, 128, 128, npix));
+    LFSR_RC(wgrad_lin(t.dqk, 256, 256, t.lnt, 128, 128, dWin));
+    LFSR_RC(wgrad_lin(t.dv, 128, 128, f.st[b], 128, 128, dWin + 256 * 128));
+    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 256, 2>, t.dqk, 256, lin[4], t.dln, 128, nullptr, 0, nullptr, 0, 128));
+    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dv, 128, lin[5], t.dst, 128, t.dsm, 128, nullptr, 0, 128));
+    LFSR_RC(ln_bwd(128, f.st[b], f.spe[b], HW, 1, sp + "norm.weight", sp + "norm.bias", t.dln, nullptr, t.dln2));
+    LFSR_RC(ew(t.dst, 128, t.dln2, 128, nullptr, 0, 1.0f, t.dst, 128, 128, npix));
     // st = MLP(unfold(ay)), spe = MLP(unfold(spa_position)): MLP.weight also gets the LayerNorm-input gradient summed over the images
     hipLaunchKernelGGL(k_pe_reduce, dim3(lfsr_blocks((long long)HW * 128, 256)), dim3(256), 0, st, t.dln2, t.dspe, nimg, HW);
-    RC(launched());
+    LFSR_RC(launched());
     float* dWm = G(sp + "MLP.weight");
     for (int half = 0; half < 2; ++half) {
-      RC(wgrad(LFSR_IN_CONV3, t.dst, 128, 64 * half, f.ay[b], 64, npix, 64, 64, 9, dWm + half * 64 * 576, 0));
-      RC(lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_CONV3, t.dspe, 128, 64 * half, f.spos, 64, 0, t.part, HW, 64, 64, 1, h, w, 9, st));
-      RC(lfsr_wgrad_reduce(t.part, lfsr_wgrad_splits(HW, 9, 64), nullptr, 0, dWm + half * 64 * 576, 64, 64, 9, 0, 0, 1, 0, 0, st));
+      LFSR_RC(wgrad(LFSR_IN_CONV3, t.dst, 128, 64 * half, f.ay[b], 64, npix, 64, 64, 9, dWm + half * 64 * 576, 0));
+      LFSR_RC(lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_CONV3, t.dspe, 128, 64 * half, f.spos, 64, 0, t.part, HW, 64, 64, 1, h, w, 9, st));
+      LFSR_RC(lfsr_wgrad_reduce(t.part, lfsr_wgrad_splits(HW, 9, 64), nullptr, 0, dWm + half * 64 * 576, 64, 64, 9, 0, 0, 1, 0, 0, st));
     }
-    RC(dgrad3(t.dst, 128, 0, t.mloT[b], t.d64, nullptr, nullptr));
-    RC(dgrad3(t.dst, 128, 64, t.mhiT[b], t.t64, t.d64, nullptr));   // t64 = dL/d ay
+    LFSR_RC(dgrad3(t.dst, 128, 0, t.mloT[b], t.d64, nullptr, nullptr));
+    LFSR_RC(dgrad3(t.dst, 128, 64, t.mhiT[b], t.t64, t.d64, nullptr));   // t64 = dL/d ay
 
     // ---- AngTrans (LFT.py:233-246): ay = am + FFN(LN(am)), am = out_proj(attn) + x[b] ---------------------------------------------
-    RC(lfsr_layernorm_fwd(f.am[b], 64, 0, nullptr, 0, 0, 1, P.w(an + "feed_forward.0.weight"), P.w(an + "feed_forward.0.bias"), t.lnt, 64, 0, npix, 64, 1e-5f, stream));
-    RC(lfsr_linear_fwd(t.lnt, 64, 0, 64, P.w(an + "feed_forward.1.weight"), nullptr, nullptr, 0, 0, t.hid_a[b], 128, 0, npix, 128, 0.0f, stream));
-    RC(wgrad_lin(t.t64, 64, 64, t.hid_a[b], 128, 128, G(an + "feed_forward.4.weight")));
-    RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.t64, 64, lin[6], t.dh, 128, nullptr, 0, t.hid_a[b], 128, 128));
-    RC(wgrad_lin(t.dh, 128, 128, t.lnt, 64, 64, G(an + "feed_forward.1.weight")));
-    RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dh, 128, lin[7], t.dln, 64, nullptr, 0, nullptr, 0, 64));
-    RC(ln_bwd(64, f.am[b], nullptr, 1, 1, an + "feed_forward.0.weight", an + "feed_forward.0.bias", t.dln, t.t64, t.dsm));   // dsm: dL/d am (64)
-    RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dsm, 64, lin[8], t.dso, 64, nullptr, 0, nullptr, 0, 64));
-    RC(wgrad_lin(t.dsm, 64, 64, f.ao[b], 64, 64, G(an + "attention.out_proj.weight")));
-    RC(attn_bwd(8, f.aqk[b], 128, 64, f.av[b], 64, f.ao[b], t.dso, 64, t.dqk, t.dv, B, h, w, (long long)AA * HW, w, 1, AA, 1, HW, 0, AA, AA, 0, 1, 0));
-    RC(lfsr_layernorm_fwd(f.x[b], 64, 0, f.ape, 64, AA, HW, P.w(an + "norm.weight"), P.w(an + "norm.bias"), t.lnt, 64, 0, npix, 64, 1e-5f, stream));
+    LFSR_RC(lfsr_layernorm_fwd(f.am[b], 64, 0, nullptr, 0, 0, 1, P.w(an + "feed_forward.0.weight"), P.w(an + "feed_forward.0.bias"), t.lnt, 64, 0, npix, 64, 1e-5f, stream));
+    LFSR_RC(lfsr_linear_fwd(t.lnt, 64, 0, 64, P.w(an + "feed_forward.1.weight"), nullptr, nullptr, 0, 0, t.hid_a[b], 128, 0, npix, 128, 0.0f, stream));
+    LFSR_RC(wgrad_lin(t.t64, 64, 64, t.hid_a[b], 128, 128, G(an + "feed_forward.4.weight")));
+    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.t64, 64, lin[6], t.dh, 128, nullptr, 0, t.hid_a[b], 128, 128));
+    LFSR_RC(wgrad_lin(t.dh, 128, 128, t.lnt, 64, 64, G(an + "feed_forward.1.weight")));
+    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dh, 128, lin[7], t.dln, 64, nullptr, 0, nullptr, 0, 64));
+    LFSR_RC(ln_bwd(64, f.am[b], nullptr, 1, 1, an + "feed_forward.0.weight", an + "feed_forward.0.bias", t.dln, t.t64, t.dsm));   // dsm: dL/d am (64)
+    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dsm, 64, lin[8], t.dso, 64, nullptr, 0, nullptr, 0, 64));
+    LFSR_RC(wgrad_lin(t.dsm, 64, 64, f.ao[b], 64, 64, G(an + "attention.out_proj.weight")));
+    LFSR_RC(attn_bwd(8, f.aqk[b], 128, 64, f.av[b], 64, f.ao[b], t.dso, 64, t.dqk, t.dv, B, h, w, (long long)AA * HW, w, 1, AA, 1, HW, 0, AA, AA, 0, 1, 0));
+    LFSR_RC(lfsr_layernorm_fwd(f.x[b], 64, 0, f.ape, 64, AA, HW, P.w(an + "norm.weight"), P.w(an + "norm.bias"), t.lnt, 64, 0, npix, 64, 1e-5f, stream));
     dWin = G(an + "attention.in_proj_weight");
-    RC(wgrad_lin(t.dqk, 128, 128, t.lnt, 64, 64, dWin));
-    RC(wgrad_lin(t.dv, 64, 64, f.x[b], 64, 64, dWin + 128 * 64));
-    RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dqk, 128, lin[9], t.dln, 64, nullptr, 0, nullptr, 0, 64));
+    LFSR_RC(wgrad_lin(t.dqk, 128, 128, t.lnt, 64, 64, dWin));
+    LFSR_RC(wgrad_lin(t.dv, 64, 64, f.x[b], 64, 64, dWin + 128 * 64));
+    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dqk, 128, lin[9], t.dln, 64, nullptr, 0, nullptr, 0, 64));
     float* dXp = t.dx[(nl - b) & 1];
-    RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dv, 64, lin[10], dXp, 64, t.dsm, 64, nullptr, 0, 64));
-    RC(ln_bwd(64, f.x[b], f.ape, AA, HW, an + "norm.weight", an + "norm.bias", t.dln, dXp, dXp));
+    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dv, 64, lin[10], dXp, 64, t.dsm, 64, nullptr, 0, 64));
+    LFSR_RC(ln_bwd(64, f.x[b], f.ape, AA, HW, an + "norm.weight", an + "norm.bias", t.dln, dXp, dXp));
     dX = dXp;
   }
 
   // ---- init: buf0 = lrelu(conv_init.4(c2)) + f0, c2 = lrelu(conv_init.2(c1)), c1 = lrelu(conv_init.0(f0)), f0 = conv_init0(x) ------------
-  RC(ew(t.dbuf0, 64, dX, 64, nullptr, 0, 1.0f, t.dbuf0, 64, 64, npix));
-  RC(pack3T("conv_init.0.weight", t.initT[0]));
-  RC(pack3T("conv_init.2.weight", t.initT[1]));
-  RC(pack3T("conv_init.4.weight", t.initT[2]));
+  LFSR_RC(ew(t.dbuf0, 64, dX, 64, nullptr, 0, 1.0f, t.dbuf0, 64, 64, npix));
+  LFSR_RC(pack3T("conv_init.0.weight", t.initT[0]));
+  LFSR_RC(pack3T("conv_init.2.weight", t.initT[1]));
+  LFSR_RC(pack3T("conv_init.4.weight", t.initT[2]));
   // conv_init.4's LeakyReLU output without the residual, for its mask (the forward's launch minus r1)
-  RC(lfsr_conv3x3_fwd(f.c2, 64, 0, P.w("conv_init.4.weight"), t.r4, 64, 0, nullptr, 0, 0, nullptr, 0, 0, nimg, h, w, L, stream));
-  RC(ew(t.dbuf0, 64, nullptr, 0, t.r4, 64, L, t.d64, 64, 64, npix));
-  RC(wgrad(LFSR_IN_CONV3, t.d64, 64, 0, f.c2, 64, npix, 64, 64, 9, G("conv_init.4.weight"), 0));
-  RC(dgrad3(t.d64, 64, 0, t.initT[2], t.t64, nullptr, f.c2));
-  RC(wgrad(LFSR_IN_CONV3, t.t64, 64, 0, f.c1, 64, npix, 64, 64, 9, G("conv_init.2.weight"), 0));
-  RC(dgrad3(t.t64, 64, 0, t.initT[1], t.d64, nullptr, f.c1));
-  RC(wgrad(LFSR_IN_CONV3, t.d64, 64, 0, f.f0, 64, npix, 64, 64, 9, G("conv_init.0.weight"), 0));
-  RC(dgrad3(t.d64, 64, 0, t.initT[0], t.t64, t.dbuf0, nullptr));
-  RC(lfsr_init_gather9(x, t.xg9, B, A, h, w, st));
-  RC(wgrad(LFSR_IN_SAME, t.t64, 64, 0, t.xg9, 16, npix, 64, 16, 1, G("conv_init0.0.weight"), 0, 9));
-#undef RC
+  LFSR_RC(lfsr_conv3x3_fwd(f.c2, 64, 0, P.w("conv_init.4.weight"), t.r4, 64, 0, nullptr, 0, 0, nullptr, 0, 0, nimg, h, w, L, stream));
+  LFSR_RC(ew(t.dbuf0, 64, nullptr, 0, t.r4, 64, L, t.d64, 64, 64, npix));
+  LFSR_RC(wgrad(LFSR_IN_CONV3, t.d64, 64, 0, f.c2, 64, npix, 64, 64, 9, G("conv_init.4.weight"), 0));
+  LFSR_RC(dgrad3(t.d64, 64, 0, t.initT[2], t.t64, nullptr, f.c2));
+  LFSR_RC(wgrad(LFSR_IN_CONV3, t.t64, 64, 0, f.c1, 64, npix, 64, 64, 9, G("conv_init.2.weight"), 0));
+  LFSR_RC(dgrad3(t.t64, 64, 0, t.initT[1], t.d64, nullptr, f.c1));
+  LFSR_RC(wgrad(LFSR_IN_CONV3, t.d64, 64, 0, f.f0, 64, npix, 64, 64, 9, G("conv_init.0.weight"), 0));
+  LFSR_RC(dgrad3(t.d64, 64, 0, t.initT[0], t.t64, t.dbuf0, nullptr));
+  LFSR_RC(lfsr_init_gather9(x, t.xg9, B, A, h, w, st));
+  LFSR_RC(wgrad(LFSR_IN_SAME, t.t64, 64, 0, t.xg9, 16, npix, 64, 16, 1, G("conv_init0.0.weight"), 0, 9));
   return LFSR_OK;
 }
 

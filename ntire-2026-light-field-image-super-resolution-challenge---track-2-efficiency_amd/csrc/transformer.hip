@@ -13,7 +13,7 @@
 #include <stdlib.h>
 
 #include "gemm_gather_kernel.h"
-#include "lfsr_internal.h"
+#include "param_table.h"
 
 namespace {
 
@@ -609,3 +609,74 @@ int lfsr_hr_tail_fwd(const float* hr, const float* w, const float* x_lr, float* 
 }
 
 }  // extern "C"
+
+// ---- the sublayers of the EPIT and LFT forwards (epit.cpp, lft.cpp) ---------------------------------------------------------------------
+// LayerNorms formed inside the consuming kernel: feed_forward.0 inside the fused feed-forward by default (EPIT: 293 us against 33 + 295 us, 10 launches
+// less per forward).  The attention norm inside the q | k | v projection measured SLOWER on the fp32 row-GEMM (EPIT: 334 us against 33 + 209 us --
+// each of the four q | k column panels repeats the norm of its row tile, and 384 x 128 fp32 weights do not fit one block's LDS; LFT: 1464 against
+// 143 + 795 us for SpaTrans at 32 patches) and pays on the three-term bf16 row-GEMM with 128-column panels (EPIT 818 -> 831, LFT 1636 -> 1680
+// patches/s), so it is the default there.  LFSR_LN_FUSE=0: every norm its own launch; 1: the attention norms as launches; 2: both fused.
+LfsrTransSel lfsr_trans_sel() {
+  const char* lf = lfsr_sel("LFSR_LN_FUSE");
+  const char* rgs = lfsr_sel("LFSR_ROWGEMM");
+  const char* psel = lfsr_sel("LFSR_FFN_PRESPLIT");
+  const bool rowgemm_f32 = (rgs && (rgs[0] == 'f' || rgs[0] == '1')) || lfsr_arith_f32();
+  LfsrTransSel s;
+  s.ln_fuse = !(lf && lf[0] == '0');
+  s.ln_fuse_qkv = lf ? lf[0] == '2' : !rowgemm_f32;
+  s.ffn_fused = !lfsr_sel("LFSR_NO_FFN_FUSED");     // LFSR_NO_FFN_FUSED: the two-launch form (A/B runs)
+  s.presplit = !(psel && psel[0] == '0');             // LFSR_FFN_PRESPLIT=0: the kernel splits the weight chunks itself (A/B runs)
+  s.up_tail = !lfsr_sel("LFSR_NO_UPTAIL");
+  return s;
+}
+
+int lfsr_trans_head(const LfsrParamTable& P, const float* x, float* f0, float* c1, float* c2, float* buf0, int B, int A, int h, int w, void* stream) {
+  const int nimg = B * A * A;
+  auto conv = [&](const float* in, const char* key, float* o, const float* r1) -> int {
+    return lfsr_conv3x3_fwd(in, 64, 0, P.w(key), o, 64, 0, r1, 64, 0, nullptr, 0, 0, nimg, h, w, 0.2f, stream);   // LeakyReLU(0.2)
+  };
+  LFSR_RC(lfsr_initconv_fwd(x, P.w("conv_init0.0.weight"), f0, 64, 0, B, A, h, w, stream));
+  LFSR_RC(conv(f0, "conv_init.0.weight", c1, nullptr));
+  LFSR_RC(conv(c1, "conv_init.2.weight", c2, nullptr));
+  return conv(c2, "conv_init.4.weight", buf0, f0);
+}
+
+int lfsr_trans_qkv(const LfsrTransSel& sel, const LfsrParamTable& P, const std::string& pre, const float* x, int E, const float* pe, long long pe_rows,
+                   long long pe_div, float* qk, float* v, float* tn, long long M, void* stream) {
+  const float *W = P.w(pre + "attention.in_proj_weight"), *g = P.w(pre + "norm.weight"), *b = P.w(pre + "norm.bias");
+  const int rc = sel.ln_fuse_qkv ? lfsr_rowgemm_ln_launch(x, E, 0, E, W, g, b, 1e-5f, 2 * E, pe, pe ? E : 0, pe_rows, pe_div, qk, 2 * E, 0, v, E, 0, 2 * E,
+                                                          M, 3 * E, lfsr_stream(stream))
+                                 : LFSR_E_ARG;
+  if (rc != LFSR_E_ARG) return rc;
+  LFSR_RC(lfsr_layernorm_fwd(x, E, 0, pe, pe ? E : 0, pe ? pe_rows : 0, pe_div, g, b, tn, E, 0, M, E, 1e-5f, stream));
+  LFSR_RC(lfsr_linear_fwd(tn, E, 0, E, W, nullptr, nullptr, 0, 0, qk, 2 * E, 0, M, 2 * E, 1.0f, stream));      // q | k from the norm
+  return lfsr_linear_fwd(x, E, 0, E, W + 2 * E * E, nullptr, nullptr, 0, 0, v, E, 0, M, E, 1.0f, stream);       // v from the raw rows
+}
+
+int lfsr_trans_ffn(const LfsrTransSel& sel, const LfsrParamTable& P, const std::string& pre, const float* x, int E, size_t split_off, float* y, float* lnx,
+                   float* hid, long long M, void* stream) {
+  const float *g = P.w(pre + "feed_forward.0.weight"), *b = P.w(pre + "feed_forward.0.bias");
+  const float *W1 = P.w(pre + "feed_forward.1.weight"), *W4 = P.w(pre + "feed_forward.4.weight");
+  const int rc = (sel.ln_fuse && sel.ffn_fused) ? lfsr_ffn_ln_launch(x, E, 0, g, b, 1e-5f, W1, W4, x, E, 0, y, E, 0, M, E, 2 * E, E, 0.0f, lfsr_stream(stream),
+                                                                     sel.presplit ? P.packed + split_off : nullptr)
+                                                : LFSR_E_ARG;
+  if (rc != LFSR_E_ARG) return rc;
+  LFSR_RC(lfsr_layernorm_fwd(x, E, 0, nullptr, 0, 0, 1, g, b, lnx, E, 0, M, E, 1e-5f, stream));
+  if (sel.ffn_fused) return lfsr_ffn_fwd(lnx, E, 0, W1, W4, x, E, 0, y, E, 0, M, E, 2 * E, E, 0.0f, stream);
+  LFSR_RC(lfsr_linear_fwd(lnx, E, 0, E, W1, nullptr, nullptr, 0, 0, hid, 2 * E, 0, M, 2 * E, 0.0f, stream));   // ReLU; the hidden rows go through HBM
+  return lfsr_linear_fwd(hid, 2 * E, 0, 2 * E, W4, nullptr, x, E, 0, y, E, 0, M, E, 1.0f, stream);
+}
+
+size_t lfsr_trans_ffn_reserve(LfsrParamTable& P, int E) { return P.reserve((lfsr_ffn_b3_presplit_bytes(E, 2 * E, E) + 3) / 4); }
+
+int lfsr_trans_ffn_presplit(const LfsrParamTable& P, const std::string& pre, int E, size_t split_off, void* stream) {
+  return lfsr_ffn_b3_presplit(P.w(pre + "feed_forward.1.weight"), P.w(pre + "feed_forward.4.weight"), E, 2 * E, E, P.packed + split_off, lfsr_stream(stream));
+}
+
+int lfsr_trans_tail(const LfsrTransSel& sel, const LfsrParamTable& P, const float* f, const float* x, float* out, float* hr, int B, int A, int h, int w, int s,
+                    void* stream) {
+  const float *W0 = P.w("upsampling.0.weight"), *W3 = P.w("upsampling.3.weight");
+  if ((s == 2 || s == 4) && sel.up_tail) return lfsr_up_tail_fwd(f, 64, 0, W0, W3, x, out, B, A, h, w, s, 0.2f, stream);
+  LFSR_RC(lfsr_upsample_ps_fwd(f, 64, 0, W0, hr, B, A, h, w, s, stream));
+  return lfsr_hr_tail_fwd(hr, W3, x, out, B, A, h, w, s, 0.2f, stream);
+}
