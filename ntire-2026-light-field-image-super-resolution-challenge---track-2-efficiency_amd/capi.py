@@ -334,6 +334,10 @@ def max_patches_per_launch(A, h, w, widest_row_floats, limit=1 << 31):
     """The kernels address their operands with 32-bit BYTE offsets (buffer descriptors: an out-of-range offset is a dropped access), so every activation tensor of one
     forward must stay below 2 GiB -- 1 GiB for DistgSSR, whose F(4x4,3x3) conv kernel keeps one more bit for its "outside the image" offsets: B * A^2 * h * w pixels x the
     widest row (DistgSSR: the 144-channel concat buffer, counted as 160; EPIT / LFT: the 256-float q | k rows).
+    LF_InterNet is the exception: its batches are split by 256-float rows too, but its widest tensor is the 320-float concat of the spatial group outputs, which
+    therefore passes 2 GiB in one launch sequence (5x5 x 32x32: B = 66..81).  Every kernel that touches it addresses with 64 bits there (the gather-GEMM's
+    non-descriptor loads, long-long row indices in the slice copies), and lfsr_internet_forward bounds it at 2^31 FLOATS; checked against fp64 at B = 66 in
+    tests/test_gpu_internet_geometries.py::test_forward_batch_66_concat_past_2_gib.
     The C entry points return LFSR_E_ARG beyond that; the runtimes below split a larger batch into equal launches instead (patches are independent and the path is
     batch-invariant bit for bit -- tests/test_gpu_distgssr.py::test_batch32_equals_single_patches -- so the split changes no value)."""
     per_patch = A * A * h * w * widest_row_floats * 4

@@ -146,6 +146,7 @@ size_t lfsr_internet_workspace_bytes(const lfsr_internet* c, int B, int h, int w
 
 int lfsr_internet_forward(lfsr_internet* c, const float* x, float* out, int B, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
   if (!c || !c->run_args_ok(x, out, B, h, w, workspace)) return LFSR_E_ARG;
+  if (c->ngroups != 4) return LFSR_E_ARG;   // SpaBottle is instantiated for 5 x 64 input channels: refused before anything is launched
   LfsrArena ws(workspace);
   float* buf[8];
   internet_layout(c, B, h, w, ws, buf);
@@ -192,7 +193,6 @@ int lfsr_internet_forward(lfsr_internet* c, const float* x, float* out, int B, i
   // BottleNeck (LF_InterNet.py:119-124)
   LFSR_RC(lfsr_linear_fwd(CA, ca_stride, 0, 64 * G, P.w("BottleNeck.AngBottle.weight"), nullptr, nullptr, 0, 0, Ar[0], 128, 0, nlr, 64, 0.0f, stream));
   LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, Ar[0], 128, 0, P.w("BottleNeck.Ang2Spa.0.weight"), CS, cs_stride, 64 * G, nullptr, 0, 0, (int)nlr, AA * 64, 1, 64, 1.0f));
-  if (G != 4) return LFSR_E_ARG;   // SpaBottle instantiated for 5 x 64 input channels
   LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 320, 2>, CS, cs_stride, 0, P.w("BottleNeck.SpaBottle.weight"), BO, 64, 0, XS0, 64, 0, (int)npix, 64, 9, 64, 0.0f));
   // ReconBlock (LF_InterNet.py:136-141), folded: 3x3 conv 64 -> s^2, epilogue = MacPI2SAI + PixelShuffle(s)
   LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_PS_HR, 64, 1>, BO, 64, 0, P.packed + c->off_wf, out, 1, 0, nullptr, 0, 0, (int)npix, c->s * c->s, 9, 1, 1.0f));

@@ -190,7 +190,11 @@ void train_layout(const lfsr_internet* c, int B, int h, int w, LfsrArena& ws, In
 }
 
 // geometry the training path covers: the forward's per-tensor bound (the widest tensor, the 320-channel concat, below 2^31 floats), the
-// upstream configuration n_groups = n_layers = 4
+// upstream configuration n_groups = n_layers = 4.
+// The bound is in floats, not bytes: CS / dCS may span 2 GiB and more, and every launch that touches them then addresses with 64 bits --
+// the gather-GEMM takes its non-descriptor loads (launch_gemm's addr32), the 3x3 data gradients into dCS leave the Winograd kernels
+// (F(4x4) declines from 1 GiB, F(2x2) from 2 GiB) for the direct halo kernel, whose addresses are long long, as are those of the generic
+// weight gradient (k_wgrad: an int pixel index times a long long stride) and of k_ew64 / k_copy64.  Only the pixel COUNT has to fit an int.
 bool train_geometry_ok(const lfsr_internet* c, int B, int h, int w) {
   if (!c || B <= 0 || h <= 0 || w <= 0 || c->ngroups != NG || c->nlayers != NL) return false;
   const long long npix = (long long)B * c->A * c->A * h * w;

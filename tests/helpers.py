@@ -120,3 +120,138 @@ def hip_mask_to_ref(mask_flat, kind, B, A, h, w):
 
 def ref_mask_to_hip(mask_ref, kind, B, A, h, w):
     return mask_ref.reshape(-1)[mask_perm(kind, B, A, h, w)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# LF_InterNet: the parameter table at any angRes / scale, the reference graph with every intermediate the HIP training forward saves
+# (lfsr_internet_train_saved), and the maps between the graph's layouts and the HIP path's rows
+# ---------------------------------------------------------------------------------------------------------------------
+# (A, s, B, h, w) and what each row reaches
+INTERNET_MATRIX = ((7, 2, 1, 5, 6),       # 49 gather taps, 3136 Ang2Spa GEMM columns, AngFE rows padded 49 -> 52
+                   (2, 3, 2, 9, 7),       # even A (no centre view), scale 3, odd ragged views, AngFE rows 4 wide exactly
+                   (4, 4, 1, 6, 5),       # even A, A^2 = 16, scale 4
+                   (5, 3, 2, 13, 16),     # the benchmark's angRes at scale 3; 81.25 row tiles of 128 pixels, 3.25 tiles of LR pixels
+                   (3, 2, 3, 33, 40),     # views larger than 32x32; 3960 LR pixels: the row-streaming GEMM forms in inference
+                   (9, 2, 1, 4, 4),       # largest accepted angRes, AngFE rows padded 81 -> 84
+                   (1, 2, 2, 8, 8),       # smallest accepted angRes: one gather tap
+                   (5, 2, 3, 32, 32),     # SpaBottle's gather spans >= 2 GiB: 64-bit addresses
+                   (5, 2, 8, 32, 32))     # SpaBottle and SpaConvSq on them: the published training geometry
+
+
+def internet_spec(A, s, n_groups=4, n_layers=4):
+    """(key, shape) list of LF_InterNet at angRes A and scale s: lfsr_internet_create's table (model/SR/LF_InterNet.py's state_dict)"""
+    spec = [("AngFE.0.weight", (64, 1, A, A)), ("SpaFE.0.weight", (64, 1, 3, 3))]
+    for g in range(n_groups):
+        for l in range(n_layers):
+            q = f"CascadeInterBlock.body.{g}.chained_layers.{l}."
+            spec += [(q + "Spa2Ang.weight", (64, 64, A, A)), (q + "Ang2Spa.0.weight", (A * A * 64, 64, 1, 1)),
+                     (q + "AngConvSq.weight", (64, 128, 1, 1)), (q + "SpaConvSq.weight", (64, 128, 3, 3))]
+    spec += [("BottleNeck.AngBottle.weight", (64, 64 * n_groups, 1, 1)), ("BottleNeck.Ang2Spa.0.weight", (A * A * 64, 64, 1, 1)),
+             ("BottleNeck.SpaBottle.weight", (64, 64 * (n_groups + 1), 3, 3)),
+             ("ReconBlock.PreConv.weight", (64 * s * s, 64, 3, 3)), ("ReconBlock.FinalConv.weight", (1, 64, 1, 1))]
+    return spec
+
+
+def internet_case(A, s, B, h, w):
+    """-> (state_dict, input): synth_state_dict seed 0 / synth_input seed 1, as the golden cases"""
+    return synth_state_dict(internet_spec(A, s), seed=0), synth_input((B, 1, A * h, A * w), seed=1)
+
+
+# kind -> (which of lfsr_internet_train_saved, channel slice of the 128-wide rows, layout, per chain layer)
+INTERNET_SAVED = {"xs": (0, (0, 64), "vcl", True), "spa2": (0, (64, 128), "vcl", True), "xa": (1, (0, 64), "lr", True), "ang2": (1, (64, 128), "lr", True),
+                  "relu_spa": (2, None, "vcl", True), "relu_ang": (3, None, "lr", True), "relu_spabottle": (4, None, "vcl", False),
+                  "relu_angbottle": (5, None, "lr", False)}
+INTERNET_RELU_KINDS = ("ang2", "relu_spa", "relu_ang", "relu_spabottle", "relu_angbottle")      # the tensors whose signs are ReLU decisions
+
+
+def internet_keys():
+    """every (kind, index) the training forward saves: 6 per chain layer x 16, and the BottleNeck's two"""
+    return [(k, i) for k, (_, _, _, per) in INTERNET_SAVED.items() for i in (range(16) if per else (0,))]
+
+
+def internet_ref_to_rows(t, layout, A):
+    """reference layout -> the HIP path's rows x 64: MacPI (B,64,h*A,w*A) -> VCL [b][u][v][y][x][c]; (B,64,h,w) -> LR rows [b][y][x][c]"""
+    B, Cc = t.shape[:2]
+    if layout == "lr":
+        return t.permute(0, 2, 3, 1).reshape(-1, Cc)
+    h, w = t.shape[2] // A, t.shape[3] // A
+    return t.reshape(B, Cc, h, A, w, A).permute(0, 3, 5, 2, 4, 1).reshape(-1, Cc)
+
+
+def internet_rows_to_ref(v, layout, B, A, h, w):
+    """the inverse: rows x 64 in HIP order -> the reference layout"""
+    if layout == "lr":
+        return v.reshape(B, h, w, -1).permute(0, 3, 1, 2)
+    return v.reshape(B, A, A, h, w, -1).permute(0, 5, 3, 1, 4, 2).reshape(B, -1, h * A, w * A)
+
+
+def internet_saved_rows(rt, xg, kind, index=0):
+    """what forward_train(xg) saved for (kind, index), as rows x 64 in HIP order (a GPU tensor)"""
+    which, sl, _, _ = INTERNET_SAVED[kind]
+    v = rt.train_saved(xg, which, index)
+    return v.reshape(-1, 64) if sl is None else v.reshape(-1, 128)[:, sl[0]:sl[1]]
+
+
+def internet_hip_masks(rt, xg, A):
+    """the ReLU decisions (> 0) of forward_train(xg), in the reference layouts: what internet_layers_fp64's `forced` takes"""
+    B, h, w = xg.shape[0], xg.shape[2] // A, xg.shape[3] // A
+    return {(k, i): internet_rows_to_ref((internet_saved_rows(rt, xg, k, i) > 0).cpu(), INTERNET_SAVED[k][2], B, A, h, w)
+            for k, i in internet_keys() if k in INTERNET_RELU_KINDS}
+
+
+def internet_layers_fp64(x, params, A, s, forced=None, dtype=None):
+    """LF_InterNet's graph (model/SR/LF_InterNet.py:33-141) on stock torch CPU ops -> (output, layers, flips).
+    layers[(kind, index)]: every tensor of INTERNET_SAVED in the reference layout (spatial: MacPI NCHW, angular: (B,64,h,w)).
+    params: {key: tensor} (fp64 unless `dtype` says otherwise; they may require grad).  forced: {(kind, index): bool mask in the reference
+    layout} for the five ReLU kinds -- the decisions are then the caller's, and flips counts those that differ from the graph's own."""
+    import torch
+    F = torch.nn.functional
+    dtype = dtype or torch.float64
+    p = {k: torch.as_tensor(v).to(dtype) for k, v in params.items()}
+    xd = torch.as_tensor(x).to(dtype)
+    B, _, Hh, Ww = xd.shape
+    h, w = Hh // A, Ww // A
+    L, flips = {}, 0
+
+    def relu(z, key):
+        nonlocal flips
+        if forced is None:
+            y = F.relu(z)
+        else:
+            m = forced[key]
+            flips += int(((z > 0) != m).sum())
+            y = z * m.to(z.dtype)
+        L[key] = y
+        return y
+    m = xd.reshape(B, 1, A, h, A, w).permute(0, 1, 3, 2, 5, 4).reshape(B, 1, h * A, w * A)           # SAI2MacPI
+    xa, xs = F.conv2d(m, p["AngFE.0.weight"], stride=A), F.conv2d(m, p["SpaFE.0.weight"], dilation=A, padding=A)
+    ba, bs, oa_l, os_l = xa, xs, [], []
+    for g in range(4):
+        for l in range(4):
+            q, i = f"CascadeInterBlock.body.{g}.chained_layers.{l}.", g * 4 + l
+            L["xs", i], L["xa", i] = bs, ba
+            ang2 = relu(F.conv2d(bs, p[q + "Spa2Ang.weight"], stride=A), ("ang2", i))
+            spa2 = L["spa2", i] = F.pixel_shuffle(F.conv2d(ba, p[q + "Ang2Spa.0.weight"]), A)
+            oa = relu(F.conv2d(torch.cat((ba, ang2), 1), p[q + "AngConvSq.weight"]), ("relu_ang", i)) + ba
+            os_ = relu(F.conv2d(torch.cat((bs, spa2), 1), p[q + "SpaConvSq.weight"], dilation=A, padding=A), ("relu_spa", i)) + bs
+            ba, bs = oa, os_
+        oa_l.append(ba)
+        os_l.append(bs)
+    a = relu(F.conv2d(torch.cat(oa_l, 1), p["BottleNeck.AngBottle.weight"]), ("relu_angbottle", 0))
+    cs = torch.cat((torch.cat(os_l, 1), F.pixel_shuffle(F.conv2d(a, p["BottleNeck.Ang2Spa.0.weight"]), A)), 1)
+    out = relu(F.conv2d(cs, p["BottleNeck.SpaBottle.weight"], dilation=A, padding=A), ("relu_spabottle", 0)) + xs
+    pre = F.conv2d(out, p["ReconBlock.PreConv.weight"], dilation=A, padding=A)
+    pre = pre.reshape(B, pre.shape[1], h, A, w, A).permute(0, 1, 3, 2, 5, 4).reshape(B, pre.shape[1], A * h, A * w)      # MacPI2SAI
+    y = F.conv2d(F.pixel_shuffle(pre, s), p["ReconBlock.FinalConv.weight"])
+    return y, L, flips
+
+
+def forced_fp64_grads(rt, xg, sd, x, label, A, s):
+    """fp64 autograd of the reference graph with every ReLU decision taken from what the HIP training forward saved (lfsr_internet_train_saved),
+    and the number of those decisions that differ from fp64's own.  A pre-activation within fp32 rounding of 0 (seen: -1.9e-8 in fp64,
+    +8.6e-9 on the GPU) is a legitimate tie whose two sides have different gradients downstream; this graph makes the same choices."""
+    import torch
+    p = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in sd.items()}
+    y, _, flips = internet_layers_fp64(x, p, A, s, forced=internet_hip_masks(rt, xg, A))
+    torch.nn.functional.l1_loss(y, torch.as_tensor(label, dtype=torch.float64)).backward()
+    return {k: v.grad.numpy() for k, v in p.items()}, flips

@@ -10,7 +10,7 @@ import torch
 from lfsr_amd import capi
 from lfsr_amd.synth import synth_input, synth_state_dict
 from oracle.lfsr_torch_port import internet_forward
-from tests.helpers import GOLDEN, model_case
+from tests.helpers import GOLDEN, forced_fp64_grads, internet_layers_fp64, internet_ref_to_rows, internet_saved_rows, model_case
 
 pytestmark = pytest.mark.gpu
 TAGS = ("a3h6w8s4", "a5h8s2")
@@ -51,50 +51,6 @@ def port_grads(sd, x, label, A, s, dtype=torch.float64):
     loss = torch.nn.functional.l1_loss(out, torch.as_tensor(label).to(dtype))
     loss.backward()
     return float(loss.detach()), {k: p.grad.numpy() for k, p in params.items()}
-
-
-def forced_fp64_grads(rt, xg, sd, x, label, A, s):
-    """fp64 autograd of the port's graph with every ReLU decision taken from what the HIP training forward saved (lfsr_internet_train_saved),
-    and the number of those decisions that differ from fp64's own.  A pre-activation within fp32 rounding of 0 (seen: -1.9e-8 in fp64,
-    +8.6e-9 on the GPU) is a legitimate tie whose two sides have different gradients downstream; this graph makes the same choices."""
-    F = torch.nn.functional
-    p = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in sd.items()}
-    xd = torch.as_tensor(x, dtype=torch.float64)
-    B, _, Hh, Ww = xd.shape
-    h, w = Hh // A, Ww // A
-
-    def lr_mask(v):        # rows (b, y, x) x 64 -> (B, 64, h, w)
-        return (v.reshape(B, h, w, 64).permute(0, 3, 1, 2) > 0).cpu()
-
-    def vcl_mask(v):       # VCL [b][u][v][y][x][c] -> MacPI (B, 64, h*A, w*A)
-        return (v.reshape(B, A, A, h, w, 64).permute(0, 5, 3, 1, 4, 2).reshape(B, 64, h * A, w * A) > 0).cpu()
-    flips = 0
-
-    def relu(z, m):
-        nonlocal flips
-        flips += int(((z > 0) != m).sum())
-        return z * m.to(z.dtype)
-    m = xd.reshape(B, 1, A, h, A, w).permute(0, 1, 3, 2, 5, 4).reshape(B, 1, h * A, w * A)
-    xa, xs = F.conv2d(m, p["AngFE.0.weight"], stride=A), F.conv2d(m, p["SpaFE.0.weight"], dilation=A, padding=A)
-    ba, bs, oa_l, os_l = xa, xs, [], []
-    for g in range(4):
-        for l in range(4):
-            q, i = f"CascadeInterBlock.body.{g}.chained_layers.{l}.", g * 4 + l
-            ang2 = relu(F.conv2d(bs, p[q + "Spa2Ang.weight"], stride=A), lr_mask(rt.train_saved(xg, 1, i).reshape(-1, 128)[:, 64:].contiguous()))
-            spa2 = F.pixel_shuffle(F.conv2d(ba, p[q + "Ang2Spa.0.weight"]), A)
-            oa = relu(F.conv2d(torch.cat((ba, ang2), 1), p[q + "AngConvSq.weight"]), lr_mask(rt.train_saved(xg, 3, i))) + ba
-            os_ = relu(F.conv2d(torch.cat((bs, spa2), 1), p[q + "SpaConvSq.weight"], dilation=A, padding=A), vcl_mask(rt.train_saved(xg, 2, i))) + bs
-            ba, bs = oa, os_
-        oa_l.append(ba)
-        os_l.append(bs)
-    a = relu(F.conv2d(torch.cat(oa_l, 1), p["BottleNeck.AngBottle.weight"]), lr_mask(rt.train_saved(xg, 5, 0)))
-    cs = torch.cat((torch.cat(os_l, 1), F.pixel_shuffle(F.conv2d(a, p["BottleNeck.Ang2Spa.0.weight"]), A)), 1)
-    out = relu(F.conv2d(cs, p["BottleNeck.SpaBottle.weight"], dilation=A, padding=A), vcl_mask(rt.train_saved(xg, 4, 0))) + xs
-    pre = F.conv2d(out, p["ReconBlock.PreConv.weight"], dilation=A, padding=A)
-    pre = pre.reshape(B, pre.shape[1], h, A, w, A).permute(0, 1, 3, 2, 5, 4).reshape(B, pre.shape[1], A * h, A * w)
-    y = F.conv2d(F.pixel_shuffle(pre, s), p["ReconBlock.FinalConv.weight"])
-    F.l1_loss(y, torch.as_tensor(label, dtype=torch.float64)).backward()
-    return {k: v.grad.numpy() for k, v in p.items()}, flips
 
 
 def check_against_port(net, bucket, ref):
@@ -150,27 +106,11 @@ def test_grads_match_fp64_port_and_bucket(tag):
 
 
 def _relu_flips_spa(rt, xg, sd, x, A, s):
-    """ReLU decisions of SpaConvSq (16 layers) that differ between the HIP forward's saved values and the fp64 port"""
-    xd = torch.as_tensor(x, dtype=torch.float64)
-    p = {k: torch.as_tensor(v, dtype=torch.float64) for k, v in sd.items()}
-    F = torch.nn.functional
-    B, _, Hh, Ww = xd.shape
-    h, w = Hh // A, Ww // A
-    m = xd.reshape(B, 1, A, h, A, w).permute(0, 1, 3, 2, 5, 4).reshape(B, 1, h * A, w * A)
-    ba, bs = F.conv2d(m, p["AngFE.0.weight"], stride=A), F.conv2d(m, p["SpaFE.0.weight"], dilation=A, padding=A)
-    flips = 0
-    for g in range(4):
-        for l in range(4):
-            q = f"CascadeInterBlock.body.{g}.chained_layers.{l}."
-            ang2 = F.relu(F.conv2d(bs, p[q + "Spa2Ang.weight"], stride=A))
-            spa2 = F.pixel_shuffle(F.conv2d(ba, p[q + "Ang2Spa.0.weight"]), A)
-            za = F.conv2d(torch.cat((ba, ang2), 1), p[q + "AngConvSq.weight"])
-            zs = F.conv2d(torch.cat((bs, spa2), 1), p[q + "SpaConvSq.weight"], dilation=A, padding=A)
-            ref = (zs > 0).reshape(B, 64, h, A, w, A).permute(0, 3, 5, 2, 4, 1).reshape(-1)     # MacPI -> VCL [b][u][v][y][x][c]
-            hip = (rt.train_saved(xg, 2, g * 4 + l) > 0).cpu()
-            flips += int((ref != hip).sum())
-            ba, bs = F.relu(za) + ba, F.relu(zs) + bs
-    return flips
+    """ReLU decisions of SpaConvSq (16 layers) that differ between the HIP forward's saved values and the fp64 graph"""
+    with torch.no_grad():
+        _, layers, _ = internet_layers_fp64(x, sd, A, s)
+    return sum(int(((internet_ref_to_rows(layers["relu_spa", i], "vcl", A) > 0) != (internet_saved_rows(rt, xg, "relu_spa", i) > 0).cpu()).sum())
+               for i in range(16))
 
 
 def test_baseline_geometry_against_fp64():
