@@ -255,3 +255,214 @@ def forced_fp64_grads(rt, xg, sd, x, label, A, s):
     y, _, flips = internet_layers_fp64(x, p, A, s, forced=internet_hip_masks(rt, xg, A))
     torch.nn.functional.l1_loss(y, torch.as_tensor(label, dtype=torch.float64)).backward()
     return {k: v.grad.numpy() for k, v in p.items()}, flips
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# LFT: the geometry matrix, the reference graph with every tensor lfsr_lft_train_saved can return, and the maps between the graph's
+# layouts and the HIP path's rows
+# ---------------------------------------------------------------------------------------------------------------------
+# (A, s, B, h, w) and what each row reaches.  w <= h + 2 everywhere: the reference clamps the column window with h (LFT.py:168), so at
+# w >= h + 3 the last columns' queries have no key; the numpy oracle then returns NaN (softmax over an all -inf row) while torch's SDPA on
+# the CPU does not, and there is no reference to compare with.
+LFT_MATRIX = ((7, 2, 1, 5, 6),        # 49 angular tokens on k_window_attn_lds<8, 8>; odd A other than 3, 5
+              (2, 3, 2, 9, 7),        # even A, scale 3, h > w, odd ragged view
+              (4, 4, 1, 6, 8),        # even A, scale 4, w = h + 2: the widest view the reference's clamp leaves without an empty window
+              (8, 2, 1, 4, 5),        # A^2 = 64: the upper bound of the LDS angular kernel
+              (9, 2, 1, 4, 4),        # A^2 = 81: the generic k_window_attn<8>
+              (15, 2, 1, 3, 4),       # largest accepted angRes (225 tokens, 225 position-embedding rows)
+              (1, 2, 2, 8, 8),        # smallest: one-token angular attention
+              (5, 3, 2, 13, 15),      # the benchmark's angRes at scale 3; npix 9 750: k_tail_bwd loops with s^2 = 9; w = h + 2 at A = 5
+              (3, 2, 1, 40, 36),      # views wider than 32: spatial attention off the 5x5 MFMA kernel, several conv tiles per row, fwd and bwd
+              (5, 4, 8, 32, 32))      # the published training geometry: the ragged weight-gradient splits and the grid-stride loops of k_ew
+
+# which of lfsr_lft_train_saved -> (layout, floats per row, number of indices); 0-5 are there after forward_train, 6-9 after backward
+LFT_SAVED = {0: ("vcl", 64, 5), 1: ("ang", 64, 4), 2: ("spa", 128, 4), 3: ("spa", 128, 4), 4: ("spa", 128, 4), 5: ("vcl", 64, 2),
+             6: ("ang", 128, 4), 7: ("spa", 256, 4), 8: ("vcl", 64, 1), 9: ("hr", 64, 1)}
+LFT_DECISION_KINDS = (5, 6, 7, 8, 9)      # the tensors whose signs are ReLU / LeakyReLU decisions
+LFT_PER_SAMPLE_NPIX = 50000               # above this many LR pixels the fp64 work is done one sample at a time (dense masked attention)
+
+
+def lft_keys(kinds=tuple(LFT_SAVED)):
+    """every (which, index) of `kinds`: 23 after forward_train and 10 more after backward"""
+    return [(k, i) for k in kinds for i in range(LFT_SAVED[k][2])]
+
+
+def lft_case(A, s, B, h, w):
+    """-> (state_dict, input): synth_state_dict seed 0 / synth_input seed 1, as the golden cases.  LFT's parameter shapes do not depend on
+    angRes (tests/test_lft_reference.py asserts it), so the golden angRes-5 spec serves every A"""
+    return synth_state_dict(model_spec("LFT", 5, s), seed=0), synth_input((B, 1, A * h, A * w), seed=1)
+
+
+def lft_ref_to_rows(t, layout, B):
+    """reference layout -> the HIP path's rows [b][u][v][y][x][c] (VCL).  vcl: (B, c, A^2, h, w); ang: AngTrans tokens (A^2, B h w, c);
+    spa: SpaTrans tokens (h w, B A^2, c); hr: (B, 64, A h s, A w s) -> the channel-last mosaic's rows"""
+    if layout == "vcl":
+        return t.permute(0, 2, 3, 4, 1).reshape(-1, t.shape[1])
+    if layout == "ang":
+        return t.reshape(t.shape[0], B, -1, t.shape[2]).permute(1, 0, 2, 3).reshape(-1, t.shape[2])
+    if layout == "spa":
+        return t.permute(1, 0, 2).reshape(-1, t.shape[2])
+    if layout == "hr":
+        return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
+    raise KeyError(layout)
+
+
+def lft_rows_to_ref(v, layout, B, A, h, w, s=1):
+    """the inverse: flat values in HIP order -> the reference layout"""
+    AA = A * A
+    if layout == "vcl":
+        return v.reshape(B, AA, h, w, -1).permute(0, 4, 1, 2, 3)
+    if layout == "ang":
+        c = v.numel() // (B * AA * h * w)
+        return v.reshape(B, AA, h * w, c).permute(1, 0, 2, 3).reshape(AA, B * h * w, c)
+    if layout == "spa":
+        return v.reshape(B * AA, h * w, -1).permute(1, 0, 2)
+    if layout == "hr":
+        return v.reshape(B, A * h * s, A * w * s, 64).permute(0, 3, 1, 2)
+    raise KeyError(layout)
+
+
+def lft_saved_rows(rt, xg, kind, index=0):
+    """what forward_train(xg) (kinds 0-5) or the backward after it (6-9) left for (kind, index), as rows in HIP order (a GPU tensor)"""
+    return rt.train_saved(xg, kind, index).reshape(-1, LFT_SAVED[kind][1])
+
+
+def lft_hip_masks(rt, xg, A, s, sample=None):
+    """the ReLU / LeakyReLU decisions (> 0) the HIP path took, read after its backward, in the reference layouts: what lft_layers_fp64's
+    `forced` takes.  sample = i: the decisions of sample i alone, as a B = 1 graph takes them (rows are sample-major)"""
+    B, h, w = xg.shape[0], xg.shape[2] // A, xg.shape[3] // A
+    out = {}
+    for k, i in lft_keys(LFT_DECISION_KINDS):
+        m = (lft_saved_rows(rt, xg, k, i) > 0).cpu()
+        if sample is not None:
+            n = m.shape[0] // B
+            m = m[sample * n:(sample + 1) * n]
+        out[k, i] = lft_rows_to_ref(m, LFT_SAVED[k][0], B if sample is None else 1, A, h, w, s)
+    return out
+
+
+def lft_position_encoding(lengths, dim, temperature=10000):
+    """PositionEncoding.forward LFT.py:106-130 in fp64 (sin of the even columns then cos of the odd ones, concatenated)"""
+    import torch
+    grid = torch.arange(dim, dtype=torch.float64)
+    grid = temperature ** (2 * torch.div(grid, 2, rounding_mode="floor") / dim)
+    out = []
+    for n in lengths:
+        pos = torch.arange(n, dtype=torch.float64).view(-1, 1) / grid
+        out.append(torch.cat([pos[:, 0::2].sin(), pos[:, 1::2].cos()], dim=1))
+    return out
+
+
+def lft_layers_fp64(x, params, A, s, forced=None, dtype=None):
+    """LFT's graph (model/SR/LFT.py:67-98, as oracle/lfsr_torch_port.py::lft_forward states it) on stock torch CPU ops, fp64 throughout
+    including the position encodings -> (output, layers, flips).
+    layers[(which, index)]: every tensor lfsr_lft_train_saved can return, detached, in the reference's layout (LFT_SAVED; lft_ref_to_rows).
+    params: {key: tensor} (fp64 unless `dtype` says otherwise; they may require grad).  forced: {(which, index): bool mask in the reference
+    layout} for LFT_DECISION_KINDS -- the decisions are then the caller's, and flips counts those that differ from the graph's own."""
+    import torch
+    F = torch.nn.functional
+    dtype = dtype or torch.float64
+    p = {k: torch.as_tensor(v).to(dtype) for k, v in params.items()}
+    xd = torch.as_tensor(x).to(dtype)
+    B, _, Hh, Ww = xd.shape
+    h, w, AA = Hh // A, Ww // A, A * A
+    L, flips = {}, 0
+
+    def act(z, key, slope, keep_pre=False):
+        nonlocal flips
+        if forced is None:
+            y = F.leaky_relu(z, slope) if slope else F.relu(z)
+        else:
+            m = forced[key]
+            flips += int(((z > 0) != m).sum())
+            y = torch.where(m, z, z * slope)
+        L[key] = (z if keep_pre else y).detach()
+        return y
+
+    def conv133(z, wt):       # nn.Conv3d(k=(1,3,3), pad=(0,1,1), bias=False)
+        return F.conv3d(z, wt, padding=(0, 1, 1))
+
+    def mha(qk, v, pre, mask=None):      # nn.MultiheadAttention(need_weights=False), (L, N, E), 8 heads, no biases
+        in_w, out_w = p[pre + "attention.in_proj_weight"], p[pre + "attention.out_proj.weight"]
+        Ln, N, E = qk.shape
+        heads = lambda z: z.reshape(Ln, N * 8, E // 8).transpose(0, 1)
+        o = F.scaled_dot_product_attention(heads(F.linear(qk, in_w[:E])), heads(F.linear(qk, in_w[E:2 * E])), heads(F.linear(v, in_w[2 * E:])),
+                                           attn_mask=mask)
+        return F.linear(o.transpose(0, 1).reshape(Ln, N, E), out_w)
+
+    def ffn(tok, pre, key):
+        ff = F.layer_norm(tok, tok.shape[-1:], p[pre + "feed_forward.0.weight"], p[pre + "feed_forward.0.bias"])
+        return F.linear(act(F.linear(ff, p[pre + "feed_forward.1.weight"]), key, 0.0), p[pre + "feed_forward.4.weight"]) + tok
+    # the views and their bicubic skip (LFT.py:263-273)
+    lr = xd.reshape(B, 1, A, h, A, w).permute(0, 1, 2, 4, 3, 5)
+    skip = F.interpolate(lr.reshape(B * AA, 1, h, w), scale_factor=s, mode="bicubic", align_corners=False)
+    skip = skip.reshape(B, 1, A, A, h * s, w * s).permute(0, 1, 2, 4, 3, 5).reshape(B, 1, A * h * s, A * w * s)
+    buf = conv133(lr.reshape(B, 1, AA, h, w), p["conv_init0.0.weight"])
+    t = act(conv133(buf, p["conv_init.0.weight"]), (5, 0), 0.2)
+    t = act(conv133(t, p["conv_init.2.weight"]), (5, 1), 0.2)
+    buf = act(conv133(t, p["conv_init.4.weight"]), (8, 0), 0.2) + buf
+    c = buf.shape[1]
+    ph, pw, pa = (e.to(dtype) for e in lft_position_encoding([h, w, AA], c))
+    spa_pos = ((ph[:, None, :] + pw[None, :, :]) / 2).permute(2, 0, 1).reshape(1, c, 1, h, w)
+    # SpaTrans.gen_mask LFT.py:161-174: 5x5 window, the column clamp uses h
+    i_, j_ = torch.arange(h).view(h, 1, 1, 1), torch.arange(w).view(1, w, 1, 1)
+    ii, jj = torch.arange(h).view(1, 1, h, 1), torch.arange(w).view(1, 1, 1, w)
+    ok = (ii >= i_ - 2) & (ii < i_ + 3) & (jj >= j_ - 2) & (jj < torch.clamp(j_ + 3, max=h))
+    mask = torch.full((h, w, h, w), float("-inf"), dtype=dtype)
+    mask[ok] = 0.0
+    mask = mask.reshape(h * w, h * w)
+    t = buf
+    nblk = 1 + max(int(k.split(".")[1]) for k in p if k.startswith("altblock."))
+    for i in range(nblk):
+        L[0, i] = t.detach()
+        pre = f"altblock.{i}.ang_trans."          # AngTrans LFT.py:233-246
+        tok = t.permute(2, 0, 3, 4, 1).reshape(AA, B * h * w, c)
+        tn = F.layer_norm(tok + pa.reshape(AA, 1, c), (c,), p[pre + "norm.weight"], p[pre + "norm.bias"])
+        tok = mha(tn, tok, pre) + tok
+        L[1, i] = tok.detach()
+        tok = ffn(tok, pre, (6, i))
+        t = tok.reshape(AA, B, h, w, c).permute(1, 4, 0, 2, 3)
+        pre = f"altblock.{i}.spa_trans."          # SpaTrans LFT.py:188-203
+        wm = p[pre + "MLP.weight"]
+
+        def sai2token(z):   # F.unfold(k3, pad 1) + Linear(576 -> 128), LFT.py:176-182
+            n = z.shape[0] * z.shape[2]
+            u = F.unfold(z.permute(0, 2, 1, 3, 4).reshape(n, c, h, w), kernel_size=3, padding=1)   # (n, 576, h w)
+            return F.linear(u.permute(2, 0, 1), wm)
+        tok = sai2token(t)
+        L[3, i] = tok.detach()
+        tn = F.layer_norm(tok + sai2token(spa_pos), tok.shape[-1:], p[pre + "norm.weight"], p[pre + "norm.bias"])
+        tok = mha(tn, tok, pre, mask) + tok
+        L[2, i] = tok.detach()
+        tok = ffn(tok, pre, (7, i))
+        L[4, i] = tok.detach()
+        t = F.conv3d(tok.reshape(h, w, B, AA, -1).permute(2, 4, 3, 0, 1), p[pre + "linear.0.weight"])
+    t = t + buf
+    L[0, nblk] = t.detach()
+    mosaic = t.reshape(B, c, A, A, h, w).permute(0, 1, 2, 4, 3, 5).reshape(B, c, A * h, A * w)
+    up = F.pixel_shuffle(F.conv2d(mosaic, p["upsampling.0.weight"]), s)
+    y = F.conv2d(act(up, (9, 0), 0.2, keep_pre=True), p["upsampling.3.weight"], padding=1) + skip
+    return y, L, flips
+
+
+def lft_forced_fp64_grads(rt, xg, sd, x, label, A, s):
+    """fp64 autograd of lft_layers_fp64 under L1 `mean` loss with every ReLU / LeakyReLU decision taken from what the HIP path computed
+    (lfsr_lft_train_saved, read after the backward), and the number of those decisions that differ from fp64's own.  A pre-activation within
+    fp32 rounding of 0 is a legitimate tie whose two sides have different gradients downstream (one flipped tail pixel moves the gradient of
+    a small case by ~1e-3); this graph makes the same choices.  Large batches go one sample at a time: the batch gradient of a mean loss is
+    the mean of the per-sample gradients, each under that sample's slice of the decisions."""
+    import torch
+    B, h, w = x.shape[0], x.shape[2] // A, x.shape[3] // A
+    p = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in sd.items()}
+    lab = torch.as_tensor(label, dtype=torch.float64)
+    flips = 0
+    if B > 1 and B * A * A * h * w > LFT_PER_SAMPLE_NPIX:
+        for i in range(B):
+            y, _, f = lft_layers_fp64(x[i:i + 1], p, A, s, forced=lft_hip_masks(rt, xg, A, s, sample=i))
+            (torch.nn.functional.l1_loss(y, lab[i:i + 1]) / B).backward()
+            flips += f
+            del y
+    else:
+        y, _, flips = lft_layers_fp64(x, p, A, s, forced=lft_hip_masks(rt, xg, A, s))
+        torch.nn.functional.l1_loss(y, lab).backward()
+    return {k: v.grad.numpy() for k, v in p.items()}, flips

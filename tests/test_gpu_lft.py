@@ -58,11 +58,12 @@ def test_spatial_window_attention_vs_masked_mha():
     assert np.abs(o.cpu().numpy() - ref).max() < 1e-5
 
 
-@pytest.mark.parametrize("B,A,h,w", [(2, 3, 4, 6), (1, 5, 3, 5), (2, 5, 8, 8)])
+@pytest.mark.parametrize("B,A,h,w", [(2, 3, 4, 6), (1, 5, 3, 5), (2, 5, 8, 8), (1, 8, 2, 3), (1, 9, 2, 2), (2, 1, 3, 4)])
 def test_angular_attention_vs_mha(B, A, h, w):
     """AngTrans attention (LFT.py:236-241): the A*A views at one (y, x) are the sequence, 8 heads of 8, no mask; q | k read from one 128-wide buffer, token stride = one
     view image -- the strided addressing lft.cpp uses -- against dense fp64 multi-head attention.  A = 5 runs k_ang_attn_pair (two queries per thread, four pixels per
-    block: 15 sequences leave a block with three), A = 3 the LDS-tiled kernel"""
+    block: 15 sequences leave a block with three), A = 3 and A = 8 (64 tokens, its bound) and A = 1 (one token) the LDS-tiled kernel, A = 9 the generic
+    k_window_attn<8>"""
     lib = capi.load()
     E, NH = 64, 8
     AA, HW = A * A, h * w

@@ -10,7 +10,7 @@ import torch
 from lfsr_amd import capi
 from lfsr_amd.synth import synth_input, synth_state_dict
 from oracle import lfsr_torch_port as P
-from tests.helpers import GOLDEN, model_case
+from tests.helpers import GOLDEN, lft_forced_fp64_grads, model_case
 
 pytestmark = pytest.mark.gpu
 TAGS = ("a5h8s4", "a3h6w8s2")
@@ -61,39 +61,9 @@ def port_grads(sd, x, label, A, s, dtype=torch.float64):
 
 
 def forced_fp64_grads(rt, xg, sd, x, label, A, s):
-    """fp64 autograd of the port's graph with every ReLU / LeakyReLU decision taken from what the HIP path computed (lfsr_lft_train_saved,
-    read after the backward), and the number of those decisions that differ from fp64's own.  A pre-activation within fp32 rounding of 0
-    is a legitimate tie whose two sides have different gradients downstream (one flipped tail pixel moves the gradient of a small case by
-    ~1e-3); this graph makes the same choices.  Call it with the fp64_port fixture active."""
-    F = torch.nn.functional
-    B, _, Hh, Ww = x.shape
-    h, w, AA = Hh // A, Ww // A, A * A
-
-    def vcl(t, c):         # VCL rows -> the port's (B, c, A^2, h, w)
-        return t.reshape(B, AA, h, w, c).permute(0, 4, 1, 2, 3)
-    masks = [vcl(rt.train_saved(xg, 5, 0), 64), vcl(rt.train_saved(xg, 5, 1), 64), vcl(rt.train_saved(xg, 8, 0), 64)]
-    for b in range(4):
-        masks.append(rt.train_saved(xg, 6, b).reshape(B, AA, h * w, 128).permute(1, 0, 2, 3).reshape(AA, B * h * w, 128))   # (a, b h w, 128)
-        masks.append(rt.train_saved(xg, 7, b).reshape(B * AA, h * w, 256).permute(1, 0, 2))                             # (h w, b a, 256)
-    masks.append(rt.train_saved(xg, 9, 0).reshape(B, A * h * s, A * w * s, 64).permute(0, 3, 1, 2))
-    masks = [(m > 0).cpu() for m in masks]
-    flips, calls = 0, []
-    relu0, lrelu0 = F.relu, F.leaky_relu
-
-    def forced(z, slope):
-        nonlocal flips
-        m = masks[len(calls)]
-        calls.append(1)
-        flips += int(((z > 0) != m).sum())
-        return torch.where(m, z, z * slope)
-    F.relu = lambda z, inplace=False: forced(z, 0.0)
-    F.leaky_relu = lambda z, negative_slope=0.01, inplace=False: forced(z, negative_slope)
-    try:
-        _, g = port_grads(sd, x, label, A, s)
-    finally:
-        F.relu, F.leaky_relu = relu0, lrelu0
-    assert len(calls) == len(masks)
-    return g, flips
+    """fp64 autograd of the reference graph with every ReLU / LeakyReLU decision taken from what the HIP path computed, and the number of
+    those decisions that differ from fp64's own: tests/helpers.py::lft_forced_fp64_grads"""
+    return lft_forced_fp64_grads(rt, xg, sd, x, label, A, s)
 
 
 def check_against_port(net, bucket, ref):
@@ -166,7 +136,7 @@ def test_baseline_geometry_against_fp64(fp64_port):
     med0, mx0 = check_against_port(net, bucket, ref)
     print(f"BASELINE 5x5 32x32 x4: rel-L2 vs fp64 with the HIP decisions median {med:.2e} max {mx:.2e}; vs fp64 median {med0:.2e} max {mx0:.2e} "
           f"({flips} decisions differ)")
-    assert med <= 5e-5 and mx <= 1e-2
+    assert med <= 5e-5 and mx < 1e-4      # per parameter, as tests/test_gpu_lft_geometries.py holds at this patch with B = 8 (worst seen there: 1.1e-06)
     assert mx0 <= 1e-2
 
 
