@@ -392,7 +392,6 @@ int lfsr_bwd_gemm(const LfsrGemm& g, hipStream_t st) {
   BG(IN_CHK_V, OUT_SAME, 32, 1)     //                  vertical
   BG(IN_LINE_H, OUT_EPIH, 32, 2)    // EPIConv.0 dgrad, horizontal (32 -> A x 64), accumulates into dX
   BG(IN_LINE_V, OUT_EPIV, 32, 2)    //                  vertical
-  BG(IN_CONV3, OUT_SAME, 64, 2)     // 3x3 dgrad fallback
 #undef BG
   return LFSR_E_ARG;
 }
@@ -401,35 +400,24 @@ int lfsr_bwd_gemm(const LfsrGemm& g, hipStream_t st) {
 // instead of a separate read-modify-write pass over dx.  LFSR_E_ARG = not covered (the caller adds r2 itself).
 int lfsr_conv3x3_bwd_data_r2(const float* dy, int dy_stride, const float* wT_packed, float* dx, const float* r1, const float* r2, int n_img, int h, int w, hipStream_t st) {
   if ((dy_stride & 3) || !r1 || !r2) return LFSR_E_ARG;
-  const char* sel = lfsr_conv3_dgrad_sel();
-  if (sel) return LFSR_E_ARG;      // (lab selections of another 3x3 form: the plain path)
+  if (lfsr_conv3_dgrad_sel() != LFSR_C3_DEFAULT) return LFSR_E_ARG;      // (lab selections of another 3x3 form: the plain path)
   LfsrOpTimer op_t("conv3x3_dgrad", n_img, h * w, st);
-  return lfsr_conv3x3_wino4_launch(dy, dy_stride, 0, wT_packed + LFSR_CONV3_DIRECT_FLOATS + LFSR_CONV3_WINO2_FLOATS, dx, 64, 0, r1, 64, 0, r2, 64, 0, nullptr, 0, 0, 1.0f,
-                                   n_img, h, w, 1.0f, st);
+  LfsrConv3 c{};
+  c.x = dy; c.x_stride = dy_stride; c.w_packed = wT_packed; c.y = dx; c.y_stride = 64; c.r1 = r1; c.r1_stride = 64; c.r2 = r2; c.r2_stride = 64;
+  c.mk_slope = 1.0f; c.n_img = n_img; c.h = h; c.w = w; c.slope = 1.0f;
+  return lfsr_conv3x3_run(c, true, st);
 }
 
+// dx = conv^T(dy) [* LeakyReLU'(mk)] [+ r1]: the 3x3 conv's kernels (conv3x3.cpp) on the transposed, tap-flipped pack
 int lfsr_conv3x3_bwd_data(const float* dy, int dy_stride, int dy_choff, const float* wT_packed, float* dx, int dx_stride, int dx_choff,
                           const float* r1, int r1_stride, int r1_choff, const float* mk, int mk_stride, int mk_choff, float mk_slope,
                           int n_img, int h, int w, hipStream_t st) {
   LfsrOpTimer op_t("conv3x3_dgrad", n_img, h * w, st);
-  const bool al = !((dy_stride | dy_choff | dx_stride | dx_choff) & 3) && (!r1 || !((r1_stride | r1_choff) & 3)) && (!mk || !((mk_stride | mk_choff) & 3));
-  {
-    const char* sel = lfsr_conv3_dgrad_sel();
-    if (al && !(sel && (sel[0] == 'h' || sel[0] == 'g'))) {
-      const int rc = lfsr_conv3x3_wino_launch(dy, dy_stride, dy_choff, wT_packed + LFSR_CONV3_DIRECT_FLOATS, wT_packed, dx, dx_stride, dx_choff, r1, r1_stride, r1_choff,
-                                              nullptr, 0, 0, mk, mk_stride, mk_choff, mk_slope, n_img, h, w, 1.0f, sel, st);
-      if (rc != LFSR_E_ARG) return rc;   // (E_ARG: a geometry the Winograd launchers do not cover -> the direct kernel)
-    }
-  }
-  if (al)
-    return lfsr_conv3x3_halo_launch(dy, dy_stride, dy_choff, wT_packed, dx, dx_stride, dx_choff, r1, r1_stride, r1_choff, nullptr, 0, 0,
-                                    mk, mk_stride, mk_choff, mk_slope, n_img, h, w, 1.0f, st);
-  LfsrGemm g{};
-  g.in_mode = LFSR_IN_CONV3; g.out_mode = LFSR_OUT_SAME; g.cin = 64;
-  g.X = dy; g.x_stride = dy_stride; g.x_choff = dy_choff; g.Wp = wT_packed; g.Y = dx; g.y_stride = dx_stride; g.y_choff = dx_choff;
-  g.R1 = r1; g.r1_stride = r1_stride; g.r1_choff = r1_choff; g.Mk = mk; g.mk_stride = mk_stride; g.mk_choff = mk_choff; g.mk_slope = mk_slope;
-  g.M = n_img * h * w; g.N = 64; g.A = 1; g.h = h; g.w = w; g.ntaps = 9; g.CH = 64;
-  return lfsr_bwd_gemm(g, st);
+  LfsrConv3 c{};
+  c.x = dy; c.x_stride = dy_stride; c.x_choff = dy_choff; c.w_packed = wT_packed; c.y = dx; c.y_stride = dx_stride; c.y_choff = dx_choff;
+  c.r1 = r1; c.r1_stride = r1_stride; c.r1_choff = r1_choff; c.mk = mk; c.mk_stride = mk_stride; c.mk_choff = mk_choff; c.mk_slope = mk_slope;
+  c.n_img = n_img; c.h = h; c.w = w; c.slope = 1.0f;
+  return lfsr_conv3x3_run(c, true, st);
 }
 
 int lfsr_head_bwd_data(const float* dout, const float* wf, float* df, float* g16, int B, int A, int h, int w, int s, hipStream_t st) {

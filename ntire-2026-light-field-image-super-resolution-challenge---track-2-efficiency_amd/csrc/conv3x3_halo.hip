@@ -278,11 +278,17 @@ __global__ __launch_bounds__(512) void k_conv3x3_halo(ConvArgs p) {
 
 }  // namespace
 
-// internal entry used by lfsr_conv3x3_fwd (gemm_gather.hip)
-int lfsr_conv3x3_halo_launch(const float* x, int x_stride, int x_choff, const float* w_packed, float* y, int y_stride, int y_choff,
-                             const float* r1, int r1_stride, int r1_choff, const float* r2, int r2_stride, int r2_choff,
-                             const float* mk, int mk_stride, int mk_choff, float mk_slope,
-                             int n_img, int h, int w, float slope, hipStream_t st) {
+static ConvArgs conv_args(const LfsrConv3& c) {
+  ConvArgs p{};
+  p.X = c.x; p.x_stride = c.x_stride; p.x_choff = c.x_choff; p.Wp = c.w_direct();
+  p.Y = c.y; p.y_stride = c.y_stride; p.y_choff = c.y_choff;
+  p.R1 = c.r1; p.r1_stride = c.r1_stride; p.r1_choff = c.r1_choff; p.R2 = c.r2; p.r2_stride = c.r2_stride; p.r2_choff = c.r2_choff;
+  p.Mk = c.mk; p.mk_stride = c.mk_stride; p.mk_choff = c.mk_choff; p.mk_slope = c.mk_slope;
+  p.n_img = c.n_img; p.H = c.h; p.W = c.w; p.tiles_y = (c.h + TR - 1) / TR; p.tiles_x = (c.w + TC - 1) / TC; p.slope = c.slope;
+  return p;
+}
+
+int lfsr_conv3x3_halo_launch(const LfsrConv3& c, hipStream_t st) {
   static std::atomic<bool> attr_set[64];   // per device: the >64 KB dynamic-LDS opt-in is a per-device function attribute
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
@@ -294,16 +300,11 @@ int lfsr_conv3x3_halo_launch(const float* x, int x_stride, int x_choff, const fl
     if (e != hipSuccess) return LFSR_HIP_ERR(e);
     attr_set[dev] = true;
   }
-  ConvArgs p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wp = w_packed;
-  p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff;
-  p.R1 = r1; p.r1_stride = r1_stride; p.r1_choff = r1_choff; p.R2 = r2; p.r2_stride = r2_stride; p.r2_choff = r2_choff;
-  p.Mk = mk; p.mk_stride = mk_stride; p.mk_choff = mk_choff; p.mk_slope = mk_slope;
-  p.n_img = n_img; p.H = h; p.W = w; p.tiles_y = (h + TR - 1) / TR; p.tiles_x = (w + TC - 1) / TC; p.slope = slope;
+  ConvArgs p = conv_args(c);
 #ifdef LFSR_CONV_DIAG
   p.dbg = g_lfsr_diag_buf;
 #endif
-  long long nblk = (long long)n_img * p.tiles_y * p.tiles_x;
+  long long nblk = (long long)c.n_img * p.tiles_y * p.tiles_x;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return LFSR_E_ARG;
   int ncu = 256;
   {
@@ -322,13 +323,13 @@ int lfsr_conv3x3_halo_launch(const float* x, int x_stride, int x_choff, const fl
   if (body > 0) {
     p.tile_begin = 0; p.tile_count = body;
     unsigned grid = (unsigned)(body < ncu ? body : ncu);
-    if (mk) hipLaunchKernelGGL((k_conv3x3_halo<true, false>), dim3(grid), dim3(512), SMEM_BYTES, st, p);
+    if (c.mk) hipLaunchKernelGGL((k_conv3x3_halo<true, false>), dim3(grid), dim3(512), SMEM_BYTES, st, p);
     else hipLaunchKernelGGL((k_conv3x3_halo<false, false>), dim3(grid), dim3(512), SMEM_BYTES, st, p);
     LFSR_CHECK_LAUNCH();
   }
   if (tail > 0) {
     p.tile_begin = body; p.tile_count = tail;
-    if (mk) hipLaunchKernelGGL((k_conv3x3_halo<true, true>), dim3(2 * tail), dim3(512), SMEM_BYTES, st, p);
+    if (c.mk) hipLaunchKernelGGL((k_conv3x3_halo<true, true>), dim3(2 * tail), dim3(512), SMEM_BYTES, st, p);
     else hipLaunchKernelGGL((k_conv3x3_halo<false, true>), dim3(2 * tail), dim3(512), SMEM_BYTES, st, p);
     LFSR_CHECK_LAUNCH();
   }
@@ -336,10 +337,7 @@ int lfsr_conv3x3_halo_launch(const float* x, int x_stride, int x_choff, const fl
 }
 
 // channel-split launch over tiles [tile_begin, tile_begin + tile_count) only: the tail of the Winograd kernel (conv3x3_wino.hip)
-int lfsr_conv3x3_halo_tail_launch(const float* x, int x_stride, int x_choff, const float* w_packed, float* y, int y_stride, int y_choff,
-                                  const float* r1, int r1_stride, int r1_choff, const float* r2, int r2_stride, int r2_choff,
-                                  const float* mk, int mk_stride, int mk_choff, float mk_slope,
-                                  int n_img, int h, int w, float slope, int tile_begin, int tile_count, hipStream_t st) {
+int lfsr_conv3x3_halo_tail_launch(const LfsrConv3& c, int tile_begin, int tile_count, hipStream_t st) {
   static std::atomic<bool> attr_set[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
@@ -350,14 +348,9 @@ int lfsr_conv3x3_halo_tail_launch(const float* x, int x_stride, int x_choff, con
     attr_set[dev] = true;
   }
   if (tile_count <= 0) return LFSR_OK;
-  ConvArgs p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wp = w_packed;
-  p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff;
-  p.R1 = r1; p.r1_stride = r1_stride; p.r1_choff = r1_choff; p.R2 = r2; p.r2_stride = r2_stride; p.r2_choff = r2_choff;
-  p.Mk = mk; p.mk_stride = mk_stride; p.mk_choff = mk_choff; p.mk_slope = mk_slope;
-  p.n_img = n_img; p.H = h; p.W = w; p.tiles_y = (h + TR - 1) / TR; p.tiles_x = (w + TC - 1) / TC; p.slope = slope;
+  ConvArgs p = conv_args(c);
   p.tile_begin = tile_begin; p.tile_count = tile_count;
-  if (mk) hipLaunchKernelGGL((k_conv3x3_halo<true, true>), dim3(2 * tile_count), dim3(512), SMEM_BYTES, st, p);
+  if (c.mk) hipLaunchKernelGGL((k_conv3x3_halo<true, true>), dim3(2 * tile_count), dim3(512), SMEM_BYTES, st, p);
   else hipLaunchKernelGGL((k_conv3x3_halo<false, true>), dim3(2 * tile_count), dim3(512), SMEM_BYTES, st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;

@@ -464,21 +464,6 @@ __global__ __launch_bounds__(256) void k_pack_wino(const float* __restrict__ dir
 
 }  // namespace
 
-static int conv3_sel_mask(const char* sel) {
-  if (!sel) return LFSR_W_WINO4;
-  if (sel[0] == 'h' || sel[0] == 'g') return 0;                              // direct kernels: the direct pack only
-  if (sel[0] == 'w' && sel[1] == 'i' && sel[2] == 'n' && sel[3] == 'o') {
-    if (sel[4] == '2') return LFSR_W_WINO2;
-  }
-  return LFSR_W_WINO4;
-}
-
-// LFSR_CONV3X3 selects the forward kernel; LFSR_DGRAD3 (same vocabulary) the data-gradient kernel, which otherwise follows LFSR_CONV3X3
-const char* lfsr_conv3_fwd_sel() { return lfsr_sel("LFSR_CONV3X3"); }
-const char* lfsr_conv3_dgrad_sel() { const char* d = lfsr_sel("LFSR_DGRAD3"); return d ? d : lfsr_sel("LFSR_CONV3X3"); }
-
-int lfsr_conv3_variant_mask() { return conv3_sel_mask(lfsr_conv3_fwd_sel()) | conv3_sel_mask(lfsr_conv3_dgrad_sel()); }
-
 int lfsr_pack_wino_m(const float* direct_packed, float* out, int mask, hipStream_t st) {
   if (!direct_packed || !out) return LFSR_E_ARG;
   int rc = LFSR_OK;
@@ -492,23 +477,8 @@ int lfsr_pack_wino_m(const float* direct_packed, float* out, int mask, hipStream
 
 int lfsr_pack_wino(const float* direct_packed, float* out, hipStream_t st) { return lfsr_pack_wino_m(direct_packed, out, LFSR_W_ALL, st); }
 
-// w_wino: the Winograd-domain pack (lfsr_pack_wino); w_direct: the [9][64][64] pack, used by the channel-split tail launch.
-int lfsr_conv3x3_wino_launch(const float* x, int x_stride, int x_choff, const float* w_wino, const float* w_direct, float* y, int y_stride, int y_choff,
-                             const float* r1, int r1_stride, int r1_choff, const float* r2, int r2_stride, int r2_choff,
-                             const float* mk, int mk_stride, int mk_choff, float mk_slope,
-                             int n_img, int h, int w, float slope, const char* sel, hipStream_t st) {
-  {   // F(4x4,3x3), the default (conv3x3_wino4.hip);
-      // LFSR_CONV3X3=wino2 keeps this file's F(2x2,3x3) kernel (A/B runs), as do operands the F(4x4) launchers do not cover
-    const bool is_w = sel && sel[0] == 'w' && sel[1] == 'i' && sel[2] == 'n' && sel[3] == 'o';
-    if (!(is_w && sel[4] == '2')) {
-      const int rc = lfsr_conv3x3_wino4_launch(x, x_stride, x_choff, w_wino + LFSR_CONV3_WINO2_FLOATS, y, y_stride, y_choff, r1, r1_stride, r1_choff,
-                                               r2, r2_stride, r2_choff, mk, mk_stride, mk_choff, mk_slope, n_img, h, w, slope, st);
-      if (rc != LFSR_E_ARG) return rc;
-    }
-  }
-  // this file's F(2x2) kernel runs only when LFSR_CONV3X3 selects it (the runtimes pack only the selected copies): operands the F(4x4)
-  // launchers do not cover (1 GiB and more) go to the callers' direct 9-tap kernel
-  if (!(conv3_sel_mask(sel) & LFSR_W_WINO2)) return LFSR_E_ARG;
+// The F(2x2) kernel on the F(2x2) part of the pack; LFSR_E_ARG = geometry not covered (operand spans of 2 GiB and more)
+int lfsr_conv3x3_wino2_launch(const LfsrConv3& c, hipStream_t st) {
   static std::atomic<bool> attr_set[64];
   static std::atomic<int> cus[64];
   int dev = 0;
@@ -523,49 +493,41 @@ int lfsr_conv3x3_wino_launch(const float* x, int x_stride, int x_choff, const fl
   }
   const int ncu = cus[dev];
   WinoArgs p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wu = w_wino;
-  p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff;
-  p.R1 = r1; p.r1_stride = r1_stride; p.r1_choff = r1_choff; p.R2 = r2; p.r2_stride = r2_stride; p.r2_choff = r2_choff;
-  p.Mk = mk; p.mk_stride = mk_stride; p.mk_choff = mk_choff; p.mk_slope = mk_slope;
-  p.n_img = n_img; p.H = h; p.W = w; p.tiles_y = (h + TR - 1) / TR; p.tiles_x = (w + TC - 1) / TC; p.slope = slope;
-  const long long nblk = (long long)n_img * p.tiles_y * p.tiles_x;
+  p.X = c.x; p.x_stride = c.x_stride; p.x_choff = c.x_choff; p.Wu = c.w_wino2();
+  p.Y = c.y; p.y_stride = c.y_stride; p.y_choff = c.y_choff;
+  p.R1 = c.r1; p.r1_stride = c.r1_stride; p.r1_choff = c.r1_choff; p.R2 = c.r2; p.r2_stride = c.r2_stride; p.r2_choff = c.r2_choff;
+  p.Mk = c.mk; p.mk_stride = c.mk_stride; p.mk_choff = c.mk_choff; p.mk_slope = c.mk_slope;
+  p.n_img = c.n_img; p.H = c.h; p.W = c.w; p.tiles_y = (c.h + TR - 1) / TR; p.tiles_x = (c.w + TC - 1) / TC; p.slope = c.slope;
+  const long long nblk = (long long)c.n_img * p.tiles_y * p.tiles_x;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return LFSR_E_ARG;
-  // every operand is addressed through a buffer descriptor with 32-bit byte offsets: spans of 2 GiB and more go to the direct kernel
+  // every operand is addressed through a buffer descriptor with 32-bit byte offsets
+  const long long npix4 = (long long)c.n_img * c.h * c.w * 4;
   {
-    int ms = x_stride > y_stride ? x_stride : y_stride;
-    if (r1 && r1_stride > ms) ms = r1_stride;
-    if (r2 && r2_stride > ms) ms = r2_stride;
-    if (mk && mk_stride > ms) ms = mk_stride;
-    if ((long long)n_img * h * w * ms * 4 >= (1LL << 31) || (long long)h * w >= (1 << 24)) {
-      if (!w_direct) return LFSR_E_ARG;
-      return lfsr_conv3x3_halo_launch(x, x_stride, x_choff, w_direct, y, y_stride, y_choff, r1, r1_stride, r1_choff, r2, r2_stride, r2_choff,
-                                      mk, mk_stride, mk_choff, mk_slope, n_img, h, w, slope, st);
-    }
+    int ms = c.x_stride > c.y_stride ? c.x_stride : c.y_stride;
+    if (c.r1 && c.r1_stride > ms) ms = c.r1_stride;
+    if (c.r2 && c.r2_stride > ms) ms = c.r2_stride;
+    if (c.mk && c.mk_stride > ms) ms = c.mk_stride;
+    if (npix4 * ms >= (1LL << 31) || (long long)c.h * c.w >= (1 << 24)) return LFSR_E_ARG;
   }
   // tiles beyond the last full round (L = ntiles % CUs) go to a channel-split tail launch, two blocks per tile, when that halves
   // the tail (2L <= CUs); LFSR_CONV_TAIL=halo runs the tail on the direct 9-tap kernel instead (A/B)
   int tail = (int)(nblk % ncu);
   if (nblk < ncu || 2 * tail > ncu || lfsr_sel("LFSR_CONV_NOTAIL")) tail = 0;
   const char* tsel = lfsr_sel("LFSR_CONV_TAIL");
-  const bool tail_direct = tsel && tsel[0] == 'h' && w_direct;
+  const bool tail_direct = tsel && tsel[0] == 'h';
   const int body = (int)nblk - tail;
   p.ntiles = body;
   p.nbody = body < ncu ? body : ncu;
   const int wino_tail = tail_direct ? 0 : tail;
-  {
-    const long long npix4 = (long long)n_img * h * w * 4;   // (spans < 2 GiB: checked above)
-    p.x_bytes = (int)(npix4 * x_stride); p.y_bytes = (int)(npix4 * y_stride);
-    p.r1_bytes = r1 ? (int)(npix4 * r1_stride) : 0; p.r2_bytes = r2 ? (int)(npix4 * r2_stride) : 0; p.mk_bytes = mk ? (int)(npix4 * mk_stride) : 0;
-  }
+  p.x_bytes = (int)(npix4 * c.x_stride); p.y_bytes = (int)(npix4 * c.y_stride);
+  p.r1_bytes = c.r1 ? (int)(npix4 * c.r1_stride) : 0; p.r2_bytes = c.r2 ? (int)(npix4 * c.r2_stride) : 0; p.mk_bytes = c.mk ? (int)(npix4 * c.mk_stride) : 0;
 #ifdef LFSR_CONV_DIAG
   p.dbg = g_lfsr_diag_buf;
 #endif
   const unsigned grid = (unsigned)(p.nbody + 2 * wino_tail);
-  if (mk) hipLaunchKernelGGL((k_conv3x3_wino<true>), dim3(grid), dim3(512), SMEM_BYTES, st, p);
+  if (c.mk) hipLaunchKernelGGL((k_conv3x3_wino<true>), dim3(grid), dim3(512), SMEM_BYTES, st, p);
   else hipLaunchKernelGGL((k_conv3x3_wino<false>), dim3(grid), dim3(512), SMEM_BYTES, st, p);
   LFSR_CHECK_LAUNCH();
-  if (tail > 0 && tail_direct)
-    return lfsr_conv3x3_halo_tail_launch(x, x_stride, x_choff, w_direct, y, y_stride, y_choff, r1, r1_stride, r1_choff, r2, r2_stride, r2_choff,
-                                         mk, mk_stride, mk_choff, mk_slope, n_img, h, w, slope, body, tail, st);
+  if (tail > 0 && tail_direct) return lfsr_conv3x3_halo_tail_launch(c, body, tail, st);
   return LFSR_OK;
 }

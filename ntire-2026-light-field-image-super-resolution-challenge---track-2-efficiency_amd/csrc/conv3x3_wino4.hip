@@ -582,6 +582,7 @@ __global__ __launch_bounds__(512) void k_conv3x3_wino4(Wino4Args p) {
               if (g == W4_HAG) BARRIER_NOWAIT();       // (A)
             }
           }
+          static_assert(W4_XB == 1, "the half tile's consumers skip barrier (B) behind the last chunk as the producers do only with W4_XB: at W4_XB = 0 the counts differ and the block hangs");
           if (c < 3) LDS_BARRIER();                    // (B)
         }
         // first pass of At M A (over xi) for the wave's three nu: T[a][n] -> acc[3 a + n]
@@ -726,11 +727,8 @@ int lfsr_pack_wino4(const float* direct_packed, float* out, hipStream_t st) {
   return LFSR_OK;
 }
 
-// LFSR_E_ARG = geometry not covered (operands of 1 GiB and more): the caller falls back to the F(2x2,3x3) kernel
-int lfsr_conv3x3_wino4_launch(const float* x, int x_stride, int x_choff, const float* w_wino4, float* y, int y_stride, int y_choff,
-                              const float* r1, int r1_stride, int r1_choff, const float* r2, int r2_stride, int r2_choff,
-                              const float* mk, int mk_stride, int mk_choff, float mk_slope,
-                              int n_img, int h, int w, float slope, hipStream_t st) {
+// The F(4x4) kernel on the F(4x4) part of the pack; LFSR_E_ARG = geometry not covered (operand spans of 1 GiB and more): the dispatcher (conv3x3.cpp) goes on down its chain
+int lfsr_conv3x3_wino4_launch(const LfsrConv3& c, hipStream_t st) {
   static std::atomic<bool> attr_set[64];
   static std::atomic<int> cus[64];
   int dev = 0;
@@ -749,25 +747,24 @@ int lfsr_conv3x3_wino4_launch(const float* x, int x_stride, int x_choff, const f
     cus[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
     attr_set[dev] = true;
   }
-  int ms = x_stride > y_stride ? x_stride : y_stride;
-  if (r1 && r1_stride > ms) ms = r1_stride;
-  if (r2 && r2_stride > ms) ms = r2_stride;
-  if (mk && mk_stride > ms) ms = mk_stride;
-  if ((long long)n_img * h * w * ms * 4 >= (1LL << 30)) return LFSR_E_ARG;
+  const long long npix4 = (long long)c.n_img * c.h * c.w * 4;
+  int ms = c.x_stride > c.y_stride ? c.x_stride : c.y_stride;
+  if (c.r1 && c.r1_stride > ms) ms = c.r1_stride;
+  if (c.r2 && c.r2_stride > ms) ms = c.r2_stride;
+  if (c.mk && c.mk_stride > ms) ms = c.mk_stride;
+  if (npix4 * ms >= (1LL << 30)) return LFSR_E_ARG;
   Wino4Args p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.x_bytes = (int)((long long)n_img * h * w * x_stride * 4);
-  p.Wu = w_wino4;
-  p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff;
-  p.R1 = r1; p.r1_stride = r1_stride; p.r1_choff = r1_choff; p.R2 = r2; p.r2_stride = r2_stride; p.r2_choff = r2_choff;
-  p.Mk = mk; p.mk_stride = mk_stride; p.mk_choff = mk_choff; p.mk_slope = mk_slope;
-  const long long npix4 = (long long)n_img * h * w * 4;
-  p.y_bytes = (int)(npix4 * y_stride); p.r1_bytes = r1 ? (int)(npix4 * r1_stride) : 0; p.r2_bytes = r2 ? (int)(npix4 * r2_stride) : 0;
-  p.mk_bytes = mk ? (int)(npix4 * mk_stride) : 0;
+  p.X = c.x; p.x_stride = c.x_stride; p.x_choff = c.x_choff; p.x_bytes = (int)(npix4 * c.x_stride);
+  p.Wu = c.w_wino4();
+  p.Y = c.y; p.y_stride = c.y_stride; p.y_choff = c.y_choff; p.y_bytes = (int)(npix4 * c.y_stride);
+  p.R1 = c.r1; p.r1_stride = c.r1_stride; p.r1_choff = c.r1_choff; p.r1_bytes = c.r1 ? (int)(npix4 * c.r1_stride) : 0;
+  p.R2 = c.r2; p.r2_stride = c.r2_stride; p.r2_choff = c.r2_choff; p.r2_bytes = c.r2 ? (int)(npix4 * c.r2_stride) : 0;
+  p.Mk = c.mk; p.mk_stride = c.mk_stride; p.mk_choff = c.mk_choff; p.mk_slope = c.mk_slope; p.mk_bytes = c.mk ? (int)(npix4 * c.mk_stride) : 0;
 #ifdef LFSR_CONV_DIAG
   p.dbg = g_lfsr_diag_buf;
 #endif
-  p.n_img = n_img; p.H = h; p.W = w; p.tiles_y = (h + 7) / 8; p.tiles_x = (w + 31) / 32; p.slope = slope;
-  const long long nt = (long long)n_img * p.tiles_y * p.tiles_x;
+  p.n_img = c.n_img; p.H = c.h; p.W = c.w; p.tiles_y = (c.h + 7) / 8; p.tiles_x = (c.w + 31) / 32; p.slope = c.slope;
+  const long long nt = (long long)c.n_img * p.tiles_y * p.tiles_x;
   if (nt <= 0 || nt > 0x7fffffffLL) return LFSR_E_ARG;
   p.ntiles = (int)nt;
   const int slots = cus[dev];
@@ -778,16 +775,16 @@ int lfsr_conv3x3_wino4_launch(const float* x, int x_stride, int x_choff, const f
     const long long fpb = nt / slots, rem = nt % slots;
     if (rem > 0 && 2 * rem <= slots && !lfsr_sel("LFSR_CONV_NOHALF")) { p.full_per_block = (int)fpb; p.nhalf = (int)rem; grid = (unsigned)(fpb > 0 ? slots : 2 * rem); }
   }
-  if (!mk && !r1 && r2) { p.R1 = r2; p.r1_stride = r2_stride; p.r1_choff = r2_choff; p.r1_bytes = p.r2_bytes; p.R2 = nullptr; p.r2_bytes = 0; }   // a lone residual is the first operand
-  const int act = slope == 1.f ? 0 : (slope >= 0.f && slope < 1.f ? 1 : 2);
-  const bool aligned = h % 8 == 0 && w % 32 == 0;
+  if (!c.mk && !c.r1 && c.r2) { p.R1 = c.r2; p.r1_stride = c.r2_stride; p.r1_choff = c.r2_choff; p.r1_bytes = p.r2_bytes; p.R2 = nullptr; p.r2_bytes = 0; }   // a lone residual is the first operand
+  const int act = c.slope == 1.f ? 0 : (c.slope >= 0.f && c.slope < 1.f ? 1 : 2);
+  const bool aligned = c.h % 8 == 0 && c.w % 32 == 0;
 #define W4_GO2(M, E, L, G) do { \
     if (act == 0) hipLaunchKernelGGL((k_conv3x3_wino4<M, E, L, 0, G>), dim3(grid), dim3(512), SMEM_BYTES, st, p); \
     else if (act == 1) hipLaunchKernelGGL((k_conv3x3_wino4<M, E, L, 1, G>), dim3(grid), dim3(512), SMEM_BYTES, st, p); \
     else hipLaunchKernelGGL((k_conv3x3_wino4<M, E, L, 2, G>), dim3(grid), dim3(512), SMEM_BYTES, st, p); } while (0)
 #define W4_GO(M, E, L) do { if (aligned) W4_GO2(M, E, L, true); else W4_GO2(M, E, L, false); } while (0)
-  if (mk && p.R1) W4_GO(true, true, true);
-  else if (mk) W4_GO(true, true, false);
+  if (c.mk && p.R1) W4_GO(true, true, true);
+  else if (c.mk) W4_GO(true, true, false);
   else if (p.R1 && p.R2) W4_GO(false, true, true);
   else if (p.R1) W4_GO(false, true, false);
   else W4_GO(false, false, false);

@@ -147,7 +147,7 @@ int lfsr_distgssr_load_param(lfsr_distgssr* c, const char* key, const float* dat
     // record the packs; lfsr_distgssr_finalize launches them, one kernel per kind (3x3 weights with another kernel selection keep the eager path below)
     auto pad32 = [](int v) { return (v + 31) / 32 * 32; };
     const bool c3 = sl->O == 64 && sl->C == 64 && sl->T == 9 && sl->perm == 0;
-    if (c3) c->d_c3.push_back(LfsrPackDesc{data, dst, dst + LFSR_CONV3_DIRECT_FLOATS + LFSR_CONV3_WINO2_FLOATS, 0, 64, 64, 9, 64, 0, 0, 0});
+    if (c3) c->d_c3.push_back(LfsrPackDesc{data, dst, dst + LFSR_CONV3_WINO4_OFF, 0, 64, 64, 9, 64, 0, 0, 0});
     else {
       c->d_gen.push_back(LfsrPackDesc{data, dst, nullptr, 0, sl->O, sl->C, sl->T, pad32(sl->O), sl->perm, sl->ch, 0});
       if (sl->O == 32 && sl->C == 64 && sl->T == 25 && sl->perm == 0) {
@@ -156,7 +156,7 @@ int lfsr_distgssr_load_param(lfsr_distgssr* c, const char* key, const float* dat
       }
       if (sl->O == 160 && sl->C == 32 && sl->T == 1 && sl->perm == 0) c->d_epib.push_back(LfsrPackDesc{dst, dst + 160 * 32, nullptr, 1, 160, 32, 1, 160, 0, 0, 0});
     }
-    if (kindT == 1 && c3) c->d_c3.push_back(LfsrPackDesc{data, tdst, tdst + LFSR_CONV3_DIRECT_FLOATS + LFSR_CONV3_WINO2_FLOATS, 0, 64, 64, 9, 64, 0, 0, 1});
+    if (kindT == 1 && c3) c->d_c3.push_back(LfsrPackDesc{data, tdst, tdst + LFSR_CONV3_WINO4_OFF, 0, 64, 64, 9, 64, 0, 0, 1});
     else if (kindT == 1) c->d_gen.push_back(LfsrPackDesc{data, tdst, nullptr, 1, sl->O, sl->C, sl->T, pad32(sl->C), 0, 0, 1});
     if (kindT == 2) c->d_gen.push_back(LfsrPackDesc{data, tdst, nullptr, 1, sl->O, sl->C, sl->T, pad32(sl->C), 0, 0, 0});
     if (kindT == 3) c->d_gen.push_back(LfsrPackDesc{data, tdst, nullptr, 2, sl->O, sl->C, 1, pad32(sl->C), 1, 16, 0});
@@ -514,8 +514,7 @@ static int distgssr_backward_impl(lfsr_distgssr* c, const float* x, const float*
     if (!r) r = lfsr_wgrad_reduce(t.P[0], lfsr_wgrad_conv3_blocks(nimg, h, w), nullptr, 0, G(key), 64, 64, 9, 0, 0, 0, 0, 0, st);
     return r;
   };
-  auto dgrad3 = [&](const float* dy, int dy_stride, const std::string& key, float* dx, const float* r1, const float* r2_unused, const float* mk, int mk_stride) -> int {
-    (void)r2_unused;
+  auto dgrad3 = [&](const float* dy, int dy_stride, const std::string& key, float* dx, const float* r1, const float* mk, int mk_stride) -> int {
     return lfsr_conv3x3_bwd_data(dy, dy_stride, 0, c->wT(key), dx, 64, 0, r1, 64, 0, mk, mk_stride, 0, L, nimg, h, w, st);
   };
   auto pick = [&](const float* a, const float* b, const float* d) -> float* {
@@ -542,7 +541,7 @@ static int distgssr_backward_impl(lfsr_distgssr* c, const float* x, const float*
   const float* last = t.GOUT[c->G - 1];
   LFSR_RC(wgrad3("disentg.conv.weight", last, dD, 64));
   float* gcur = pick(dD, nullptr, nullptr);
-  LFSR_RC(dgrad3(dD, 64, "disentg.conv.weight", gcur, nullptr, nullptr, nullptr, 0));
+  LFSR_RC(dgrad3(dD, 64, "disentg.conv.weight", gcur, nullptr, nullptr, 0));
   // ---- groups, reversed ----------------------------------------------------------------------------------------
   for (int g = c->G - 1; g >= 0; --g) {
     float* dG = gcur;   // gradient at the group's output; also flows through the group skip to its input
@@ -551,7 +550,7 @@ static int distgssr_backward_impl(lfsr_distgssr* c, const float* x, const float*
     std::string gk = "disentg.Group." + std::to_string(g) + ".conv.weight";
     LFSR_RC(wgrad3(gk, blk_last, dG, 64));
     float* gy = pick(dD, dG, nullptr);
-    LFSR_RC(dgrad3(dG, 64, gk, gy, nullptr, nullptr, nullptr, 0));
+    LFSR_RC(dgrad3(dG, 64, gk, gy, nullptr, nullptr, 0));
     for (int b = c->NB - 1; b >= 0; --b) {
       const int i = g * c->NB + b;
       std::string p = "disentg.Group." + std::to_string(g) + ".Block." + std::to_string(b) + ".";
@@ -559,7 +558,7 @@ static int distgssr_backward_impl(lfsr_distgssr* c, const float* x, const float*
       float* gx = pick(dD, dG, gy);
       // fuse.2 : OUT = conv(FZ) + Xin
       LFSR_RC(wgrad3(p + "fuse.2.weight", t.FZ[i], gy, 64));
-      LFSR_RC(dgrad3(gy, 64, p + "fuse.2.weight", t.dF, nullptr, nullptr, t.FZ[i], 64));
+      LFSR_RC(dgrad3(gy, 64, p + "fuse.2.weight", t.dF, nullptr, t.FZ[i], 64));
       // fuse.0 : FZ = lrelu(1x1(CAT))
       {   // streaming kernel (every row of dF and CAT read once, one slab per block); else the generic split-K kernel
         float* Pw = t.PA;
@@ -581,14 +580,14 @@ static int distgssr_backward_impl(lfsr_distgssr* c, const float* x, const float*
       }
       // SpaConv : CAT[0:64] = lrelu(conv(S1)), S1 = lrelu(conv(Xin))
       LFSR_RC(wgrad3(p + "SpaConv.2.weight", t.S1[i], t.dCAT, 144));
-      LFSR_RC(dgrad3(t.dCAT, 144, p + "SpaConv.2.weight", t.dS1, nullptr, nullptr, t.S1[i], 64));
+      LFSR_RC(dgrad3(t.dCAT, 144, p + "SpaConv.2.weight", t.dS1, nullptr, t.S1[i], 64));
       LFSR_RC(wgrad3(p + "SpaConv.0.weight", Xin, t.dS1, 64));
       // gx = gy (block skip) + dSpa; in the group's first block the group skip dG rides along as the second residual (else: one more pass over gx at the group's end)
       if (b == 0 && !skip_fused) {
         const int r2rc = lfsr_conv3x3_bwd_data_r2(t.dS1, 64, c->wT(p + "SpaConv.0.weight"), gx, gy, dG, nimg, h, w, st);
         if (r2rc == LFSR_OK) skip_fused = true; else if (r2rc != LFSR_E_ARG) return r2rc;
       }
-      if (!(b == 0 && skip_fused)) LFSR_RC(dgrad3(t.dS1, 64, p + "SpaConv.0.weight", gx, gy, nullptr, nullptr, 0));
+      if (!(b == 0 && skip_fused)) LFSR_RC(dgrad3(t.dS1, 64, p + "SpaConv.0.weight", gx, gy, nullptr, 0));
       // AngConv : CAT[64:80] = PS(lrelu(1x1(A16))), A16 = lrelu(convAxA(Xin))          (branch_bwd.cpp; also exported as lfsr_angconv_bwd)
       // EPIConv (horizontal, then vertical; shared weights -> both partial sets summed in one reduce)                 (lfsr_epiconv_hv_bwd)
       const float *wa0 = c->w(p + "AngConv.0.weight"), *wa0T = c->wT(p + "AngConv.0.weight"), *wa2T = c->wT(p + "AngConv.2.weight");

@@ -255,15 +255,27 @@ int lfsr_pack_conv_weight(const float* w, float* packed, int O, int C, int taps,
 
 }  // extern "C"
 
+// the 3x3 conv 64 -> 64 on the gather-GEMM, either direction: the one form without an alignment demand on y / r1 / r2 / mk
+int lfsr_conv3x3_gather_launch(const LfsrConv3& c, hipStream_t st) {
+  if ((c.x_stride | c.x_choff) & 3) return LFSR_E_ARG;
+  GemmArgs p{};
+  p.X = c.x; p.x_stride = c.x_stride; p.x_choff = c.x_choff; p.Wp = c.w_direct(); p.bias = nullptr;
+  p.Y = c.y; p.y_stride = c.y_stride; p.y_choff = c.y_choff;
+  p.R1 = c.r1; p.r1_stride = c.r1_stride; p.r1_choff = c.r1_choff; p.R2 = c.r2; p.r2_stride = c.r2_stride; p.r2_choff = c.r2_choff;
+  p.Mk = c.mk; p.mk_stride = c.mk_stride; p.mk_choff = c.mk_choff; p.mk_slope = c.mk_slope;
+  p.M = c.n_img * c.h * c.w; p.N = 64; p.Npad = 64; p.A = 1; p.AA = 1; p.H = c.h; p.W = c.w; p.ntaps = 9; p.CH = 64; p.slope = c.slope;
+  return launch_gemm<IN_CONV3, OUT_SAME, 64, 2>(p, st);
+}
+
 int lfsr_pack_conv_weight_m(const float* w, float* packed, int O, int C, int taps, int perm, int ch, int mask, void* stream) {
   if (!w || !packed || O <= 0 || C <= 0 || taps <= 0 || (perm != 0 && perm != 1)) return LFSR_E_ARG;
   if (perm == 1 && (ch <= 0 || O % ch != 0)) return LFSR_E_ARG;
   if (O == 64 && C == 64 && taps == 9 && perm == 0 && mask == LFSR_W_WINO4)   // the runtimes' lean repack: one launch per weight
-    return lfsr_pack_conv3_raw_wino4(w, packed, packed + LFSR_CONV3_DIRECT_FLOATS + LFSR_CONV3_WINO2_FLOATS, 0, lfsr_stream(stream));
+    return lfsr_pack_conv3_raw_wino4(w, packed, packed + LFSR_CONV3_WINO4_OFF, 0, lfsr_stream(stream));
   long long total = (long long)taps * npad32(O) * C;
   hipLaunchKernelGGL(k_pack_weight, dim3(lfsr_blocks(total, 256)), dim3(256), 0, lfsr_stream(stream), w, packed, O, C, taps, npad32(O), perm, ch);
   LFSR_CHECK_LAUNCH();
-  if (O == 64 && C == 64 && taps == 9 && perm == 0) return lfsr_pack_wino_m(packed, packed + LFSR_CONV3_DIRECT_FLOATS, mask, lfsr_stream(stream));
+  if (O == 64 && C == 64 && taps == 9 && perm == 0) return lfsr_pack_wino_m(packed, packed + LFSR_CONV3_WINO2_OFF, mask, lfsr_stream(stream));
   if (O == 32 && C == 64 && taps == 25 && perm == 0) {
     const int rc = lfsr_pack_epi_wino(packed, packed + 25 * 32 * 64, lfsr_stream(stream));
     return rc ? rc : lfsr_pack_epi_b3(packed, packed + 25 * 32 * 64 + LFSR_EPI_WINO_FLOATS, 0, lfsr_stream(stream));
@@ -281,28 +293,11 @@ int lfsr_conv3x3_fwd(const float* x, int x_stride, int x_choff, const float* w_p
   if (!x || !w_packed || !y || n_img <= 0 || h <= 0 || w <= 0) return LFSR_E_ARG;
   if (x_stride < x_choff + 64 || y_stride < y_choff + 64 || (x_stride | x_choff) & 3) return LFSR_E_ARG;
   if ((long long)n_img * h * w >= (1LL << 31) / 4) return LFSR_E_ARG;
-  {
-    // the tile kernels need 16-B aligned channel vectors on every operand; LFSR_CONV3X3 = halo | gather forces the direct
-    // 9-tap halo kernel / the v1 gather-GEMM (A/B runs)
-    const char* sel = lfsr_conv3_fwd_sel();
-    const bool force_v1 = sel && sel[0] == 'g';
-    const bool force_halo = sel && sel[0] == 'h';
-    const bool al = !((y_stride | y_choff) & 3) && (!r1 || !((r1_stride | r1_choff) & 3)) && (!r2 || !((r2_stride | r2_choff) & 3));
-    if (al && !force_v1 && !force_halo) {
-      const int rc = lfsr_conv3x3_wino_launch(x, x_stride, x_choff, w_packed + LFSR_CONV3_DIRECT_FLOATS, w_packed, y, y_stride, y_choff, r1, r1_stride, r1_choff,
-                                              r2, r2_stride, r2_choff, nullptr, 0, 0, 1.0f, n_img, h, w, slope, sel, lfsr_stream(stream));
-      if (rc != LFSR_E_ARG) return rc;   // (E_ARG: a geometry the Winograd launchers do not cover -> the direct kernel)
-    }
-    if (al && !force_v1)
-      return lfsr_conv3x3_halo_launch(x, x_stride, x_choff, w_packed, y, y_stride, y_choff, r1, r1_stride, r1_choff, r2, r2_stride, r2_choff,
-                                      nullptr, 0, 0, 1.0f, n_img, h, w, slope, lfsr_stream(stream));
-  }
-  GemmArgs p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wp = w_packed; p.bias = nullptr;
-  p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff;
-  p.R1 = r1; p.r1_stride = r1_stride; p.r1_choff = r1_choff; p.R2 = r2; p.r2_stride = r2_stride; p.r2_choff = r2_choff;
-  p.M = n_img * h * w; p.N = 64; p.Npad = 64; p.A = 1; p.AA = 1; p.H = h; p.W = w; p.ntaps = 9; p.CH = 64; p.slope = slope;
-  return launch_gemm<IN_CONV3, OUT_SAME, 64, 2>(p, lfsr_stream(stream));
+  LfsrConv3 c{};
+  c.x = x; c.x_stride = x_stride; c.x_choff = x_choff; c.w_packed = w_packed; c.y = y; c.y_stride = y_stride; c.y_choff = y_choff;
+  c.r1 = r1; c.r1_stride = r1_stride; c.r1_choff = r1_choff; c.r2 = r2; c.r2_stride = r2_stride; c.r2_choff = r2_choff;
+  c.mk_slope = 1.0f; c.n_img = n_img; c.h = h; c.w = w; c.slope = slope;
+  return lfsr_conv3x3_run(c, false, lfsr_stream(stream));
 }
 
 int lfsr_pointwise_fwd(const float* x, int x_stride, int x_choff, int cin, const float* w_packed, const float* bias,

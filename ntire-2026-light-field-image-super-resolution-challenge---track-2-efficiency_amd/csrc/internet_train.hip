@@ -275,7 +275,7 @@ int lfsr_internet_forward_train(lfsr_internet* c, const float* x, float* out, in
   auto packT = [&](const std::string& key, float* o, int T, int Npad_in, int C, int O, int k0, int Kc, int flip) -> int {
     hipLaunchKernelGGL(k_pack_T_from_fwd, dim3(cap_grid((long long)T * Kc * O)), dim3(256), 0, st, P.w(key), o, T, Npad_in, C, O, k0, Kc, flip);
     LFSR_CHECK_LAUNCH();
-    if (T == 9 && O == 64 && Kc == 64) return lfsr_pack_wino_m(o, o + LFSR_CONV3_DIRECT_FLOATS, LFSR_W_ALL, st);   // the 64 -> 64 3x3 data gradient's Winograd copies
+    if (T == 9 && O == 64 && Kc == 64) return lfsr_pack_wino_m(o, o + LFSR_CONV3_WINO2_OFF, LFSR_W_ALL, st);   // the 64 -> 64 3x3 data gradient's Winograd copies
     return LFSR_OK;
   };
   for (int g = 0; g < NG; ++g)

@@ -61,30 +61,46 @@ struct LfsrOpTimer {
   hipStream_t st_;
 };
 
-// conv3x3_halo.hip
-int lfsr_conv3x3_halo_launch(const float* x, int x_stride, int x_choff, const float* w_packed, float* y, int y_stride, int y_choff,
-                             const float* r1, int r1_stride, int r1_choff, const float* r2, int r2_stride, int r2_choff,
-                             const float* mk, int mk_stride, int mk_choff, float mk_slope,
-                             int n_img, int h, int w, float slope, hipStream_t st);
-int lfsr_conv3x3_halo_tail_launch(const float* x, int x_stride, int x_choff, const float* w_packed, float* y, int y_stride, int y_choff,
-                                  const float* r1, int r1_stride, int r1_choff, const float* r2, int r2_stride, int r2_choff,
-                                  const float* mk, int mk_stride, int mk_choff, float mk_slope,
-                                  int n_img, int h, int w, float slope, int tile_begin, int tile_count, hipStream_t st);
-// conv3x3_wino.hip: Winograd F(2x2,3x3) form of the same op.  A packed 3x3 64->64 weight is the direct pack [9][64][64]
-// (LFSR_CONV3_DIRECT_FLOATS) immediately followed by its Winograd-domain pack (LFSR_CONV3_WINO_FLOATS), see lfsr_pack_wino.
+// The 64 -> 64 3x3 conv's packed weight: the direct pack [9][64][64] (LFSR_CONV3_DIRECT_FLOATS), then its Winograd-domain copies (LFSR_CONV3_WINO_FLOATS, see
+// lfsr_pack_wino): the F(2x2,3x3) pack of conv3x3_wino.hip (LFSR_CONV3_WINO2_FLOATS), then the F(4x4,3x3) pack of conv3x3_wino4.hip.
 #define LFSR_CONV3_DIRECT_FLOATS (9 * 64 * 64)
-// The Winograd part is the F(2x2,3x3) pack (LFSR_CONV3_WINO2_FLOATS) followed by the F(4x4,3x3) pack of conv3x3_wino4.hip.
 #define LFSR_CONV3_WINO2_FLOATS (16 * 64 * 64)
 #define LFSR_CONV3_WINO4_FLOATS (36 * 64 * 64)
 #define LFSR_CONV3_WINO_FLOATS (LFSR_CONV3_WINO2_FLOATS + LFSR_CONV3_WINO4_FLOATS)
+#define LFSR_CONV3_WINO2_OFF LFSR_CONV3_DIRECT_FLOATS                                  // where the copies begin in a pack: the only place that spells the layout out
+#define LFSR_CONV3_WINO4_OFF (LFSR_CONV3_DIRECT_FLOATS + LFSR_CONV3_WINO2_FLOATS)
+// One 3x3 conv 64 -> 64 (forward, or a data gradient on the transposed pack): y = lrelu(conv(x), slope) [* (mk > 0 ? 1 : mk_slope)] [+ r1] [+ r2].
+// Every kernel launcher of the operator takes this; lfsr_conv3x3_run (conv3x3.cpp) picks the launcher.
+struct LfsrConv3 {
+  const float* x; int x_stride, x_choff;
+  const float* w_packed;                            // base of the whole pack
+  float* y; int y_stride, y_choff;
+  const float* r1; int r1_stride, r1_choff;         // residuals (may be null)
+  const float* r2; int r2_stride, r2_choff;
+  const float* mk; int mk_stride, mk_choff; float mk_slope;   // backward: the saved activation behind a LeakyReLU (may be null)
+  int n_img, h, w;
+  float slope;
+  const float* w_direct() const { return w_packed; }
+  const float* w_wino2() const { return w_packed + LFSR_CONV3_WINO2_OFF; }
+  const float* w_wino4() const { return w_packed + LFSR_CONV3_WINO4_OFF; }
+};
+// The launchers return LFSR_E_ARG for a geometry they do not cover: the dispatcher then goes on to the next kernel of its chain.
+int lfsr_conv3x3_halo_launch(const LfsrConv3& c, hipStream_t st);                                      // conv3x3_halo.hip: direct 9-tap form
+int lfsr_conv3x3_halo_tail_launch(const LfsrConv3& c, int tile_begin, int tile_count, hipStream_t st);  // ... its channel-split launch over a tile range only
+int lfsr_conv3x3_wino2_launch(const LfsrConv3& c, hipStream_t st);                                     // conv3x3_wino.hip: F(2x2,3x3); operand spans below 2 GiB
+int lfsr_conv3x3_wino4_launch(const LfsrConv3& c, hipStream_t st);                                     // conv3x3_wino4.hip: F(4x4,3x3); operand spans below 1 GiB
+int lfsr_conv3x3_gather_launch(const LfsrConv3& c, hipStream_t st);                                    // gemm_gather.hip: gather-GEMM, no alignment demand on y / r1 / r2 / mk
+// conv3x3.cpp: which kernel runs.  LFSR_CONV3X3 selects the forward kernel, LFSR_DGRAD3 (same vocabulary) the data-gradient kernel, which otherwise follows
+// LFSR_CONV3X3.  The selection is read when weights are packed AND at every launch: set it before loading a model.
+enum LfsrConv3Sel { LFSR_C3_DEFAULT = 0, LFSR_C3_WINO4, LFSR_C3_WINO2, LFSR_C3_HALO, LFSR_C3_GATHER };   // DEFAULT: nothing selected (runs as WINO4)
+LfsrConv3Sel lfsr_conv3_fwd_sel();
+LfsrConv3Sel lfsr_conv3_dgrad_sel();
+int lfsr_conv3x3_run(const LfsrConv3& c, bool dgrad, hipStream_t st);
 int lfsr_pack_wino(const float* direct_packed, float* out, hipStream_t st);   // every Winograd-domain copy (the operator-level pack)
 // ... or only the copies in `mask` (LFSR_W_WINO2 | LFSR_W_WINO4).  The model runtimes repack every weight each
-// training step and write only what the selected 3x3 kernel reads: lfsr_conv3_variant_mask() = the copies LFSR_CONV3X3 selects (default: wino4).
-// The selection is read when weights are packed AND when a conv is launched: set it before loading a model.
+// training step and write only what the selected 3x3 kernels read: lfsr_conv3_variant_mask() (default: wino4).
 enum { LFSR_W_WINO2 = 1, LFSR_W_WINO4 = 2, LFSR_W_ALL = 3 };
 int lfsr_conv3_variant_mask();          // union of the copies the forward (LFSR_CONV3X3) and the data-gradient (LFSR_DGRAD3) selections read
-const char* lfsr_conv3_fwd_sel();
-const char* lfsr_conv3_dgrad_sel();
 // Batched repack (training: every weight is repacked every step; one launch per pack KIND with a device-side descriptor table instead of one 4-us
 // launch per weight and layout).  kind 0: lfsr_pack_conv_weight's direct pack (perm 0 / 1), 1: lfsr_pack_weight_T (flip = taps reversed), 2: lfsr_pack_weight_chunkT.
 struct LfsrPackDesc { const float* src; float* dst; float* dst2; int kind, O, C, T, Npad, perm, ch, flip; };
@@ -96,15 +112,6 @@ int lfsr_pack_wino_m(const float* direct_packed, float* out, int mask, hipStream
 int lfsr_pack_conv_weight_m(const float* w, float* packed, int O, int C, int taps, int perm, int ch, int mask, void* stream);
 int lfsr_pack_weight_T_m(const float* w, float* out, int O, int C, int T, int flip, int mask, hipStream_t st);
 int lfsr_pack_wino4(const float* direct_packed, float* out, hipStream_t st);
-// conv3x3_wino4.hip: F(4x4,3x3) form; LFSR_E_ARG = geometry not covered (operands of 1 GiB and more)
-int lfsr_conv3x3_wino4_launch(const float* x, int x_stride, int x_choff, const float* w_wino4, float* y, int y_stride, int y_choff,
-                              const float* r1, int r1_stride, int r1_choff, const float* r2, int r2_stride, int r2_choff,
-                              const float* mk, int mk_stride, int mk_choff, float mk_slope,
-                              int n_img, int h, int w, float slope, hipStream_t st);
-int lfsr_conv3x3_wino_launch(const float* x, int x_stride, int x_choff, const float* w_wino, const float* w_direct, float* y, int y_stride, int y_choff,
-                             const float* r1, int r1_stride, int r1_choff, const float* r2, int r2_stride, int r2_choff,
-                             const float* mk, int mk_stride, int mk_choff, float mk_slope,
-                             int n_img, int h, int w, float slope, const char* sel, hipStream_t st);
 // ang_fused.hip: the AngConv branch (conv AxA stride A 64->16, 1x1 16->16AA, PixelShuffle(A)) in one launch
 bool lfsr_ang_fused_ok(int A);
 int lfsr_ang_fused_launch(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed, float* t, float* y,

@@ -539,7 +539,7 @@ int lfsr_lft_backward(lfsr_lft* c, const float* x, const float* dout, int B, int
   auto packT = [&](const float* Wp, int n0, int C, int O, float* o) -> int { return lfsr_pack_T_from_fwd(Wp + (size_t)n0 * C, o, 1, O, C, O, 0, C, 0, st); };
   auto pack3T = [&](const std::string& key, float* o) -> int {
     LFSR_RC(lfsr_pack_T_from_fwd(P.w(key), o, 9, 64, 64, 64, 0, 64, 1, st));
-    return lfsr_pack_wino_m(o, o + LFSR_CONV3_DIRECT_FLOATS, LFSR_W_ALL, st);   // the 64 -> 64 3x3 data gradient's Winograd copies
+    return lfsr_pack_wino_m(o, o + LFSR_CONV3_WINO2_OFF, LFSR_W_ALL, st);   // the 64 -> 64 3x3 data gradient's Winograd copies
   };
 
   // ---- tail: upsampling.0 (1x1 64 -> 64 s^2), PixelShuffle(s), LeakyReLU 0.2, 3x3 conv 64 -> 1, + bicubic skip (no parameters) ----------
