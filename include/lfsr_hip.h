@@ -207,7 +207,8 @@ int lfsr_distgssr_backward(lfsr_distgssr* ctx, const float* x, const float* dout
 size_t lfsr_packed_weight_tr_floats(int O, int C, int taps);
 int lfsr_pack_conv_weight_tr(const float* w, float* packed_T, int O, int C, int taps, void* stream);
 /* dx = (conv3x3^T(dy)) * LeakyReLU'(act) + r1: `act` = the saved output of the LeakyReLU(act_slope) in front of this conv's input
- * (NULL: none), r1 = a gradient arriving over a skip connection (NULL: none).  64 -> 64, per-view zero pad 1. */
+ * (NULL: none), r1 = a gradient arriving over a skip connection (NULL: none).  64 -> 64, per-view zero pad 1.  dy_stride and dy_choff must be
+ * multiples of 4 (LFSR_E_ARG otherwise); dx, r1 and act may sit at any offset (off the 16-byte grid the gather-GEMM runs). */
 int lfsr_conv3x3_dgrad(const float* dy, int dy_stride, int dy_choff, const float* wT_packed, float* dx, int dx_stride, int dx_choff,
                        const float* r1, int r1_stride, int r1_choff, const float* act, int act_stride, int act_choff, float act_slope,
                        int n_img, int h, int w, void* stream);

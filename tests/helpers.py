@@ -57,7 +57,8 @@ _PERMS = {}
 
 
 def mask_ref_shape(kind, B, A, h, w):
-    return {"S1": (B, 64, h * A, w * A), "S2": (B, 64, h * A, w * A), "FZ": (B, 64, h * A, w * A), "A1": (B, 16, h, w), "A2": (B, 16 * A * A, h, w),
+    return {"S1": (B, 64, h * A, w * A), "S2": (B, 64, h * A, w * A), "FZ": (B, 64, h * A, w * A), "OUT": (B, 64, h * A, w * A), "A1": (B, 16, h, w),
+            "A2": (B, 16 * A * A, h, w),
             "EH1": (B, 32, h * A, w), "EH2": (B, 32 * A, h * A, w), "EV1": (B, 32, w * A, h), "EV2": (B, 32 * A, w * A, h)}[kind]
 
 
@@ -72,7 +73,7 @@ def _ref_to_hip(kind, t, B, A, h, w):
     def ps1d(z, f):   # DistgSSR.py:114-131 (factor-major channel order)
         Bz, fC, Hh, Ww = z.shape
         return z.reshape(Bz, f, fC // f, Hh, Ww).permute(0, 2, 3, 4, 1).reshape(Bz, fC // f, Hh, Ww * f)
-    if kind in ("S1", "S2", "FZ"):
+    if kind in ("S1", "S2", "FZ", "OUT"):
         return vcl(t)
     if kind == "A1":
         return t.permute(0, 2, 3, 1).reshape(-1)
@@ -466,3 +467,216 @@ def lft_forced_fp64_grads(rt, xg, sd, x, label, A, s):
         y, _, flips = lft_layers_fp64(x, p, A, s, forced=lft_hip_masks(rt, xg, A, s))
         torch.nn.functional.l1_loss(y, lab).backward()
     return {k: v.grad.numpy() for k, v in p.items()}, flips
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# DistgSSR: the geometry matrix, the parameter table at any angRes / scale, the reference graph with every tensor
+# lfsr_distgssr_train_saved can return, and the maps between the graph's layouts and the HIP path's rows (_ref_to_hip / mask_perm above)
+# ---------------------------------------------------------------------------------------------------------------------
+# (A, s, B, h, w) and what each row reaches
+DISTG_MATRIX = ((7, 2, 1, 5, 6),        # A != 5: gather EPI forward, three-kernel block tail, gather forms of every EPI gradient; npix 1470 < 2048: gather fuse.0 dgrad
+                (9, 2, 1, 4, 4),        # 81 views, 9x9 AngConv.0
+                (15, 2, 1, 3, 4),       # the largest angRes lfsr_distgssr_create accepts
+                (1, 3, 2, 9, 7),        # one view, EPI lines of one pixel group, scale 3, odd ragged views
+                (3, 3, 2, 13, 16),      # the fp32 fused-EPI kernels at A = 3, scale 3, odd h in the two-row Winograd weight-gradient tiles
+                (5, 3, 2, 13, 16),      # the bench angRes: k_distg_tail, epi_b3, line-form gradients on ragged lines, k_head_bwd<3>
+                (5, 2, 1, 40, 24),      # h > 32 >= w: line form for the horizontal pass, gather for the vertical, unmerged EPIConv.0 wgrad, two row tiles per view
+                (5, 4, 1, 24, 40),      # the transpose of the row above
+                (3, 2, 1, 33, 40),      # both view sides past 32 at A = 3; k_ang0_dgrad runs 6 chunks of 220 pixels
+                (5, 4, 3, 32, 32),      # an odd batch at the bench geometry
+                (5, 4, 8, 32, 32),      # the published training geometry: 204 800 pixels, past the block caps of k_add_inplace, k_head_bwd, k_init_gather9
+                (4, 2, 1, 6, 5),        # even A: forward-only rows (the backward must refuse)
+                (2, 3, 2, 9, 7))
+DISTG_PER_SAMPLE_NPIX = 50000             # above this many LR pixels the fp64 work is done one sample at a time
+# which of lfsr_distgssr_train_saved -> the kinds its rows hold side by side, and each kind's channels per row (all post-LeakyReLU values; "OUT" is
+# the block output, the only one that is no decision)
+DISTG_SAVED = {0: ("S1",), 1: ("S2", "A2", "EH2", "EV2"), 2: ("A1",), 3: ("EH1",), 4: ("EV1",), 5: ("FZ",), 6: ("OUT",)}
+DISTG_CH = {"S1": 64, "S2": 64, "A2": 16, "EH2": 32, "EV2": 32, "A1": 16, "EH1": 32, "EV1": 32, "FZ": 64, "OUT": 64}
+DISTG_BLOCKS = tuple(f"disentg.Group.{g}.Block.{b}." for g in range(4) for b in range(4))
+
+
+def distg_spec(A, s):
+    """(key, shape) list of DistgSSR at angRes A and scale s: lfsr_distgssr_create's table (model/SR/DistgSSR.py's state_dict), 137 entries"""
+    AA = A * A
+    spec = [("init_conv.weight", (64, 1, 3, 3))]
+    for g in range(4):
+        for b in range(4):
+            p = f"disentg.Group.{g}.Block.{b}."
+            spec += [(p + "SpaConv.0.weight", (64, 64, 3, 3)), (p + "SpaConv.2.weight", (64, 64, 3, 3)),
+                     (p + "AngConv.0.weight", (16, 64, A, A)), (p + "AngConv.2.weight", (AA * 16, 16, 1, 1)),
+                     (p + "EPIConv.0.weight", (32, 64, 1, AA)), (p + "EPIConv.2.weight", (A * 32, 32, 1, 1)),
+                     (p + "fuse.0.weight", (64, 144, 1, 1)), (p + "fuse.2.weight", (64, 64, 3, 3))]
+        spec.append((f"disentg.Group.{g}.conv.weight", (64, 64, 3, 3)))
+    spec += [("disentg.conv.weight", (64, 64, 3, 3)), ("upsample.0.weight", (64 * s * s, 64, 1, 1)), ("upsample.0.bias", (64 * s * s,)),
+             ("upsample.2.weight", (1, 64, 1, 1))]
+    return spec
+
+
+def distg_case(A, s, B, h, w):
+    """-> (state_dict, input): synth_state_dict seed 0 / synth_input seed 1, as the golden cases"""
+    return synth_state_dict(distg_spec(A, s), seed=0), synth_input((B, 1, A * h, A * w), seed=1)
+
+
+def distg_keys():
+    """every (which, index) of lfsr_distgssr_train_saved: 7 x 16"""
+    return [(k, i) for k in DISTG_SAVED for i in range(16)]
+
+
+def distg_samples(A, s, B, h, w):
+    """the slices of the batch the fp64 graph takes at once: the whole batch, or one sample at a time at the published geometry"""
+    return [slice(i, i + 1) for i in range(B)] if B > 1 and B * A * A * h * w > DISTG_PER_SAMPLE_NPIX else [slice(0, B)]
+
+
+def distg_layers_fp64(x, params, A, s, forced=None, dtype=None):
+    """DistgSSR's graph (model/SR/DistgSSR.py:29-36, 104-111, op for op as oracle/lfsr_torch_port.py::distgssr_forward_graph states it) on stock
+    torch CPU ops -> (output, layers, flips).
+    layers[(kind, index)]: the LeakyReLU outputs of MASK_KINDS and the block output "OUT" of block index = group * 4 + block, detached, in the
+    reference's layouts (mask_ref_shape): every value lfsr_distgssr_train_saved can return (DISTG_SAVED; distg_ref_to_rows).
+    params: {key: tensor} (fp64 unless `dtype` says otherwise; they may require grad).  forced: {(kind, index): bool mask in the reference
+    layout} for MASK_KINDS -- the decisions are then the caller's (y = t where mask else 0.1 t, the port's `force=`), and flips counts those
+    that differ from the graph's own."""
+    import torch
+    from oracle.lfsr_torch_port import macpi2sai, pixel_shuffle1d, sai2macpi
+    F = torch.nn.functional
+    dtype = dtype or torch.float64
+    p = {k: torch.as_tensor(v).to(dtype) for k, v in params.items()}
+    xd = torch.as_tensor(x).to(dtype)
+    L, flips = {}, 0
+
+    def block(z, pre, i):
+        def lr(t, kind):
+            nonlocal flips
+            if forced is None:
+                y = F.leaky_relu(t, 0.1)
+            else:
+                m = forced[kind, i]
+                flips += int(((t > 0) != m).sum())
+                y = torch.where(m, t, 0.1 * t)
+            L[kind, i] = y.detach()
+            return y
+        spa = lr(F.conv2d(z, p[pre + "SpaConv.0.weight"], dilation=A, padding=A), "S1")
+        spa = lr(F.conv2d(spa, p[pre + "SpaConv.2.weight"], dilation=A, padding=A), "S2")
+        ang = lr(F.conv2d(z, p[pre + "AngConv.0.weight"], stride=A), "A1")
+        ang = F.pixel_shuffle(lr(F.conv2d(ang, p[pre + "AngConv.2.weight"]), "A2"), A)
+
+        def epi(t, tag):
+            e = lr(F.conv2d(t, p[pre + "EPIConv.0.weight"], stride=(1, A), padding=(0, A * (A - 1) // 2)), tag + "1")
+            return pixel_shuffle1d(lr(F.conv2d(e, p[pre + "EPIConv.2.weight"]), tag + "2"), A)
+        epih = epi(z, "EH")
+        epiv = epi(z.permute(0, 1, 3, 2).contiguous(), "EV").permute(0, 1, 3, 2)
+        buf = torch.cat((spa, ang, epih, epiv), dim=1)
+        buf = lr(F.conv2d(buf, p[pre + "fuse.0.weight"]), "FZ")
+        out = F.conv2d(buf, p[pre + "fuse.2.weight"], dilation=A, padding=A) + z
+        L["OUT", i] = out.detach()
+        return out
+    x_up = F.interpolate(xd, scale_factor=s, mode="bilinear", align_corners=False)
+    buf0 = F.conv2d(sai2macpi(xd, A), p["init_conv.weight"], dilation=A, padding=A)
+    buf = buf0
+    for g in range(4):
+        gin = buf
+        for b in range(4):
+            buf = block(buf, f"disentg.Group.{g}.Block.{b}.", g * 4 + b)
+        buf = F.conv2d(buf, p[f"disentg.Group.{g}.conv.weight"], dilation=A, padding=A) + gin
+    buf = F.conv2d(buf, p["disentg.conv.weight"], dilation=A, padding=A) + buf0
+    up = F.conv2d(macpi2sai(buf, A), p["upsample.0.weight"], p["upsample.0.bias"])
+    up = F.conv2d(F.pixel_shuffle(up, s), p["upsample.2.weight"])
+    return up + x_up, L, flips
+
+
+def distg_ref_to_rows(layers, which, index, B, A, h, w):
+    """the reference's tensors of (which, index) as the HIP path stores them: rows in HIP order, the kinds of DISTG_SAVED[which] side by side
+    (which 1: the 144-wide concat buffer)"""
+    import torch
+    return torch.cat([_ref_to_hip(k, layers[k, index], B, A, h, w).reshape(-1, DISTG_CH[k]) for k in DISTG_SAVED[which]], 1)
+
+
+def distg_saved_rows(rt, xg, which, index=0):
+    """what forward_train(xg) saved for (which, index), as rows in HIP order (a GPU view of the training workspace)"""
+    return rt.train_saved(xg, which, index).reshape(-1, sum(DISTG_CH[k] for k in DISTG_SAVED[which]))
+
+
+def distg_hip_masks_flat(rt, xg):
+    """the LeakyReLU decisions (> 0) of forward_train(xg), flat in HIP order: {(kind, index): CPU bool tensor}"""
+    return {(k, i): hip_saved_mask(rt, xg, k, i) for i in range(16) for k in MASK_KINDS}
+
+
+def distg_masks_to_ref(flat, B, A, h, w, sample=None):
+    """the same decisions in the reference layouts: what distg_layers_fp64's `forced` takes.  sample = i: the decisions of sample i alone, as a
+    B = 1 graph takes them (every HIP layout is sample-major)"""
+    out = {}
+    for (k, i), m in flat.items():
+        if sample is not None:
+            n = m.numel() // B
+            m = m[sample * n:(sample + 1) * n]
+        out[k, i] = hip_mask_to_ref(m, k, B if sample is None else 1, A, h, w)
+    return out
+
+
+def distg_forced_fp64_grads(rt, xg, sd, x, label, A, s, masks=None):
+    """fp64 autograd of distg_layers_fp64 under L1 `mean` loss with every LeakyReLU decision taken from what the HIP training forward saved
+    (lfsr_distgssr_train_saved; `masks`: distg_hip_masks_flat read earlier), and the number of those decisions that differ from fp64's own.  A
+    pre-activation within fp32 rounding of 0 is a legitimate tie whose two sides have different gradients downstream; this graph makes the same
+    choices.  Large batches go one sample at a time: the batch gradient of a mean loss is the mean of the per-sample gradients, each under that
+    sample's slice of the decisions."""
+    import torch
+    B, h, w = x.shape[0], x.shape[2] // A, x.shape[3] // A
+    masks = distg_hip_masks_flat(rt, xg) if masks is None else masks
+    p = {k: torch.tensor(v, dtype=torch.float64, requires_grad=True) for k, v in sd.items()}
+    lab = torch.as_tensor(label, dtype=torch.float64)
+    flips = 0
+    for sl in distg_samples(A, s, B, h, w):
+        n = sl.stop - sl.start
+        y, _, f = distg_layers_fp64(x[sl], p, A, s, forced=distg_masks_to_ref(masks, B, A, h, w, sample=None if n == B else sl.start))
+        (torch.nn.functional.l1_loss(y, lab[sl]) * (n / B)).backward()
+        flips += f
+        del y
+    return {k: v.grad.numpy() for k, v in p.items()}, flips
+
+
+def _rel_l2(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
+
+
+def distg_cpu_fp32_rel(geom, sd, x, label):
+    """e_ref of the cancellation allowance: fp32 CPU autograd of the same graph against fp64 autograd, each under its own decisions"""
+    A, s, B, h, w = geom
+    import torch
+    out = []
+    for dt in (torch.float32, torch.float64):
+        p = {k: torch.tensor(v, dtype=dt, requires_grad=True) for k, v in sd.items()}
+        for sl in distg_samples(*geom):
+            y, _, _ = distg_layers_fp64(x[sl], p, A, s, dtype=dt)
+            (torch.nn.functional.l1_loss(y, torch.as_tensor(label[sl]).to(dt)) * ((sl.stop - sl.start) / B)).backward()
+            del y
+        out.append({k: v.grad.numpy() for k, v in p.items()})
+    return {k: _rel_l2(out[0][k], out[1][k]) for k in sd}
+
+
+def distg_forced_gradient_gate(tag, net, xg, sd, x, label, A, s, masks, geom, host=None):
+    """every parameter's gradient (137 state_dict entries) against fp64 autograd of the reference graph under the HIP forward's own LeakyReLU
+    decisions: rel-L2 < 1e-4 per parameter, no parameter and no element left out.  A parameter that misses it gets the allowance of
+    test_gpu_distgssr_train.py::test_grads_full_geometry_vs_torch_port_autograd, max(1e-4, 3 x e_ref), e_ref being the fp32 CPU autograd of the same
+    graph against fp64 under its own decisions: what is cancellation there is cancellation here (upsample.0.bias, a sum of +-1/N).
+    host: a {"s": seconds} counter of reference work on the host, added to.  -> {parameter: rel-L2}"""
+    import time
+    host = {"s": 0.0} if host is None else host
+    t0 = time.time()
+    forced, flips = distg_forced_fp64_grads(net._rt, xg, sd, x, label, A, s, masks=masks)
+    host["s"] += time.time() - t0
+    names = [k for k, _ in net.named_parameters()]
+    assert names == [k for k, _ in distg_spec(A, s)] and len(names) == 137 and sum(p.numel() for p in net.parameters()) == net.grad_bucket.numel()
+    errs = {k: _rel_l2(p.grad.detach().cpu().numpy(), forced[k]) for k, p in net.named_parameters()}
+    v = np.array(list(errs.values()))
+    print(f"{tag}: gradient rel-L2 vs fp64 median {np.median(v):.2e} max {v.max():.2e} ({max(errs, key=errs.get)}); "
+          f"LeakyReLU decisions differing from fp64's own: {flips}; host {host['s']:.0f} s so far")
+    bad = {k: e for k, e in errs.items() if not e < 1e-4}
+    if bad:
+        t0 = time.time()
+        e_ref = distg_cpu_fp32_rel(geom, sd, x, label)
+        host["s"] += time.time() - t0
+        for k, e in bad.items():
+            print(f"{tag}: {k} rel-L2 {e:.3e}, fp32 CPU autograd against fp64 {e_ref[k]:.3e}")
+        bad = {k: (e, e_ref[k]) for k, e in bad.items() if not e < max(1e-4, 3 * e_ref[k])}
+    assert not bad, bad
+    return errs

@@ -70,13 +70,16 @@ def test_grads_vs_reference_golden():
 def test_grads_vs_torch_port_autograd(A, h, w, s, B):
     """every parameter, full tensors, against autograd over stock torch CPU ops (oracle/lfsr_torch_port.py)"""
     from oracle import lfsr_torch_port as T
+    from tests import helpers as TH
     tag = "a5h8s4" if A == 5 else "a3h6w8s2"
     case, sd, x, _ = model_case("DistgSSR", tag)
     M = load_plugin()
     net = build(M, A, s, sd)
     label_np = synth_input((B, 1, A * h * s, A * w * s), seed=2)
-    out = net(torch.from_numpy(x).cuda(), None)
+    xg = torch.from_numpy(x).cuda()
+    out = net(xg, None)
     loss = torch.nn.functional.l1_loss(out, torch.from_numpy(label_np).cuda())
+    masks = TH.distg_hip_masks_flat(net._rt, xg)          # the forward's LeakyReLU decisions, before the backward
     loss.backward()
     sdt = {k: torch.from_numpy(v).double().requires_grad_(True) for k, v in sd.items()}
     with torch.enable_grad():
@@ -99,6 +102,9 @@ def test_grads_vs_torch_port_autograd(A, h, w, s, B):
     # the flat bucket holds the same numbers in state_dict order (what the RCCL all-reduce sees)
     flat = torch.cat([p.grad.reshape(-1) for p in net.parameters()])
     assert torch.equal(flat, net.grad_bucket)
+    # arithmetic alone: under the HIP forward's own decisions every parameter holds rel-L2 < 1e-4 against fp64 (the gate of
+    # tests/test_gpu_distgssr_geometries.py, with its allowance for a cancelling sum: tests/helpers.py)
+    TH.distg_forced_gradient_gate(f"({A}, {s}, {B}, {h}, {w})", net, xg, sd, x, label_np, A, s, masks, (A, s, B, h, w))
 
 
 def test_train_step_matches_inference_forward():
