@@ -287,6 +287,16 @@ int lfsr_window_attn_fwd(const float* q, int q_stride, int q_choff, const float*
                          const float* v, int v_stride, int v_choff, float* o, int o_stride, int o_choff, int nheads, int hd,
                          int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
                          int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, void* stream);
+/* Backward of lfsr_window_attn_fwd, same geometry arguments.  q | k are columns q_choff / k_choff of one buffer of row stride qk_stride (as
+ * the in-projection writes them); o is the forward's output and d_o its gradient (one row stride and channel offset for both).  Writes dQ | dK
+ * into dqk in the layout of qk and dV into dv in the layout of v; nothing outside those nheads*hd-wide column ranges is touched.
+ * stats: scratch of 4 floats per (pixel, head) over the pixel span the sequences cover (the softmax statistics the VALU kernels pass from their
+ * query pass to their key pass; the matrix-pipe kernel of the EPI geometry recomputes them and leaves it alone).  No float atomics: two runs
+ * give the same bits. */
+int lfsr_window_attn_bwd(const float* qk, int qk_stride, int q_choff, int k_choff, const float* v, int v_stride, int v_choff,
+                         const float* o, const float* d_o, int o_stride, int o_choff, float* dqk, float* dv, float* stats,
+                         int nheads, int hd, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
+                         int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, void* stream);
 /* per-view 3x3 conv 64 -> N for any N (gather-GEMM): LFT's unfold(3x3) + Linear(576 -> 128) token embedding (LFT.py:176-182) */
 int lfsr_conv3x3_n_fwd(const float* x, int x_stride, int x_choff, const float* w_packed, float* y, int y_stride, int y_choff,
                        int n_img, int h, int w, int N, float slope, void* stream);
@@ -314,6 +324,26 @@ int lfsr_epit_finalize(lfsr_epit* ctx, void* stream);
 size_t lfsr_epit_workspace_bytes(const lfsr_epit* ctx, int B, int h, int w);
 int lfsr_epit_forward(lfsr_epit* ctx, const float* x, float* out, int B, int h, int w, void* workspace, size_t workspace_bytes,
                       void* stream);
+
+/* ---- EPIT training: the same contract as the LFT training ABI below.  Gradients go into ONE flat fp32 bucket in state_dict order (71 tensors at
+ * n_block = 5: an AltFilter's epi_trans and conv weights serve both of its passes and receive the sum of both contributions, in a fixed order);
+ * the feed-forward weights' pre-split image in the packed buffer is no parameter and lfsr_epit_param_offset refuses any key outside state_dict.
+ * forward_train = the inference forward's launches (bit-equal output) on buffers that keep every sublayer's input; a no-grad forward in the
+ * inference workspace leaves them in place.  train_workspace_bytes is 0 for a null context and outside the covered geometry (every activation,
+ * the 256-float q | k rows and the 64 s^2-float HR rows included, below 2 GiB). */
+size_t lfsr_epit_num_params(const lfsr_epit* ctx);
+int lfsr_epit_param_offset(const lfsr_epit* ctx, const char* key, size_t* offset, size_t* numel);
+size_t lfsr_epit_train_workspace_bytes(const lfsr_epit* ctx, int B, int h, int w);
+int lfsr_epit_forward_train(lfsr_epit* ctx, const float* x, float* out, int B, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
+/* Where in the training workspace a saved activation lies (floats from its base), VCL rows.  Pass index j = 2 * block + vertical.
+ * which: 0 the input of AltFilter `index` (64 floats a row; index = n_block: the tail's input), 1 conv_init's LeakyReLU outputs (index 0:
+ * conv_init.0, 1: conv_init.2; 64), 2 / 3 the LeakyReLU outputs of conv.0 / conv.2 of pass `index` (64).  After a backward, what it rebuilt and
+ * took its ReLU / LeakyReLU decisions from: 4 the feed-forward hidden rows after the ReLU of pass `index` (256), 5 conv_init.4's LeakyReLU
+ * output without the residual (64; index 0), 6 the HR pre-activation ((B, A h s, A w s, 64); index 0). */
+int lfsr_epit_train_saved(const lfsr_epit* ctx, int B, int h, int w, int which, int index, size_t* offset_floats, size_t* numel);
+/* dout (B,1,A*h*s,A*w*s) = dLoss/dOut; grads: n_grads == lfsr_epit_num_params(ctx) floats, overwritten */
+int lfsr_epit_backward(lfsr_epit* ctx, const float* x, const float* dout, int B, int h, int w, void* workspace, size_t workspace_bytes,
+                       float* grads, size_t n_grads, void* stream);
 
 /* Whole-model driver: LFT forward (get_model.forward, LFT.py:67-98). */
 typedef struct lfsr_lft lfsr_lft;

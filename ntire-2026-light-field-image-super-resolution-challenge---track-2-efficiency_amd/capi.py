@@ -57,6 +57,8 @@ SIGNATURES = {
     "lfsr_linear_ln_fwd": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_i, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_i, C.c_longlong, c_i, c_p]),
     "lfsr_window_attn_fwd": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
                                    C.c_longlong, C.c_longlong, C.c_longlong, c_i, c_i, C.c_longlong, C.c_longlong, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "lfsr_window_attn_bwd": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i,
+                                   C.c_longlong, C.c_longlong, C.c_longlong, c_i, c_i, C.c_longlong, C.c_longlong, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_upsample_ps_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_up_tail_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
     "lfsr_hr_tail_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
@@ -111,7 +113,7 @@ def _model_signatures(name, n_create_ints, trainable):
 
 
 # (model, ints lfsr_<model>_create takes after A and scale, trainable)
-_MODELS = (("distgssr", 3, True), ("internet", 2, True), ("lft", 2, True), ("epit", 2, False))
+_MODELS = (("distgssr", 3, True), ("internet", 2, True), ("lft", 2, True), ("epit", 2, True))
 for _m in _MODELS:
     SIGNATURES.update(_model_signatures(*_m))
 
@@ -383,7 +385,7 @@ class GraphedForward:
 
 # ---------------------------------------------------------------------------------------------------
 # whole-model runtimes: every model drives one C-ABI life cycle, lfsr_<name>_create / packed_bytes / set_packed / load_param /
-# finalize / workspace_bytes / forward; the trainable ones (distgssr, internet, lft) add num_params / param_offset /
+# finalize / workspace_bytes / forward; every one of them trainable: num_params / param_offset /
 # train_workspace_bytes / forward_train / train_saved / backward
 # ---------------------------------------------------------------------------------------------------
 

@@ -1,12 +1,7 @@
 // Host driver for the EPIT forward (get_model.forward, model/SR/EPIT.py:51-71; AltFilter :144-161; BasicTrans :110-128)
 // on VCL buffers.  Tokens are VCL pixels; the horizontal / vertical EPI passes differ only in the strides handed to the
 // attention kernel, so none of the reference's six `rearrange` copies per AltFilter exists here.
-#include "param_table.h"
-
-struct lfsr_epit : LfsrModel {
-  int nblk = 0;
-  std::vector<size_t> ffn_split;      // per block: offset (floats) of the feed-forward weights' pre-split bf16 image in the packed buffer (ffn_b3.hip)
-};
+#include "epit_ctx.h"
 
 extern "C" {
 
@@ -74,11 +69,30 @@ int lfsr_epit_forward(lfsr_epit* c, const float* x, float* out, int B, int h, in
   float* buf[14];
   epit_layout(c, B, h, w, ws, buf);
   if (workspace_bytes < ws.bytes()) return LFSR_E_WS;
-  const int A = c->A, AA = A * A, nimg = B * AA, HW = h * w;
-  const long long npix = (long long)nimg * HW;
+  const long long npix = (long long)B * c->A * c->A * h * w;
   if (npix * 256 * 4 >= (1LL << 31)) return LFSR_E_ARG;   // every activation tensor < 2 GiB (the q | k rows are the widest): the kernels' 32-bit byte offsets; callers split the batch (capi.py)
   float *F0 = buf[0], *BUF0 = buf[1], *Pb = buf[2], *Qb = buf[3], *MID = buf[4], *Y = buf[5], *C1 = buf[6], *C2 = buf[7];
   float *T = buf[8], *TN = buf[9], *V = buf[10], *T2 = buf[11], *QK = buf[12], *HR = buf[13];
+  // the aliasing of the buffers: the blocks ping-pong between Pb and Qb, every pass runs on the same token buffers
+  EpitFwdBufs bf;
+  bf.f0 = F0; bf.c1i = C1; bf.c2i = C2; bf.buf0 = BUF0; bf.tn = TN; bf.lnx = V; bf.hid = QK; bf.hr = HR;
+  bf.x.push_back(BUF0);
+  for (int b = 0; b < c->nblk; ++b) {
+    bf.mid.push_back(MID);
+    bf.x.push_back((bf.x[b] == Pb) ? Qb : Pb);
+    for (int vert = 0; vert < 2; ++vert) {
+      bf.t.push_back(T); bf.qk.push_back(QK); bf.v.push_back(V); bf.ao.push_back(TN); bf.t2.push_back(T2); bf.tf.push_back(T);
+      bf.y.push_back(Y); bf.c1.push_back(C1); bf.c2.push_back(C2);
+    }
+  }
+  return lfsr_epit_forward_body(c, x, out, B, h, w, bf, stream);
+}
+
+}  // extern "C"
+
+int lfsr_epit_forward_body(const lfsr_epit* c, const float* x, float* out, int B, int h, int w, const EpitFwdBufs& bf, void* stream) {
+  const int A = c->A, AA = A * A, nimg = B * AA, HW = h * w;
+  const long long npix = (long long)nimg * HW;
   const LfsrParamTable& P = c->P;
   const LfsrTransSel sel = lfsr_trans_sel();
   const float L = 0.2f;   // LeakyReLU(0.2), EPIT.py:27-31,138-140
@@ -86,36 +100,34 @@ int lfsr_epit_forward(lfsr_epit* c, const float* x, float* out, int B, int h, in
     return lfsr_conv3x3_fwd(in, 64, 0, P.w(key), o, 64, 0, r1, 64, 0, r2, 64, 0, nimg, h, w, slope, stream);
   };
   // BasicTrans.forward (EPIT.py:110-128) over all sequences of one pass
-  auto trans = [&](const float* X, const std::string& e, int vertical, float* Yo, int blk) -> int {
+  auto trans = [&](const float* X, const std::string& e, int vertical, int blk) -> int {
+    const int j = 2 * blk + vertical;
+    float *T = bf.t[j], *QK = bf.qk[j], *V = bf.v[j], *AO = bf.ao[j], *T2 = bf.t2[j], *TF = bf.tf[j];
     LFSR_RC(lfsr_linear_fwd(X, 64, 0, 64, P.w(e + "linear_in.weight"), nullptr, nullptr, 0, 0, T, 128, 0, npix, 128, 1.0f, stream));
-    LFSR_RC(lfsr_trans_qkv(sel, P, e, T, 128, nullptr, 1, 1, QK, V, TN, npix, stream));     // q | k from LayerNorm(t), v from t
+    LFSR_RC(lfsr_trans_qkv(sel, P, e, T, 128, nullptr, 1, 1, QK, V, bf.tn, npix, stream));     // q | k from LayerNorm(t), v from t
     // mask_field = [2A, 11] (EPIT.py:147): all angular positions, spatial window [j-5, j+6)
-    if (!vertical) LFSR_RC(lfsr_window_attn_fwd(QK, 256, 0, QK, 256, 128, V, 128, 0, TN, 128, 0, 8, 16, B, A, w, (long long)AA * HW, HW, 1,
+    if (!vertical) LFSR_RC(lfsr_window_attn_fwd(QK, 256, 0, QK, 256, 128, V, 128, 0, AO, 128, 0, 8, 16, B, A, w, (long long)AA * HW, HW, 1,
                                                 A, h, (long long)A * HW, w, A, A, 5, 6, 0, stream));      // sequence (b, v, x); tokens (u, y)
-    else LFSR_RC(lfsr_window_attn_fwd(QK, 256, 0, QK, 256, 128, V, 128, 0, TN, 128, 0, 8, 16, B, A, h, (long long)AA * HW, (long long)A * HW, w,
+    else LFSR_RC(lfsr_window_attn_fwd(QK, 256, 0, QK, 256, 128, V, 128, 0, AO, 128, 0, 8, 16, B, A, h, (long long)AA * HW, (long long)A * HW, w,
                                       A, w, HW, 1, A, A, 5, 6, 0, stream));                               // sequence (b, u, y); tokens (v, x)
-    LFSR_RC(lfsr_linear_fwd(TN, 128, 0, 128, P.w(e + "attention.out_proj.weight"), nullptr, T, 128, 0, T2, 128, 0, npix, 128, 1.0f, stream));
-    LFSR_RC(lfsr_trans_ffn(sel, P, e, T2, 128, c->ffn_split[blk], T, V, QK, npix, stream));
-    return lfsr_linear_fwd(T, 128, 0, 128, P.w(e + "linear_out.weight"), nullptr, nullptr, 0, 0, Yo, 64, 0, npix, 64, 1.0f, stream);
+    LFSR_RC(lfsr_linear_fwd(AO, 128, 0, 128, P.w(e + "attention.out_proj.weight"), nullptr, T, 128, 0, T2, 128, 0, npix, 128, 1.0f, stream));
+    LFSR_RC(lfsr_trans_ffn(sel, P, e, T2, 128, c->ffn_split[blk], TF, bf.lnx, bf.hid, npix, stream));
+    return lfsr_linear_fwd(TF, 128, 0, 128, P.w(e + "linear_out.weight"), nullptr, nullptr, 0, 0, bf.y[j], 64, 0, npix, 64, 1.0f, stream);
   };
 
-  LFSR_RC(lfsr_trans_head(P, x, F0, C1, C2, BUF0, B, A, h, w, stream));       // lrelu(conv) + buffer   (EPIT.py:63)
-  const float* cur = BUF0;
+  LFSR_RC(lfsr_trans_head(P, x, bf.f0, bf.c1i, bf.c2i, bf.buf0, B, A, h, w, stream));       // lrelu(conv) + buffer   (EPIT.py:63)
   for (int b = 0; b < c->nblk; ++b) {
     std::string p = "altblock." + std::to_string(b) + ".";
-    float* o = (cur == Pb) ? Qb : Pb;
+    const float* cur = bf.x[b];
     const bool last = b == c->nblk - 1;
     for (int vert = 0; vert < 2; ++vert) {
-      const float* in = vert ? MID : cur;
-      LFSR_RC(trans(in, p + "epi_trans.", vert, Y, b));
-      LFSR_RC(conv(Y, p + "conv.0.weight", C1, nullptr, nullptr, L));
-      LFSR_RC(conv(C1, p + "conv.2.weight", C2, nullptr, nullptr, L));
+      const int j = 2 * b + vert;
+      LFSR_RC(trans(vert ? bf.mid[b] : cur, p + "epi_trans.", vert, b));
+      LFSR_RC(conv(bf.y[j], p + "conv.0.weight", bf.c1[j], nullptr, nullptr, L));
+      LFSR_RC(conv(bf.c1[j], p + "conv.2.weight", bf.c2[j], nullptr, nullptr, L));
       // + shortcut (the block INPUT both times, EPIT.py:153,159); the network-level skip (:66) rides on the very last conv
-      LFSR_RC(conv(C2, p + "conv.4.weight", vert ? o : MID, cur, (vert && last) ? BUF0 : nullptr, 1.0f));
+      LFSR_RC(conv(bf.c2[j], p + "conv.4.weight", vert ? bf.x[b + 1] : bf.mid[b], cur, (vert && last) ? bf.buf0 : nullptr, 1.0f));
     }
-    cur = o;
   }
-  return lfsr_trans_tail(sel, P, cur, x, out, HR, B, A, h, w, c->s, stream);
+  return lfsr_trans_tail(sel, P, bf.x[c->nblk], x, out, bf.hr, B, A, h, w, c->s, stream);
 }
-
-}  // extern "C"

@@ -203,6 +203,26 @@ int lfsr_ffn_b3_presplit(const float* w1_packed, const float* w2_packed, int K1,
 int lfsr_epi_attn_mfma_launch(const float* q, int q_stride, int q_choff, const float* k, int k_stride, int k_choff, const float* v, int v_stride, int v_choff,
                               float* o, int o_stride, int o_choff, int nheads, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
                               int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, hipStream_t st);
+// trans_bwd.hip: what the backward drivers of LFT and EPIT share.  LFSR_RED_BLOCKS: the fixed grid of the kernels that write per-block partials (a fixed order for every geometry)
+#define LFSR_RED_BLOCKS 1024
+// d = (a (+ b)) * (mk > 0 ? 1 : slope) over C columns (C % 4 == 0); b, mk optional; a and d may alias
+int lfsr_ew_launch(const float* a, int as, const float* b, int bs, const float* mk, int ms, float slope, float* d, int ds, int C, long long M, hipStream_t st);
+// LayerNorm backward of y = LN(x + pe) gamma + beta on dense rows of C in {64, 128}: dx = ... (+ r; r may alias dx), dgamma, dbeta; part: LFSR_RED_BLOCKS * 2 C floats
+int lfsr_ln_bwd_launch(int C, const float* x, const float* pe, long long pe_rows, long long pe_div, const float* gamma, const float* dy, const float* r,
+                       float* dx, float* part, long long M, float* dgamma, float* dbeta, hipStream_t st);
+// the up-sampling tail's LeakyReLU / 3x3 conv 64 -> 1 backward: du = the un-shuffled gradient of upsampling.0's output, dw3; part: LFSR_RED_BLOCKS * 576 floats
+int lfsr_tail_bwd_launch(const float* dout, const float* w3, const float* hr, float* du, float* part, float* dw3, int B, int A, int h, int w, int S, float slope,
+                         hipStream_t st);
+int lfsr_pack_up0_T_launch(const float* Wp, float* out, int s2, hipStream_t st);   // dgrad pack of upsampling.0 from its forward (perm 1) pack
+// the windowed attention backward on the VALU, any geometry of lfsr_window_attn_fwd (q | k in one buffer; O and dO share a row stride; v / o / dO / dv
+// point at their first channel).  Two gathers, one thread per (query, head) and one per (key, head); stats: 4 floats per (pixel, head) of the span the sequences cover
+int lfsr_attn_bwd_valu_launch(int hd, const float* qk, int qk_stride, int q_choff, int k_choff, const float* v, int v_stride, const float* o, const float* d_o,
+                              int o_stride, float* dqk, float* dv, float* stats, int nheads, int ns0, int ns1, int ns2, long long bs0, long long bs1,
+                              long long bs2, int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, hipStream_t st);
+// attn_bwd_mfma.hip: the EPI attention backward on MFMA (heads of 16); LFSR_E_ARG = geometry not covered
+int lfsr_epi_attn_bwd_mfma_launch(const float* qk, int qk_stride, int q_choff, int k_choff, const float* v, int v_stride, const float* o, const float* d_o,
+                                  int o_stride, float* dqk, float* dv, int nheads, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
+                                  int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, hipStream_t st);
 // win_attn_mfma.hip: 5 x 5 spatial window attention (LFT) on the matrix pipe; LFSR_E_ARG = geometry not covered
 int lfsr_win_attn_mfma_launch(const float* q, int q_stride, int q_choff, const float* k, int k_stride, int k_choff, const float* v, int v_stride, int v_choff,
                               float* o, int o_stride, int o_choff, int nheads, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,

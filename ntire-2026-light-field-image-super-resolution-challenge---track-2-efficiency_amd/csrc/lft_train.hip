@@ -6,9 +6,10 @@
 // statistics, feed-forward hidden rows or HR map: the backward recomputes those from the saved sublayer inputs with the unfused kernels.
 //
 // Backward: data gradients are gather-GEMMs over transposed packs (gemm_gather_kernel.h) and the 64 -> 64 3x3 data-gradient kernel;
-// weight gradients are the two-pass partial-slab reduction of wgrad.hip.  New kernels: the windowed attention backward (two gathers, one
-// per query and one per key: no float atomics), the LayerNorm backward with the position embedding added to its input, the tail's
-// LeakyReLU / 3x3 conv backward with the HR -> LR un-shuffle, and small fixed-order reductions.  Buckets are bitwise reproducible.
+// weight gradients are the two-pass partial-slab reduction of wgrad.hip.  The windowed attention backward (two gathers, one per query and one
+// per key: no float atomics), the LayerNorm backward with the position embedding added to its input, the tail's LeakyReLU / 3x3 conv backward
+// with the HR -> LR un-shuffle and the small fixed-order reductions are the kernels of trans_bwd.hip, which EPIT's backward shares.  Buckets
+// are bitwise reproducible.
 #include <string>
 #include <vector>
 
@@ -17,102 +18,6 @@
 
 namespace {
 
-inline unsigned cap_grid(long long total, unsigned cap = 8192) {
-  unsigned g = lfsr_blocks(total, 256);
-  return g > cap ? cap : g;
-}
-
-constexpr int RED_BLOCKS = 1024;   // fixed grid of the kernels that write per-block partials (a fixed order for every geometry)
-
-// d = (a (+ b)) * (mk > 0 ? 1 : slope)  over C columns (C % 4 == 0); b, mk optional; a and d may alias
-__global__ __launch_bounds__(256) void k_ew(const float* a, int as, const float* __restrict__ b, int bs, const float* __restrict__ mk, int ms, float slope,
-                                            float* d, int ds, int C, long long M) {
-  const int c4n = C / 4;
-  for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < M * c4n; g += (long long)gridDim.x * 256) {
-    const long long r = g / c4n;
-    const int c = (int)(g - r * c4n) * 4;
-    float4 v = *reinterpret_cast<const float4*>(a + r * as + c);
-    if (b) {
-      const float4 u = *reinterpret_cast<const float4*>(b + r * bs + c);
-      v.x += u.x; v.y += u.y; v.z += u.z; v.w += u.w;
-    }
-    if (mk) {
-      const float4 m = *reinterpret_cast<const float4*>(mk + r * ms + c);
-      v.x = m.x > 0.f ? v.x : v.x * slope; v.y = m.y > 0.f ? v.y : v.y * slope; v.z = m.z > 0.f ? v.z : v.z * slope; v.w = m.w > 0.f ? v.w : v.w * slope;
-    }
-    *reinterpret_cast<float4*>(d + r * ds + c) = v;
-  }
-}
-
-// out[j] = sum over blocks b < nb of part[b * stride + j] (j < ncol): 32 columns per block, eight groups of threads each summing every
-// eighth block in order (fp64), then the eight group sums in order -- a fixed order for a given nb
-__global__ __launch_bounds__(256) void k_colsum(const float* __restrict__ part, int nb, int stride, int ncol, float* __restrict__ out) {
-  __shared__ double red[8][32];
-  const int jl = threadIdx.x & 31, g = threadIdx.x >> 5, j = blockIdx.x * 32 + jl;
-  double s = 0.0;
-  if (j < ncol)
-    for (int b = g; b < nb; b += 8) s += (double)part[(long long)b * stride + j];
-  red[g][jl] = s;
-  __syncthreads();
-  if (g == 0 && j < ncol) {
-    for (int q = 1; q < 8; ++q) s += red[q][jl];
-    out[j] = (float)s;
-  }
-}
-
-// LayerNorm backward, y = LN(x + pe) * g + beta (pe row = (row / pe_div) % pe_rows, as k_layernorm reads it):
-//   dx = rstd (dy g - mean(dy g) - xhat mean(dy g xhat)) (+ r)      r may alias dx
-// and per-block partials part[block][0:C] = sum dy xhat (dgamma), part[block][C:2C] = sum dy (dbeta) over the block's rows.
-template <int C>
-__global__ __launch_bounds__(256) void k_ln_bwd(const float* __restrict__ x, int x_stride, const float* __restrict__ pe, int pe_stride, long long pe_rows,
-                                                long long pe_div, const float* __restrict__ g, const float* __restrict__ dy, int dy_stride,
-                                                const float* r, int r_stride, float* dx, int dx_stride, float* __restrict__ part, long long M, float eps) {
-  constexpr int LPR = C / 4, RPB = 256 / LPR;
-  __shared__ float red[RPB][2 * C];
-  const int lr = threadIdx.x % LPR, rr = threadIdx.x / LPR;
-  const float4 gv = *reinterpret_cast<const float4*>(g + lr * 4);
-  float4 dg = make_float4(0.f, 0.f, 0.f, 0.f), db = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (long long row = (long long)blockIdx.x * RPB + rr; row < M; row += (long long)gridDim.x * RPB) {
-    float4 v = *reinterpret_cast<const float4*>(x + row * x_stride + lr * 4);
-    if (pe) {
-      const float4 q = *reinterpret_cast<const float4*>(pe + ((row / pe_div) % pe_rows) * pe_stride + lr * 4);
-      v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
-    }
-    float s = v.x + v.y + v.z + v.w;
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, LPR);
-    const float mu = s * (1.0f / C);
-    const float ex = v.x - mu, ey = v.y - mu, ez = v.z - mu, ew = v.w - mu;
-    float q2 = ex * ex + ey * ey + ez * ez + ew * ew;
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) q2 += __shfl_xor(q2, o, LPR);
-    const float rstd = 1.0f / sqrtf(q2 * (1.0f / C) + eps);
-    const float hx = ex * rstd, hy = ey * rstd, hz = ez * rstd, hw = ew * rstd;
-    const float4 d = *reinterpret_cast<const float4*>(dy + row * dy_stride + lr * 4);
-    dg.x += d.x * hx; dg.y += d.y * hy; dg.z += d.z * hz; dg.w += d.w * hw;
-    db.x += d.x; db.y += d.y; db.z += d.z; db.w += d.w;
-    const float gx = d.x * gv.x, gy = d.y * gv.y, gz = d.z * gv.z, gw = d.w * gv.w;
-    float sg = gx + gy + gz + gw, sgx = gx * hx + gy * hy + gz * hz + gw * hw;
-#pragma unroll
-    for (int o = LPR / 2; o > 0; o >>= 1) { sg += __shfl_xor(sg, o, LPR); sgx += __shfl_xor(sgx, o, LPR); }
-    const float mg = sg * (1.0f / C), mgx = sgx * (1.0f / C);
-    float4 o4 = make_float4(rstd * (gx - mg - hx * mgx), rstd * (gy - mg - hy * mgx), rstd * (gz - mg - hz * mgx), rstd * (gw - mg - hw * mgx));
-    if (r) {
-      const float4 rv = *reinterpret_cast<const float4*>(r + row * r_stride + lr * 4);
-      o4.x += rv.x; o4.y += rv.y; o4.z += rv.z; o4.w += rv.w;
-    }
-    *reinterpret_cast<float4*>(dx + row * dx_stride + lr * 4) = o4;
-  }
-  red[rr][lr * 4] = dg.x; red[rr][lr * 4 + 1] = dg.y; red[rr][lr * 4 + 2] = dg.z; red[rr][lr * 4 + 3] = dg.w;
-  red[rr][C + lr * 4] = db.x; red[rr][C + lr * 4 + 1] = db.y; red[rr][C + lr * 4 + 2] = db.z; red[rr][C + lr * 4 + 3] = db.w;
-  __syncthreads();
-  for (int j = threadIdx.x; j < 2 * C; j += 256) {
-    float s = 0.f;
-    for (int q = 0; q < RPB; ++q) s += red[q][j];
-    part[(long long)blockIdx.x * 2 * C + j] = s;
-  }
-}
-
 // dspe[p][c] = sum over the n_img images of dln[img * HW + p][c] (128 channels), in image order
 __global__ __launch_bounds__(256) void k_pe_reduce(const float* __restrict__ dln, float* __restrict__ dspe, int n_img, int HW) {
   const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -120,213 +25,6 @@ __global__ __launch_bounds__(256) void k_pe_reduce(const float* __restrict__ dln
   float s = 0.f;
   for (int i = 0; i < n_img; ++i) s += dln[(long long)i * HW * 128 + e];
   dspe[e] = s;
-}
-
-// dgrad pack of upsampling.0 with the rows in PyTorch order: out[k][c s2 + ij] = Wp[ij * 64 + c][k] (Wp: the forward's perm-1 pack, 64 s2 rows of 64)
-__global__ __launch_bounds__(256) void k_pack_up0_T(const float* __restrict__ Wp, float* __restrict__ out, int s2) {
-  const int i = blockIdx.x * 256 + threadIdx.x;   // over 64 * 64 s2
-  const int N = 64 * s2;
-  if (i >= 64 * N) return;
-  const int n = i % N, k = i / N, c = n / s2, ij = n - c * s2;
-  out[i] = Wp[(ij * 64 + c) * 64 + k];
-}
-
-// Tail backward: out = conv3x3(lrelu(HR), w3) + skip on the HR mosaic, HR = PixelShuffle(upsampling.0(f)) channel-last (B, A h s, A w s, 64).
-// One thread per (LR VCL pixel p, channel c), walking the s^2 HR pixels of p:
-//   dU[p][c s2 + ij] = (sum_t dout[P - off_t] w3[c][t]) * lrelu'(HR[P][c])       (the un-shuffled gradient of upsampling.0's output)
-//   dw3[c][t] += lrelu(HR[P][c]) * dout[P - off_t]                               (per-block partials part[block][c * 9 + t])
-__global__ __launch_bounds__(256) void k_tail_bwd(const float* __restrict__ dout, const float* __restrict__ w3, const float* __restrict__ hr,
-                                                  float* __restrict__ du, float* __restrict__ part, int B, int A, int h, int w, int S, float slope) {
-  __shared__ float red[4][9 * 64];
-  const int c = threadIdx.x & 63, pl = threadIdx.x >> 6;
-  float wc[9], acc[9];
-#pragma unroll
-  for (int t = 0; t < 9; ++t) { wc[t] = w3[c * 9 + t]; acc[t] = 0.f; }
-  const int s2 = S * S, AA = A * A;
-  const long long npix = (long long)B * AA * h * w;
-  const int Hs = A * h * S, Ws = A * w * S;
-  for (long long p = (long long)blockIdx.x * 4 + pl; p < npix; p += (long long)gridDim.x * 4) {
-    const int x = (int)(p % w);
-    long long t = p / w;
-    const int y = (int)(t % h);
-    t /= h;
-    const int view = (int)(t % AA);
-    const long long b = t / AA;
-    const int u = view / A, v = view - u * A;
-    float dv[16];                                      // s^2 <= 16: the thread's s^2 outputs, stored together
-#pragma unroll
-    for (int ij = 0; ij < 16; ++ij) {
-      if (ij >= s2) continue;
-      const int i = ij / S, j = ij - i * S;
-      const int Y = (u * h + y) * S + i, X = (v * w + x) * S + j;
-      const float* dplane = dout + b * Hs * Ws;
-      float d[9];
-#pragma unroll
-      for (int tp = 0; tp < 9; ++tp) {
-        const int yy = Y - (tp / 3 - 1), xx = X - (tp % 3 - 1);
-        d[tp] = (yy >= 0 && yy < Hs && xx >= 0 && xx < Ws) ? dplane[(long long)yy * Ws + xx] : 0.f;
-      }
-      const float z = hr[((b * Hs + Y) * Ws + X) * 64 + c];
-      const float act = z >= 0.f ? z : z * slope;      // as k_hr_tail forms it
-      float da = 0.f;
-#pragma unroll
-      for (int tp = 0; tp < 9; ++tp) { da = fmaf(d[tp], wc[tp], da); acc[tp] = fmaf(act, d[tp], acc[tp]); }
-      dv[ij] = z > 0.f ? da : da * slope;
-    }
-    float* dst = du + p * 64 * s2 + c * s2;
-    if ((s2 & 3) == 0) {
-#pragma unroll
-      for (int q = 0; q < 16; q += 4)
-        if (q < s2) *reinterpret_cast<float4*>(dst + q) = make_float4(dv[q], dv[q + 1], dv[q + 2], dv[q + 3]);
-    } else {
-#pragma unroll
-      for (int q = 0; q < 16; ++q)
-        if (q < s2) dst[q] = dv[q];
-    }
-  }
-#pragma unroll
-  for (int tp = 0; tp < 9; ++tp) red[pl][c * 9 + tp] = acc[tp];
-  __syncthreads();
-  for (int jj = threadIdx.x; jj < 9 * 64; jj += 256) part[(long long)blockIdx.x * 9 * 64 + jj] = ((red[0][jj] + red[1][jj]) + red[2][jj]) + red[3][jj];
-}
-
-// ---- windowed attention backward ---------------------------------------------------------------------------------------------------
-// The stride / window parametrisation of lfsr_window_attn_fwd: sequences (s0,s1,s2) start at pixel s0 bs0 + s1 bs1 + s2 bs2, token (t1,t2)
-// sits at + t1 st1 + t2 st2 and attends keys [t1-l1, t1+r1) x [t2-l2, min(t2+r2, clip2, n2)).  P is recomputed from the saved q | k.
-struct AttnBwdArgs {
-  const float* Q; const float* K; int qk_stride, q_choff, k_choff;     // q and k in one buffer (the forward's q | k rows)
-  const float* V; int v_stride;
-  const float* O; const float* dO; int o_stride;                       // O and dO share a row stride
-  float* dQK; float* dV;                                               // dQK: the layout of q | k; dV: the layout of V
-  float4* stats;                                                       // per (query pixel, head): row max, 1 / denominator, rowsum(dO o O)
-  int nheads;
-  int ns1, ns2; long long bs0, bs1, bs2;
-  int n1, n2; long long st1, st2;
-  int l1, r1, l2, r2, clip2;
-  float scale;
-  long long total;
-};
-
-struct TokenPos { long long base; int t1, t2, head; };
-
-__device__ __forceinline__ TokenPos attn_token(long long idx, const AttnBwdArgs& p) {
-  TokenPos r;
-  r.head = (int)(idx % p.nheads);
-  long long t = idx / p.nheads;
-  r.t2 = (int)(t % p.n2); t /= p.n2;
-  r.t1 = (int)(t % p.n1); t /= p.n1;
-  const int s2 = (int)(t % p.ns2); t /= p.ns2;
-  const int s1 = (int)(t % p.ns1);
-  const long long s0 = t / p.ns1;
-  r.base = s0 * p.bs0 + s1 * p.bs1 + s2 * p.bs2;
-  return r;
-}
-
-template <int HD>
-__device__ __forceinline__ void load_row(const float* src, float (&v)[HD], float mul = 1.0f) {
-  const float4* q = reinterpret_cast<const float4*>(src);
-#pragma unroll
-  for (int i = 0; i < HD / 4; ++i) {
-    const float4 a = q[i];
-    v[4 * i] = a.x * mul; v[4 * i + 1] = a.y * mul; v[4 * i + 2] = a.z * mul; v[4 * i + 3] = a.w * mul;
-  }
-}
-
-template <int HD>
-__device__ __forceinline__ float dot(const float (&a)[HD], const float* b) {
-  const float4* q = reinterpret_cast<const float4*>(b);
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < HD / 4; ++i) {
-    const float4 v = q[i];
-    s = fmaf(a[4 * i], v.x, s); s = fmaf(a[4 * i + 1], v.y, s); s = fmaf(a[4 * i + 2], v.z, s); s = fmaf(a[4 * i + 3], v.w, s);
-  }
-  return s;
-}
-
-// pass 1, one thread per (query, head): the softmax statistics, D = rowsum(dO o O) and dQ = scale sum_k P (dP - D) k
-template <int HD>
-__global__ __launch_bounds__(256) void k_attn_bwd_q(AttnBwdArgs p) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.total) return;
-  const TokenPos tp = attn_token(idx, p);
-  const long long qpix = tp.base + tp.t1 * p.st1 + tp.t2 * p.st2;
-  const int hc = tp.head * HD;
-  float q[HD], dO[HD], o[HD], dq[HD];
-  load_row<HD>(p.Q + qpix * p.qk_stride + p.q_choff + hc, q, p.scale);
-  load_row<HD>(p.dO + qpix * p.o_stride + hc, dO);
-  load_row<HD>(p.O + qpix * p.o_stride + hc, o);
-  float D = 0.f;
-#pragma unroll
-  for (int i = 0; i < HD; ++i) { D = fmaf(dO[i], o[i], D); dq[i] = 0.f; }
-  const int a0 = max(0, tp.t1 - p.l1), a1 = min(p.n1, tp.t1 + p.r1);
-  const int b0 = max(0, tp.t2 - p.l2), b1 = min(min(p.n2, p.clip2), tp.t2 + p.r2);
-  float mx = -INFINITY, den = 0.f;     // the softmax statistics in one pass, as the forward forms them
-  for (int k1 = a0; k1 < a1; ++k1)
-    for (int k2 = b0; k2 < b1; ++k2) {
-      const float sc = dot<HD>(q, p.K + (tp.base + k1 * p.st1 + k2 * p.st2) * p.qk_stride + p.k_choff + hc);
-      const float mn = fmaxf(mx, sc);
-      den = den * expf(mx - mn) + expf(sc - mn);
-      mx = mn;
-    }
-  const float inv = 1.0f / den;
-  for (int k1 = a0; k1 < a1; ++k1)
-    for (int k2 = b0; k2 < b1; ++k2) {
-      const long long kpix = tp.base + k1 * p.st1 + k2 * p.st2;
-      const float* kr = p.K + kpix * p.qk_stride + p.k_choff + hc;
-      const float pr = expf(dot<HD>(q, kr) - mx) * inv;
-      const float ds = pr * (dot<HD>(dO, p.V + kpix * p.v_stride + hc) - D);
-      float kv[HD];
-      load_row<HD>(kr, kv);
-#pragma unroll
-      for (int i = 0; i < HD; ++i) dq[i] = fmaf(ds, kv[i], dq[i]);
-    }
-  float4* dst = reinterpret_cast<float4*>(p.dQK + qpix * p.qk_stride + p.q_choff + hc);
-#pragma unroll
-  for (int i = 0; i < HD / 4; ++i) dst[i] = make_float4(dq[4 * i] * p.scale, dq[4 * i + 1] * p.scale, dq[4 * i + 2] * p.scale, dq[4 * i + 3] * p.scale);
-  p.stats[qpix * p.nheads + tp.head] = make_float4(mx, inv, D, 0.f);
-}
-
-// pass 2, one thread per (key, head): gathers over the queries whose window holds the key
-//   dK = scale sum_q P (dP - D) q,   dV = sum_q P dO
-template <int HD>
-__global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnBwdArgs p) {
-  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.total) return;
-  const TokenPos tp = attn_token(idx, p);
-  const long long kpix = tp.base + tp.t1 * p.st1 + tp.t2 * p.st2;
-  const int hc = tp.head * HD;
-  float k[HD], v[HD], dk[HD], dv[HD];
-  load_row<HD>(p.K + kpix * p.qk_stride + p.k_choff + hc, k);
-  load_row<HD>(p.V + kpix * p.v_stride + hc, v);
-#pragma unroll
-  for (int i = 0; i < HD; ++i) { dk[i] = 0.f; dv[i] = 0.f; }
-  const int c1 = min(p.n1, tp.t1 + p.l1 + 1), c2 = min(p.n2, tp.t2 + p.l2 + 1);
-  for (int q1 = max(0, tp.t1 - p.r1 + 1); q1 < c1; ++q1) {
-    if (tp.t1 < q1 - p.l1 || tp.t1 >= min(p.n1, q1 + p.r1)) continue;
-    for (int q2 = max(0, tp.t2 - p.r2 + 1); q2 < c2; ++q2) {
-      if (tp.t2 < q2 - p.l2 || tp.t2 >= min(min(p.n2, p.clip2), q2 + p.r2)) continue;
-      const long long qpix = tp.base + q1 * p.st1 + q2 * p.st2;
-      float q[HD], dO[HD];
-      load_row<HD>(p.Q + qpix * p.qk_stride + p.q_choff + hc, q, p.scale);
-      load_row<HD>(p.dO + qpix * p.o_stride + hc, dO);
-      const float4 sv = p.stats[qpix * p.nheads + tp.head];
-      float s = 0.f, dp = 0.f;
-#pragma unroll
-      for (int i = 0; i < HD; ++i) { s = fmaf(q[i], k[i], s); dp = fmaf(dO[i], v[i], dp); }
-      const float pr = expf(s - sv.x) * sv.y;
-      const float ds = pr * (dp - sv.z);
-#pragma unroll
-      for (int i = 0; i < HD; ++i) { dk[i] = fmaf(ds, q[i], dk[i]); dv[i] = fmaf(pr, dO[i], dv[i]); }
-    }
-  }
-  float4* dkp = reinterpret_cast<float4*>(p.dQK + kpix * p.qk_stride + p.k_choff + hc);
-  float4* dvp = reinterpret_cast<float4*>(p.dV + kpix * p.v_stride + hc);
-#pragma unroll
-  for (int i = 0; i < HD / 4; ++i) {
-    dkp[i] = make_float4(dk[4 * i], dk[4 * i + 1], dk[4 * i + 2], dk[4 * i + 3]);     // q was scaled on load
-    dvp[i] = make_float4(dv[4 * i], dv[4 * i + 1], dv[4 * i + 2], dv[4 * i + 3]);
-  }
 }
 
 // ---- workspace ------------------------------------------------------------------------------------------------------------------
@@ -387,7 +85,7 @@ void train_layout(const lfsr_lft* c, int B, int h, int w, LfsrArena& ws, LftTrai
   t.stats = reinterpret_cast<float4*>(ws.take(npix * 8 * 4));
   t.hid_a.clear(); t.hid_s.clear();
   for (int b = 0; b < nl; ++b) { t.hid_a.push_back(ws.take(npix * 128)); t.hid_s.push_back(ws.take(npix * 256)); }
-  t.part = ws.take(wgrad_partial_max(B, c->A, h, w)); t.pln = ws.take((size_t)RED_BLOCKS * 256); t.ptail = ws.take((size_t)RED_BLOCKS * 9 * 64);
+  t.part = ws.take(wgrad_partial_max(B, c->A, h, w)); t.pln = ws.take((size_t)LFSR_RED_BLOCKS * 256); t.ptail = ws.take((size_t)LFSR_RED_BLOCKS * 9 * 64);
   // the forward body's scratch (unfused LayerNorm outputs, two-launch feed-forward hidden rows, the unfused tail's HR map)
   f.n64 = t.t64; f.tn = t.lnt; f.lnf = t.dln2; f.ha = t.dh; f.hs = t.hid; f.hr = t.hr;
   t.up0T = ws.take((size_t)64 * 64 * s2);
@@ -495,42 +193,18 @@ int lfsr_lft_backward(lfsr_lft* c, const float* x, const float* dout, int B, int
     return LFSR_OK;
   };
   auto ew = [&](const float* a, int as, const float* b, int bs, const float* mk, int ms, float slope, float* d, int ds, int C, long long M) -> int {
-    hipLaunchKernelGGL(k_ew, dim3(cap_grid(M * C / 4)), dim3(256), 0, st, a, as, b, bs, mk, ms, slope, d, ds, C, M);
-    return launched();
+    return lfsr_ew_launch(a, as, b, bs, mk, ms, slope, d, ds, C, M, st);
   };
   // LayerNorm backward with the gradients of its affine parameters written to dg / dbeta
   auto ln_bwd = [&](int C, const float* X, const float* pe, long long pe_rows, long long pe_div, const std::string& gkey, const std::string& bkey,
                     const float* dy, const float* r, float* dxo) -> int {
-    const int rpb = 256 / (C / 4);
-    unsigned nb = lfsr_blocks(npix, rpb);
-    if (nb > RED_BLOCKS) nb = RED_BLOCKS;
-    if (C == 64)
-      hipLaunchKernelGGL(k_ln_bwd<64>, dim3(nb), dim3(256), 0, st, X, 64, pe, 64, pe_rows, pe_div, P.w(gkey), dy, 64, r, 64, dxo, 64, t.pln, (long long)npix, 1e-5f);
-    else
-      hipLaunchKernelGGL(k_ln_bwd<128>, dim3(nb), dim3(256), 0, st, X, 128, pe, 128, pe_rows, pe_div, P.w(gkey), dy, 128, r, 128, dxo, 128, t.pln, (long long)npix, 1e-5f);
-    LFSR_RC(launched());
-    hipLaunchKernelGGL(k_colsum, dim3(C / 32), dim3(256), 0, st, t.pln, (int)nb, 2 * C, C, G(gkey));
-    LFSR_RC(launched());
-    hipLaunchKernelGGL(k_colsum, dim3(C / 32), dim3(256), 0, st, t.pln + C, (int)nb, 2 * C, C, G(bkey));
-    return launched();
+    return lfsr_ln_bwd_launch(C, X, pe, pe_rows, pe_div, P.w(gkey), dy, r, dxo, t.pln, npix, G(gkey), G(bkey), st);
   };
   auto attn_bwd = [&](int hd, const float* qk, int qks, int kchoff, const float* V, int vs, const float* O, const float* dO, int os, float* dqk, float* dv,
                       int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2, int n1, int n2, long long st1, long long st2,
                       int l1, int r1, int l2, int r2, int clip2) -> int {
-    AttnBwdArgs p{};
-    p.Q = qk; p.K = qk; p.qk_stride = qks; p.q_choff = 0; p.k_choff = kchoff; p.V = V; p.v_stride = vs; p.O = O; p.dO = dO; p.o_stride = os;
-    p.dQK = dqk; p.dV = dv; p.stats = t.stats; p.nheads = 8;
-    p.ns1 = ns1; p.ns2 = ns2; p.bs0 = bs0; p.bs1 = bs1; p.bs2 = bs2; p.n1 = n1; p.n2 = n2; p.st1 = st1; p.st2 = st2;
-    p.l1 = l1; p.r1 = r1; p.l2 = l2; p.r2 = r2; p.clip2 = clip2 > 0 ? clip2 : n2;
-    p.scale = 1.0f / sqrtf((float)hd);
-    p.total = (long long)ns0 * ns1 * ns2 * n1 * n2 * 8;
-    const unsigned grid = lfsr_blocks(p.total, 256);
-    if (hd == 8) hipLaunchKernelGGL(k_attn_bwd_q<8>, dim3(grid), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(k_attn_bwd_q<16>, dim3(grid), dim3(256), 0, st, p);
-    LFSR_RC(launched());
-    if (hd == 8) hipLaunchKernelGGL(k_attn_bwd_kv<8>, dim3(grid), dim3(256), 0, st, p);
-    else hipLaunchKernelGGL(k_attn_bwd_kv<16>, dim3(grid), dim3(256), 0, st, p);
-    return launched();
+    return lfsr_attn_bwd_valu_launch(hd, qk, qks, 0, kchoff, V, vs, O, dO, os, dqk, dv, reinterpret_cast<float*>(t.stats), 8, ns0, ns1, ns2, bs0, bs1, bs2,
+                                     n1, n2, st1, st2, l1, r1, l2, r2, clip2, st);
   };
   auto dgrad3 = [&](const float* dy, int dys, int dyo, const float* wT, float* dxo, const float* r1, const float* mk) -> int {
     return lfsr_conv3x3_bwd_data(dy, dys, dyo, wT, dxo, 64, 0, r1, 64, 0, mk, 64, 0, L, nimg, h, w, st);
@@ -544,16 +218,8 @@ int lfsr_lft_backward(lfsr_lft* c, const float* x, const float* dout, int B, int
 
   // ---- tail: upsampling.0 (1x1 64 -> 64 s^2), PixelShuffle(s), LeakyReLU 0.2, 3x3 conv 64 -> 1, + bicubic skip (no parameters) ----------
   LFSR_RC(lfsr_upsample_ps_fwd(f.x[nl], 64, 0, P.w("upsampling.0.weight"), t.hr, B, A, h, w, S, stream));   // the HR pre-activation, rebuilt
-  {
-    unsigned nb = lfsr_blocks(npix, 4);
-    if (nb > RED_BLOCKS) nb = RED_BLOCKS;
-    hipLaunchKernelGGL(k_tail_bwd, dim3(nb), dim3(256), 0, st, dout, P.w("upsampling.3.weight"), t.hr, t.du, t.ptail, B, A, h, w, S, L);
-    LFSR_RC(launched());
-    hipLaunchKernelGGL(k_colsum, dim3(9 * 64 / 32), dim3(256), 0, st, t.ptail, (int)nb, 9 * 64, 9 * 64, G("upsampling.3.weight"));
-    LFSR_RC(launched());
-  }
-  hipLaunchKernelGGL(k_pack_up0_T, dim3((64 * 64 * s2 + 255) / 256), dim3(256), 0, st, P.w("upsampling.0.weight"), t.up0T, s2);
-  LFSR_RC(launched());
+  LFSR_RC(lfsr_tail_bwd_launch(dout, P.w("upsampling.3.weight"), t.hr, t.du, t.ptail, G("upsampling.3.weight"), B, A, h, w, S, L, st));
+  LFSR_RC(lfsr_pack_up0_T_launch(P.w("upsampling.0.weight"), t.up0T, s2, st));
   float* dX = t.dx[0];   // the gradient at the altblock output (+ its skip): dL/d x[nl]
   if (s2 == 4) LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 256, 2>, t.du, 256, t.up0T, dX, 64, nullptr, 0, nullptr, 0, 64));
   else if (s2 == 9) LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 576, 2>, t.du, 576, t.up0T, dX, 64, nullptr, 0, nullptr, 0, 64));

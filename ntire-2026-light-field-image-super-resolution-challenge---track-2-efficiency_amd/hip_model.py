@@ -55,11 +55,9 @@ class _HipModelFunction(torch.autograd.Function):
 
 class HipModel(nn.Module):
     """Base of a plugin's ``get_model``: owns the runtime (``_rt``), its repack key and the dispatch of ``forward``.
-    A subclass builds its module tree after ``super().__init__()`` and implements ``_new_runtime``; ``inference_only`` set to a
-    reason makes a forward with grad enabled raise ``NotImplementedError`` with it."""
+    A subclass builds its module tree after ``super().__init__()`` and implements ``_new_runtime``."""
 
     hip_name = None           # the model's name in error texts
-    inference_only = None
 
     def __init__(self):
         super().__init__()
@@ -101,7 +99,5 @@ class HipModel(nn.Module):
         if not x.is_cuda:
             raise capi.LfsrError(f"{self.hip_name}: input must live on the MI355X (no CPU fallback in the HIP path)")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            if self.inference_only:
-                raise NotImplementedError(self.inference_only)
             return _HipModelFunction.apply(self, x.float(), *self.parameters())      # train.py:257
         return self._runtime(x.device).forward(x.float())

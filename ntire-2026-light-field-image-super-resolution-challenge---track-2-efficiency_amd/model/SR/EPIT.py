@@ -1,7 +1,7 @@
 """EPIT plugin (drop-in for the reference's ``model/SR/EPIT.py``): ``get_model`` / ``get_loss`` / ``weights_init`` with the
-reference's state_dict key names and shapes; ``forward`` runs in the gfx950 HIP library through the C ABI.
-Inference only -- the reference's own ``get_loss`` indexes ``out['SR']`` on a tensor (EPIT.py:178), i.e. EPIT training is
-broken upstream, and configs name EPIT for inference."""
+reference's state_dict key names and shapes; ``forward`` runs in the gfx950 HIP library through the C ABI, and
+with grad enabled so does the backward (lfsr_amd.hip_model).  The model trains; only the reference's own ``get_loss`` is broken
+(it indexes ``out['SR']`` on a tensor, EPIT.py:178) and is kept verbatim here: callers pass a criterion of their own."""
 import math
 
 import torch
@@ -41,7 +41,6 @@ class _AltFilter(_Holder):
 
 class get_model(HipModel):
     hip_name = "EPIT"
-    inference_only = "EPIT is inference-only here (its training is broken upstream, EPIT.py:178): call under torch.no_grad()"
 
     def __init__(self, args):
         super().__init__()
