@@ -680,3 +680,193 @@ def distg_forced_gradient_gate(tag, net, xg, sd, x, label, A, s, masks, geom, ho
         bad = {k: (e, e_ref[k]) for k, e in bad.items() if not e < max(1e-4, 3 * e_ref[k])}
     assert not bad, bad
     return errs
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# EPIT: the geometry matrix, the reference graph with every tensor lfsr_epit_train_saved can return, and the maps between the graph's
+# layouts and the HIP path's rows
+# ---------------------------------------------------------------------------------------------------------------------
+# (A, s, B, h, w) and what each row reaches.  The horizontal pass runs sequences of A h tokens, the vertical pass of A w; the matrix-pipe
+# attention kernels (forward and backward) cover up to 160 tokens, k_epi_attn_mfma<10, 0> / k_epi_attn_bwd_mfma<10, 0> at every A != 5.
+EPIT_MATRIX = ((1, 2, 2, 8, 8),       # n1 = 1; 8 tokens, less than one 16-token tile; npix 128, under the 2048-row switch between gather-GEMM and row-GEMM
+               (2, 3, 2, 9, 7),       # even A; scale 3 (two-kernel tail, s^2 = 9 dgrad pack and store branch); 18 / 14 tokens; odd ragged view
+               (4, 4, 1, 40, 6),      # exactly 160 tokens at run-time n1: all ten tiles full; views taller than 32; 24 tokens in the other pass
+               (7, 2, 1, 5, 23),      # 35 tokens on MFMA and 161, one past the bound: the vertical pass on the VALU kernels at A != 5; h = 5 = the window's left half
+               (8, 2, 1, 20, 4),      # 160 tokens with tiles aligned on two columns of 8; w = 4, narrower than the window, one Winograd tile
+               (15, 2, 1, 10, 3),     # largest accepted angRes; 150 tokens, ragged last tile, every key tile in every query's band; 45 tokens
+               (3, 2, 1, 40, 36),     # views wider than 32 in both directions; 120 / 108 tokens; several conv tiles per row, forward and backward
+               (5, 3, 2, 13, 15),     # the benchmark's angRes at scale 3; 65 / 75 tokens on the N1 = 5 kernels, ragged; k_tail_bwd with s^2 = 9
+               (5, 2, 1, 3, 32),      # h = 3, shorter than the window's halves (5, 6) and than a 4x4 conv tile; 15 / 160 tokens
+               (5, 4, 8, 32, 32))     # the published training geometry: ragged weight-gradient splits, the loops of k_ew and k_tail_bwd, lfsr_add_inplace
+
+# which of lfsr_epit_train_saved -> (layout, floats per row, number of indices); 0-3 are there after forward_train, 4-6 after backward.
+# "tok": the feed-forward hidden rows, in the reference a token tensor of the pass (even index: horizontal, odd: vertical)
+EPIT_SAVED = {0: ("vcl", 64, 6), 1: ("vcl", 64, 2), 2: ("vcl", 64, 10), 3: ("vcl", 64, 10), 4: ("tok", 256, 10), 5: ("vcl", 64, 1), 6: ("hr", 64, 1)}
+EPIT_DECISION_KINDS = (1, 2, 3, 4, 5, 6)  # the tensors whose signs are ReLU / LeakyReLU decisions: 2 + 10 + 10 + 10 + 1 + 1 = 34
+EPIT_PER_SAMPLE_NPIX = 50000              # above this many LR pixels the fp64 work is done one sample at a time
+
+
+def epit_keys(kinds=tuple(EPIT_SAVED)):
+    """every (which, index) of `kinds`: 28 after forward_train and 12 more after backward"""
+    return [(k, i) for k in kinds for i in range(EPIT_SAVED[k][2])]
+
+
+def epit_case(A, s, B, h, w):
+    """-> (state_dict, input): synth_state_dict seed 0 / synth_input seed 1, as the golden cases.  EPIT's parameter shapes do not depend on
+    angRes (tests/test_epit_reference.py asserts it), so the golden angRes-5 spec serves every A"""
+    return synth_state_dict(model_spec("EPIT", 5, s), seed=0), synth_input((B, 1, A * h, A * w), seed=1)
+
+
+def epit_samples(A, s, B, h, w):
+    """the slices of the batch the fp64 graph takes at once: the whole batch, or one sample at a time at the published geometry"""
+    return [slice(i, i + 1) for i in range(B)] if B > 1 and B * A * A * h * w > EPIT_PER_SAMPLE_NPIX else [slice(0, B)]
+
+
+def epit_layout(which, index):
+    """the layout of (which, index): "vcl", "hr", or the token layout of its pass, "tokh" (tokens (u y), sequences (b v x)) / "tokv" ((v x), (b u y))"""
+    lay = EPIT_SAVED[which][0]
+    return lay if lay != "tok" else ("tokv" if index % 2 else "tokh")
+
+
+def epit_ref_to_rows(t, layout, B, A, h, w):
+    """reference layout -> the HIP path's rows [b][u][v][y][x][c] (VCL).  vcl: (B, c, A^2, h, w); tokh: (A h, B A w, c); tokv: (A w, B A h, c);
+    hr: (B, 64, A h s, A w s) -> the channel-last mosaic's rows"""
+    if layout == "vcl":
+        return t.permute(0, 2, 3, 4, 1).reshape(-1, t.shape[1])
+    if layout == "tokh":
+        return t.reshape(A, h, B, A, w, -1).permute(2, 0, 3, 1, 4, 5).reshape(-1, t.shape[-1])
+    if layout == "tokv":
+        return t.reshape(A, w, B, A, h, -1).permute(2, 3, 0, 4, 1, 5).reshape(-1, t.shape[-1])
+    if layout == "hr":
+        return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
+    raise KeyError(layout)
+
+
+def epit_rows_to_ref(v, layout, B, A, h, w, s=1):
+    """the inverse: flat values in HIP order -> the reference layout"""
+    if layout == "vcl":
+        return v.reshape(B, A * A, h, w, -1).permute(0, 4, 1, 2, 3)
+    if layout == "tokh":
+        return v.reshape(B, A, A, h, w, -1).permute(1, 3, 0, 2, 4, 5).reshape(A * h, B * A * w, -1)
+    if layout == "tokv":
+        return v.reshape(B, A, A, h, w, -1).permute(2, 4, 0, 1, 3, 5).reshape(A * w, B * A * h, -1)
+    if layout == "hr":
+        return v.reshape(B, A * h * s, A * w * s, 64).permute(0, 3, 1, 2)
+    raise KeyError(layout)
+
+
+def epit_saved_rows(rt, xg, which, index=0):
+    """what forward_train(xg) (which 0-3) or the backward after it (4-6) left for (which, index), as rows in HIP order (a GPU tensor)"""
+    return rt.train_saved(xg, which, index).reshape(-1, EPIT_SAVED[which][1])
+
+
+def epit_hip_masks(rt, xg, A, s, sample=None):
+    """the 34 ReLU / LeakyReLU decisions (> 0) the HIP path took, read after its backward, in the reference layouts: what epit_layers_fp64's
+    `forced` takes.  sample = i: the decisions of sample i alone, as a B = 1 graph takes them (rows are sample-major)"""
+    B, h, w = xg.shape[0], xg.shape[2] // A, xg.shape[3] // A
+    out = {}
+    for k, i in epit_keys(EPIT_DECISION_KINDS):
+        m = (epit_saved_rows(rt, xg, k, i) > 0).cpu()
+        if sample is not None:
+            n = m.shape[0] // B
+            m = m[sample * n:(sample + 1) * n]
+        out[k, i] = epit_rows_to_ref(m, epit_layout(k, i), B if sample is None else 1, A, h, w, s)
+    return out
+
+
+def epit_layers_fp64(x, params, A, s, forced=None, dtype=None):
+    """EPIT's graph (model/SR/EPIT.py:51-71, op for op as oracle/lfsr_torch_port.py::epit_forward states it) on stock torch CPU ops
+    -> (output, layers, flips).
+    layers[(which, index)]: every tensor lfsr_epit_train_saved can return, detached, in the reference's layout (EPIT_SAVED; epit_ref_to_rows).
+    params: {key: tensor} (fp64 unless `dtype` says otherwise; they may require grad).  forced: {(which, index): bool mask in the reference
+    layout} for EPIT_DECISION_KINDS -- the decisions are then the caller's, and flips counts those that differ from the graph's own."""
+    import torch
+    from oracle.lfsr_torch_port import _bicubic_views, _conv133, _mha, _window_mask
+    F = torch.nn.functional
+    dtype = dtype or torch.float64
+    p = {k: torch.as_tensor(v).to(dtype) for k, v in params.items()}
+    xd = torch.as_tensor(x).to(dtype)
+    B, _, Hh, Ww = xd.shape
+    h, w = Hh // A, Ww // A
+    L, flips = {}, 0
+
+    def act(z, key, slope, keep_pre=False):
+        nonlocal flips
+        if forced is None:
+            y = F.leaky_relu(z, slope) if slope else F.relu(z)
+        else:
+            m = forced[key]
+            assert m.shape == z.shape, (key, tuple(m.shape), tuple(z.shape))
+            flips += int(((z > 0) != m).sum())
+            y = torch.where(m, z, z * slope)
+        L[key] = (z if keep_pre else y).detach()
+        return y
+
+    def trans(buf, pre, key):      # BasicTrans.forward EPIT.py:110-128; buf (b, c, sequences, tokens of one angular row, tokens of one line)
+        b, c, n, v, l = buf.shape
+        mask = _window_mask(v, l, A, A, 5, 6, l)         # mask_field [2 A, 11]
+        tok = F.linear(buf.permute(3, 4, 0, 2, 1).reshape(v * l, b * n, c), p[pre + "linear_in.weight"])
+        tn = F.layer_norm(tok, tok.shape[-1:], p[pre + "norm.weight"], p[pre + "norm.bias"])
+        tok = _mha(tn, tn, tok, p[pre + "attention.in_proj_weight"], p[pre + "attention.out_proj.weight"], 8, mask) + tok
+        ff = F.layer_norm(tok, tok.shape[-1:], p[pre + "feed_forward.0.weight"], p[pre + "feed_forward.0.bias"])
+        tok = F.linear(act(F.linear(ff, p[pre + "feed_forward.1.weight"]), key, 0.0), p[pre + "feed_forward.4.weight"]) + tok
+        return F.linear(tok, p[pre + "linear_out.weight"]).reshape(v, l, b, n, -1).permute(2, 4, 3, 0, 1)
+    views, skip = _bicubic_views(xd, A, h, w, s)
+    buf = _conv133(views, p["conv_init0.0.weight"])
+    t = act(_conv133(buf, p["conv_init.0.weight"]), (1, 0), 0.2)
+    t = act(_conv133(t, p["conv_init.2.weight"]), (1, 1), 0.2)
+    buf = act(_conv133(t, p["conv_init.4.weight"]), (5, 0), 0.2) + buf
+    t = buf
+    c = buf.shape[1]
+    nblk = 1 + max(int(k.split(".")[1]) for k in p if k.startswith("altblock."))
+    for i in range(nblk):
+        pre = f"altblock.{i}."
+        L[0, i] = t.detach()
+        shortcut = t
+
+        def conv(z, j):
+            z = act(_conv133(z, p[pre + "conv.0.weight"]), (2, j), 0.2)
+            z = act(_conv133(z, p[pre + "conv.2.weight"]), (3, j), 0.2)
+            return _conv133(z, p[pre + "conv.4.weight"])
+        z = t.reshape(B, c, A, A, h, w).permute(0, 1, 3, 5, 2, 4).reshape(B, c, A * w, A, h)        # horizontal: tokens (u y)
+        z = trans(z, pre + "epi_trans.", (4, 2 * i))
+        z = z.reshape(B, c, A, w, A, h).permute(0, 1, 4, 2, 5, 3).reshape(B, c, A * A, h, w)
+        t = conv(z, 2 * i) + shortcut
+        z = t.reshape(B, c, A, A, h, w).permute(0, 1, 2, 4, 3, 5).reshape(B, c, A * h, A, w)        # vertical: tokens (v x)
+        z = trans(z, pre + "epi_trans.", (4, 2 * i + 1))
+        z = z.reshape(B, c, A, h, A, w).permute(0, 1, 2, 4, 3, 5).reshape(B, c, A * A, h, w)
+        t = conv(z, 2 * i + 1) + shortcut
+    t = t + buf
+    L[0, nblk] = t.detach()
+    mosaic = t.reshape(B, c, A, A, h, w).permute(0, 1, 2, 4, 3, 5).reshape(B, c, A * h, A * w)
+    up = F.pixel_shuffle(F.conv2d(mosaic, p["upsampling.0.weight"]), s)
+    y = F.conv2d(act(up, (6, 0), 0.2, keep_pre=True), p["upsampling.3.weight"], padding=1) + skip
+    return y, L, flips
+
+
+def epit_forced_fp64_grads(rt, xg, sd, x, label, A, s, dtype=None):
+    """-> ({name: fp64 gradient}, number of the HIP path's decisions that differ from fp64's own).  Call after the HIP backward of xg.
+    fp64 autograd of epit_layers_fp64 under L1 `mean` loss with every one of its 34 activation decisions taken from what the HIP path computed
+    (lfsr_epit_train_saved): 3 in conv_init; per block and pass the feed-forward ReLU, conv.0 and conv.2; the tail's HR LeakyReLU.  A
+    pre-activation within fp32 rounding of 0 is a legitimate tie whose two sides have different gradients downstream (one flipped pixel moves
+    the gradient of a small case by ~1e-3); this graph makes the same choices.  The sign of the L1 loss's gradient is taken from the HIP
+    output as well.  Large batches go one sample at a time: the batch gradient of a mean loss is the mean of the per-sample gradients, each
+    under that sample's slice of the decisions.  dtype: the same autograd in another precision (torch.float32: the e_ref of the cancellation
+    allowance, fp32 CPU autograd under the same decisions)."""
+    import torch
+    dtype = dtype or torch.float64
+    B, h, w = x.shape[0], x.shape[2] // A, x.shape[3] // A
+    out_hip = rt.forward(xg).cpu().double()                  # bit-equal to the training forward's output; runs in the inference workspace
+    lab = torch.as_tensor(label, dtype=torch.float64)
+    sign = torch.sign(out_hip - lab).to(dtype)
+    p = {k: torch.tensor(v, dtype=dtype, requires_grad=True) for k, v in sd.items()}
+    flips = 0
+    for sl in epit_samples(A, s, B, h, w):
+        n = sl.stop - sl.start
+        forced = epit_hip_masks(rt, xg, A, s, sample=None if n == B else sl.start)
+        assert len(forced) == 34
+        y, _, f = epit_layers_fp64(x[sl], p, A, s, forced=forced, dtype=dtype)
+        ((y * sign[sl]).sum() / sign.numel()).backward()
+        flips += f
+        del y
+    return {k: v.grad.numpy() for k, v in p.items()}, flips

@@ -130,29 +130,50 @@ def test_linear_with_layernorm_inside(K, M, with_pe, form, monkeypatch):
         assert torch.equal(qk, qk2) and torch.equal(v, v2)
 
 
+EPI_ATTN_GEOMS = [(2, 3, 6, 8), (1, 5, 32, 32), (1, 5, 20, 32),
+                  (1, 8, 20, 2),      # 160 tokens at run-time n1 (k_epi_attn_mfma<10, 0>: all ten tiles) / 16
+                  (1, 15, 10, 1),     # 150 tokens, n1 = 15 / a 15-token pass
+                  (2, 1, 8, 3),       # n1 = 1
+                  (1, 5, 3, 32),      # the window (5 left, 6 right) wider than a 3-token column / 160 tokens
+                  (1, 7, 23, 2)]      # 161 tokens: one past the matrix-pipe kernel, which must hand over to the VALU kernel at A != 5
+EPI_ATTN_SENTINEL = -777.25
+
+
 @pytest.mark.parametrize("vertical", [0, 1])
-@pytest.mark.parametrize("geom", [(2, 3, 6, 8), (1, 5, 32, 32), (1, 5, 20, 32)])
+@pytest.mark.parametrize("geom", EPI_ATTN_GEOMS)
 @pytest.mark.parametrize("path", ["mfma", "valu"])
 def test_epi_attention_vs_masked_mha(vertical, geom, path, monkeypatch):
     """window predicate == the reference's additive -inf mask (EPIT.py:93-108) inside nn.MultiheadAttention's core; both the MFMA kernel
-    (attn_mfma.hip, default) and the VALU kernels, at a reduced geometry and at EPIT's own (5 x 32 = 160 tokens per sequence; 5 x 20: ragged last tile)"""
+    (attn_mfma.hip, default) and the VALU kernels, at a reduced geometry, at EPIT's own (5 x 32 = 160 tokens per sequence; 5 x 20: ragged last tile)
+    and at the run-time-n1 kernel's edges.  Up to 160 tokens the default is another kernel than LFSR_ATTN=valu (its sums run in another order);
+    past them both selections run the VALU kernel: the same bits."""
     lib = capi.load()
-    if path == "valu":
-        monkeypatch.setenv("LFSR_ATTN", "valu")
-    else:
-        monkeypatch.delenv("LFSR_ATTN", raising=False)
     (B, A, h, w), E, NH = geom, 128, 8
     npix = B * A * A * h * w
     q, k, v = rnd((npix, E), 7), rnd((npix, E), 8), rnd((npix, E), 9)
-    o = torch.empty(npix, E, device="cuda")
     HW = h * w
     if not vertical:
         args = (B, A, w, A * A * HW, HW, 1, A, h, A * HW, w)
     else:
         args = (B, A, h, A * A * HW, A * HW, w, A, w, HW, 1)
     qd, kd, vd = dev(q), dev(k), dev(v)
-    capi.check(lib.lfsr_window_attn_fwd(capi.dev_ptr(qd), E, 0, capi.dev_ptr(kd), E, 0, capi.dev_ptr(vd), E, 0, capi.dev_ptr(o), E, 0, NH, E // NH,
-                                        *args, A, A, 5, 6, 0, capi.stream_ptr()), "attn")
+    got_sel = {}
+    for sel in ("mfma", "valu"):
+        if sel == "valu":
+            monkeypatch.setenv("LFSR_ATTN", "valu")
+        else:
+            monkeypatch.delenv("LFSR_ATTN", raising=False)
+        o_sel = torch.full((npix + 2, E), EPI_ATTN_SENTINEL, device="cuda")      # two rows beyond the last pixel
+        capi.check(lib.lfsr_window_attn_fwd(capi.dev_ptr(qd), E, 0, capi.dev_ptr(kd), E, 0, capi.dev_ptr(vd), E, 0, capi.dev_ptr(o_sel), E, 0, NH, E // NH,
+                                            *args, A, A, 5, 6, 0, capi.stream_ptr()), "attn")
+        torch.cuda.synchronize()
+        got_sel[sel] = o_sel
+    assert bool((got_sel[path][npix:] == EPI_ATTN_SENTINEL).all())               # rows outside the operand are left untouched
+    if A * (w if vertical else h) > 160:
+        assert torch.equal(got_sel["mfma"], got_sel["valu"])
+    else:
+        assert not torch.equal(got_sel["mfma"], got_sel["valu"])
+    o = got_sel[path][:npix]
     # reference: tokens (L, N, E) in the rearranged order of AltFilter.forward (EPIT.py:150/156)
     def to_seq(t):
         t = t.astype(np.float64).reshape(B, A, A, h, w, E)                                  # b u v y x e

@@ -24,7 +24,12 @@ GEOMS = [(2, 3, 6, 8),       # L = 18 / 24: window wider than the sequence, run-
          (1, 5, 32, 2),      # L = 160 (all ten tiles) / L = 10 (less than one tile)
          (1, 5, 20, 2),      # L = 100: ragged last tile
          (2, 3, 20, 7),      # L = 60: interior band at run-time n1 / L = 21
-         (1, 5, 36, 2)]      # L = 180: beyond the matrix-pipe kernel, which must hand over to the VALU pair
+         (1, 5, 36, 2),      # L = 180: beyond the matrix-pipe kernel, which must hand over to the VALU pair
+         (1, 8, 20, 2),      # L = 160 at run-time n1 (k_epi_attn_bwd_mfma<10, 0>: all ten tiles) / L = 16
+         (1, 15, 10, 1),     # L = 150, n1 = 15 / a 15-token pass
+         (2, 1, 8, 3),       # n1 = 1
+         (1, 5, 3, 32),      # the window (5 left, 6 right) wider than a 3-token column / L = 160
+         (1, 7, 23, 2)]      # L = 161: one past the bound, the hand-over to the VALU pair at A != 5
 
 
 def rnd(shape, seed):

@@ -124,7 +124,7 @@ def test_grads_match_fp64_port_and_bucket(tag):
     med, mx = check_against_port(net, bucket, forced)
     med0, mx0 = check_against_port(net, bucket, ref)
     print(f"{tag}: rel-L2 vs fp64 with the HIP decisions median {med:.2e} max {mx:.2e}; vs fp64 median {med0:.2e} max {mx0:.2e} ({flips} decisions differ)")
-    assert med <= 5e-5 and mx <= 1e-2
+    assert med <= 5e-5 and mx < 1e-4      # per parameter (tests/test_gpu_epit_geometries.py holds every row of its matrix to the same)
     assert mx0 <= 1e-2
     cat = torch.cat([p.grad.reshape(-1) for p in net.parameters()])
     assert torch.equal(cat, net.grad_bucket)
