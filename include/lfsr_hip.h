@@ -445,9 +445,17 @@ int lfsr_epiconv_hv_bwd(const float* dy, int dy_stride, int choff_h, int choff_v
 /* ---- arithmetic of the GEMMs that exist in two forms (DistgSSR's EPI branch and fuse.0; the transformers' linears, fused FFN and up-sampling tail) ----
  * LFSR_ARITH_DEFAULT: fp32 operands carried EXACTLY as three bf16 terms on the bf16 MFMA pipe, six products, fp32 accumulation (error against fp64 not above the
  * fp32-MFMA kernels': tests/test_gpu_b3_accuracy.py); LFSR_ARITH_F32: every GEMM on fp32 MFMA.  Process-wide, read at every launch; the 3x3 convs, the angular
- * branch and the attention kernels compute on fp32 MFMA either way.  The reference computes all of these layers with stock fp32 torch ops. */
+ * branch and the attention kernels compute on fp32 MFMA either way.  The reference computes all of these layers with stock fp32 torch ops.
+ * LFSR_ARITH_BF16: reduced-precision operands for ONE layer class, opt-in.  Only the 64 -> 64 per-view 3x3 forward conv (lfsr_conv3x3_fwd on 16-B aligned operands,
+ * hence every such conv of the four model drivers' forward and forward_train) changes: its activations and weights are rounded to bf16 (nearest even), the products
+ * are exact and accumulation, LeakyReLU and residual adds are fp32; activations stay fp32 in memory.  Everything else runs exactly as under LFSR_ARITH_DEFAULT (the
+ * GEMMs keep their exact three-term bf16 form, lfsr_distg_branch_tail_fwd covers what it covers there): lfsr_conv3x3_n_fwd, LF_InterNet's 128 -> 64 convs, the
+ * angular branch, the attention kernels, unaligned conv operands (fp32 gather-GEMM) and every data- and weight-gradient kernel do not change.  A backward after a
+ * forward_train in this mode differentiates the fp32 layers at that forward's activations, as autocast does; parity with the reference's gradients is claimed only
+ * in the other two modes. */
 #define LFSR_ARITH_DEFAULT 0
 #define LFSR_ARITH_F32 1
+#define LFSR_ARITH_BF16 2
 int lfsr_set_arithmetic(int mode);
 int lfsr_get_arithmetic(void);
 

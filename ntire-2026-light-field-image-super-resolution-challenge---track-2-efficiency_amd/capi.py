@@ -170,12 +170,18 @@ def _elem(t):
     return eb
 
 
-ARITH_DEFAULT, ARITH_F32 = 0, 1
+ARITH_DEFAULT, ARITH_F32, ARITH_BF16 = 0, 1, 2
 
 
 def set_arithmetic(mode):
-    """lfsr_set_arithmetic: ARITH_DEFAULT (three exact bf16 terms on the bf16 MFMA pipe where a kernel has that form) or ARITH_F32 (every GEMM on fp32 MFMA); process-wide"""
+    """lfsr_set_arithmetic: ARITH_DEFAULT (three exact bf16 terms on the bf16 MFMA pipe where a kernel has that form), ARITH_F32 (every GEMM on fp32 MFMA) or
+    ARITH_BF16 (the default, but the 64 -> 64 per-view 3x3 forward conv rounds its activations and weights to bf16, fp32 accumulation); process-wide"""
     check(load().lfsr_set_arithmetic(int(mode)), "set_arithmetic")
+
+
+def get_arithmetic():
+    """lfsr_get_arithmetic: the mode the next launch runs in"""
+    return int(load().lfsr_get_arithmetic())
 
 
 def op_profile(enable):
@@ -363,7 +369,7 @@ class GraphedForward:
         self.graphs = {}
 
     def __call__(self, x):
-        key = (tuple(x.shape), x.device, x.dtype)
+        key = (tuple(x.shape), x.device, x.dtype, get_arithmetic())      # the arithmetic is read at launch: a graph holds the kernels of the mode it was captured in
         g = self.graphs.get(key)
         if g is None:
             static_x = x.clone()

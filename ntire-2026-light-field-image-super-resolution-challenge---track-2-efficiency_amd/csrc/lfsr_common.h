@@ -24,6 +24,7 @@ static inline hipStream_t lfsr_stream(void* s) { return reinterpret_cast<hipStre
 // launch path.  The one selection a product caller may make -- the arithmetic of the GEMMs that have an exact-three-term-bf16 form -- is an API: lfsr_set_arithmetic.
 const char* lfsr_sel(const char* name);
 bool lfsr_arith_f32();     // lfsr_set_arithmetic(LFSR_ARITH_F32): every GEMM on fp32 MFMA
+bool lfsr_arith_bf16();    // lfsr_set_arithmetic(LFSR_ARITH_BF16): the 64 -> 64 3x3 forward conv on bf16 operands (conv3x3_bf16.hip); everything else as the default
 static inline unsigned lfsr_blocks(long long n, int per) {
   long long b = (n + per - 1) / per;
   return (unsigned)(b < 1 ? 1 : b);

@@ -89,6 +89,7 @@ int lfsr_conv3x3_halo_launch(const LfsrConv3& c, hipStream_t st);               
 int lfsr_conv3x3_halo_tail_launch(const LfsrConv3& c, int tile_begin, int tile_count, hipStream_t st);  // ... its channel-split launch over a tile range only
 int lfsr_conv3x3_wino2_launch(const LfsrConv3& c, hipStream_t st);                                     // conv3x3_wino.hip: F(2x2,3x3); operand spans below 2 GiB
 int lfsr_conv3x3_wino4_launch(const LfsrConv3& c, hipStream_t st);                                     // conv3x3_wino4.hip: F(4x4,3x3); operand spans below 1 GiB
+int lfsr_conv3x3_bf16_launch(const LfsrConv3& c, hipStream_t st);                                      // conv3x3_bf16.hip: direct 9-tap form on bf16 operands, forward only (LFSR_ARITH_BF16)
 int lfsr_conv3x3_gather_launch(const LfsrConv3& c, hipStream_t st);                                    // gemm_gather.hip: gather-GEMM, no alignment demand on y / r1 / r2 / mk
 // conv3x3.cpp: which kernel runs.  LFSR_CONV3X3 selects the forward kernel, LFSR_DGRAD3 (same vocabulary) the data-gradient kernel, which otherwise follows
 // LFSR_CONV3X3.  The selection is read when weights are packed AND at every launch: set it before loading a model.

@@ -1,5 +1,5 @@
 // Library-wide options of liblfsr_hip.so.
-//  * lfsr_set_arithmetic: which arithmetic the GEMMs that have two forms run in (the product-level choice);
+//  * lfsr_set_arithmetic: which arithmetic the GEMMs that have two forms run in, or bf16 operands for the 64 -> 64 3x3 forward conv (the product-level choice);
 //  * lfsr_sel: the A/B selectors of the measurement / parity tooling (LFSR_* environment variables), live only in a process started with LFSR_LAB set.
 #include <stdlib.h>
 
@@ -20,11 +20,12 @@ const char* lfsr_sel(const char* name) {
 }
 
 bool lfsr_arith_f32() { return g_arith.load(std::memory_order_relaxed) == LFSR_ARITH_F32; }
+bool lfsr_arith_bf16() { return g_arith.load(std::memory_order_relaxed) == LFSR_ARITH_BF16; }
 
 extern "C" {
 
 int lfsr_set_arithmetic(int mode) {
-  if (mode != LFSR_ARITH_DEFAULT && mode != LFSR_ARITH_F32) return LFSR_E_ARG;
+  if (mode != LFSR_ARITH_DEFAULT && mode != LFSR_ARITH_F32 && mode != LFSR_ARITH_BF16) return LFSR_E_ARG;
   g_arith.store(mode);
   return LFSR_OK;
 }
