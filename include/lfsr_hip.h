@@ -98,8 +98,9 @@ size_t lfsr_packed_weight_floats(int O, int C, int taps);
 
 /* per-view 3x3 conv, zero pad 1 (== the MacPI conv "k3, dilation A, padding A" of DistgSSR.py:22,47,64,
  * 79-83,101; == Conv3d(1,3,3) of EPIT.py:24-32,136-142 / LFT.py:36-46), Cin=Cout=64:
- *   y = act(conv(x)) [+ r1] [+ r2],  act = LeakyReLU(slope) if slope != 1.0f.
- * n_img = B*A*A images of h x w. */
+ *   y = act(conv(x)) [+ r1] [+ r2],  act(v) = v >= 0 ? v : slope * v for any slope (1.0f: none, 0.0f: ReLU); a lone residual may be passed as r2.
+ * n_img = B*A*A images of h x w.  x_stride and x_choff must be multiples of 4 and every stride at least its offset + 64 (LFSR_E_ARG otherwise, nothing
+ * written); y, r1 and r2 may sit at any offset (off the 16-byte grid the gather-GEMM runs). */
 int lfsr_conv3x3_fwd(const float* x, int x_stride, int x_choff, const float* w_packed,
                      float* y, int y_stride, int y_choff,
                      const float* r1, int r1_stride, int r1_choff, const float* r2, int r2_stride, int r2_choff,
@@ -118,14 +119,19 @@ int lfsr_angconv_fwd(const float* x, int x_stride, int x_choff, const float* w1_
 /* EPIConv, DistgSSR.py:91-97 (horizontal: vertical = 0) and its transposed application DistgSSR.py:108
  * (vertical = 1, same weights): t = lrelu(conv 1xA^2 stride A pad A(A-1)/2 64->32);
  * y = lrelu(1x1 32->32*A) scattered by PixelShuffle1D(A).  tmp: (B*A*h*w*32) floats; on return it holds the pass's stage-1 activation t, rows ordered
- * (b*A+u, y, x) / (b*A+v, y, x) -- what lfsr_epiconv_hv_bwd takes as e_h / e_v. */
+ * (b*A+u, y, x) / (b*A+v, y, x) -- what lfsr_epiconv_hv_bwd takes as e_h / e_v.  tmp may be NULL (nothing saved) where a fused kernel runs: A odd, A <= 5,
+ * h, w <= 32, y_stride and y_choff multiples of 4, x below 2^31 bytes (B*A*A*h*w*x_stride*4), and LFSR_EPI=gather not selected in a lab process; the gather-GEMM
+ * path everywhere else needs it and answers LFSR_E_ARG without it.  lrelu(v) = v >= 0 ? v :
+ * slope * v for any slope (the three-term bf16 kernel of angRes 5 covers 0 <= slope <= 1; outside it the fp32-MFMA kernel runs). */
 int lfsr_epiconv_fwd(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed,
                      float* tmp, float* y, int y_stride, int y_choff, int B, int A, int h, int w, int vertical,
                      float slope, void* stream);
 
 /* Both EPI passes of a DisentgBlock (DistgSSR.py:107-108) in one launch: horizontal result to channel slice
  * choff_h, vertical (transposed application, same weights) to choff_v of y.  Uses the fused LDS-tile kernel
- * when (A odd, A <= 5, h,w <= 32), else two gather-GEMM launches per pass through tmp (may be NULL if fused). */
+ * when (A odd, A <= 5, h,w <= 32; y_stride and both offsets multiples of 4; x below 2^31 bytes; LFSR_EPI=gather not selected), else two gather-GEMM launches per pass through tmp (may be NULL if fused:
+ * LFSR_E_ARG, nothing written, where the gather-GEMM path would need it).  tmp is scratch here: the fused kernels leave it alone, the gather-GEMM path
+ * leaves the vertical pass's stage-1 activation in it. */
 int lfsr_epiconv_hv_fwd(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed,
                         float* tmp, float* y, int y_stride, int choff_h, int choff_v, int B, int A, int h, int w,
                         float slope, void* stream);

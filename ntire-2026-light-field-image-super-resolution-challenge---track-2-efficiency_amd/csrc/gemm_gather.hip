@@ -292,6 +292,7 @@ int lfsr_conv3x3_fwd(const float* x, int x_stride, int x_choff, const float* w_p
   LfsrOpTimer op_t("conv3x3", n_img, h * w, lfsr_stream(stream));
   if (!x || !w_packed || !y || n_img <= 0 || h <= 0 || w <= 0) return LFSR_E_ARG;
   if (x_stride < x_choff + 64 || y_stride < y_choff + 64 || (x_stride | x_choff) & 3) return LFSR_E_ARG;
+  if ((r1 && r1_stride < r1_choff + 64) || (r2 && r2_stride < r2_choff + 64)) return LFSR_E_ARG;   // (as lfsr_conv3x3_dgrad checks its r1 and act)
   if ((long long)n_img * h * w >= (1LL << 31) / 4) return LFSR_E_ARG;
   LfsrConv3 c{};
   c.x = x; c.x_stride = x_stride; c.x_choff = x_choff; c.w_packed = w_packed; c.y = y; c.y_stride = y_stride; c.y_choff = y_choff;
