@@ -62,23 +62,18 @@ __global__ void k_fold_recon(const float* __restrict__ wpre, const float* __rest
   wf[i] = (float)a;
 }
 
-inline unsigned cap_grid(long long total, unsigned cap = 8192) {
-  unsigned g = lfsr_blocks(total, 256);
-  return g > cap ? cap : g;
-}
-
 }  // namespace
 
 // AngFE and the 64-channel slice copy as host launches: the training forward (internet_train.hip) issues the same launches
 int lfsr_internet_angfe(const float* x, const float* w, float* y, int y_stride, int y_choff, int B, int A, int h, int wd, hipStream_t st) {
   const long long nlr = (long long)B * h * wd;
-  hipLaunchKernelGGL(k_angfe, dim3(cap_grid(nlr * 16)), dim3(256), 64 * A * A * sizeof(float), st, x, w, y, y_stride, y_choff, B, A, h, wd);
+  hipLaunchKernelGGL(k_angfe, dim3(lfsr_cap_grid(nlr * 16)), dim3(256), 64 * A * A * sizeof(float), st, x, w, y, y_stride, y_choff, B, A, h, wd);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }
 
 int lfsr_internet_copy64(const float* src, int s_stride, int s_choff, float* dst, int d_stride, int d_choff, long long M, hipStream_t st) {
-  hipLaunchKernelGGL(k_copy64, dim3(cap_grid(M * 16)), dim3(256), 0, st, src, s_stride, s_choff, dst, d_stride, d_choff, M);
+  hipLaunchKernelGGL(k_copy64, dim3(lfsr_cap_grid(M * 16)), dim3(256), 0, st, src, s_stride, s_choff, dst, d_stride, d_choff, M);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }
@@ -166,10 +161,10 @@ int lfsr_internet_forward(lfsr_internet* c, const float* x, float* out, int B, i
     return launcher(p, st);
   };
   // feature extraction (LF_InterNet.py:35-36)
-  hipLaunchKernelGGL(k_angfe, dim3(cap_grid(nlr * 16)), dim3(256), 64 * AA * sizeof(float), st, x, P.w("AngFE.0.weight"), Ar[0], 128, 0, B, A, h, w);
+  hipLaunchKernelGGL(k_angfe, dim3(lfsr_cap_grid(nlr * 16)), dim3(256), 64 * AA * sizeof(float), st, x, P.w("AngFE.0.weight"), Ar[0], 128, 0, B, A, h, w);
   LFSR_CHECK_LAUNCH();
   LFSR_RC(lfsr_initconv_fwd(x, P.w("SpaFE.0.weight"), S[0], 128, 0, B, A, h, w, stream));
-  hipLaunchKernelGGL(k_copy64, dim3(cap_grid(npix * 16)), dim3(256), 0, st, S[0], 128, 0, XS0, 64, 0, npix);
+  hipLaunchKernelGGL(k_copy64, dim3(lfsr_cap_grid(npix * 16)), dim3(256), 0, st, S[0], 128, 0, XS0, 64, 0, npix);
   LFSR_CHECK_LAUNCH();
   int cur = 0;
   for (int g = 0; g < G; ++g) {
@@ -185,9 +180,9 @@ int lfsr_internet_forward(lfsr_internet* c, const float* x, float* out, int B, i
       LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 128, 2>, S[cur], 128, 0, P.w(p + "SpaConvSq.weight"), S[nxt], 128, 0, S[cur], 128, 0, (int)npix, 64, 9, 64, 0.0f));
       cur = nxt;
     }
-    hipLaunchKernelGGL(k_copy64, dim3(cap_grid(nlr * 16)), dim3(256), 0, st, Ar[cur], 128, 0, CA, ca_stride, 64 * g, nlr);
+    hipLaunchKernelGGL(k_copy64, dim3(lfsr_cap_grid(nlr * 16)), dim3(256), 0, st, Ar[cur], 128, 0, CA, ca_stride, 64 * g, nlr);
     LFSR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_copy64, dim3(cap_grid(npix * 16)), dim3(256), 0, st, S[cur], 128, 0, CS, cs_stride, 64 * g, npix);
+    hipLaunchKernelGGL(k_copy64, dim3(lfsr_cap_grid(npix * 16)), dim3(256), 0, st, S[cur], 128, 0, CS, cs_stride, 64 * g, npix);
     LFSR_CHECK_LAUNCH();
   }
   // BottleNeck (LF_InterNet.py:119-124)

@@ -18,11 +18,6 @@
 
 namespace {
 
-inline unsigned cap_grid(long long total, unsigned cap = 8192) {
-  unsigned g = lfsr_blocks(total, 256);
-  return g > cap ? cap : g;
-}
-
 // d[r][c] = (a[r][c] (+ b[r][c])) * [mk[r][c] > 0]   for 64 channels; b, mk optional.  The forward's residual add (a = ReLU(z), b = residual)
 // and the backward's ReLU' masks and gradient sums.
 __global__ __launch_bounds__(256) void k_ew64(const float* a, int as, int ao, const float* __restrict__ b, int bs, int bo,
@@ -132,7 +127,7 @@ __global__ __launch_bounds__(256) void k_fold_bwd(const float* __restrict__ dWf,
 }
 
 int ew64(const float* a, int as, int ao, const float* b, int bs, int bo, const float* mk, int ms, int mo, float* d, int ds, int dof, long long M, hipStream_t st) {
-  hipLaunchKernelGGL(k_ew64, dim3(cap_grid(M * 16)), dim3(256), 0, st, a, as, ao, b, bs, bo, mk, ms, mo, d, ds, dof, M);
+  hipLaunchKernelGGL(k_ew64, dim3(lfsr_cap_grid(M * 16)), dim3(256), 0, st, a, as, ao, b, bs, bo, mk, ms, mo, d, ds, dof, M);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }
@@ -140,7 +135,6 @@ int ew64(const float* a, int as, int ao, const float* b, int bs, int bo, const f
 // ---- workspace --------------------------------------------------------------------------------------------------------------
 constexpr int NG = 4, NL = 4, NLAYER = NG * NL;
 inline int angfe_kpad(int A) { return (A * A + 3) / 4 * 4; }
-inline size_t tr3_floats() { return lfsr_packed_weight_tr_floats(64, 64, 9); }
 
 struct InterTrainWs {
   // saved by forward_train
@@ -177,10 +171,10 @@ void train_layout(const lfsr_internet* c, int B, int h, int w, LfsrArena& ws, In
   for (int l = 0; l < NLAYER; ++l) { t.RS[l] = ws.take(npix * 64); t.RA[l] = ws.take(nlr * 64); }
   t.CS = ws.take(npix * 64 * (NG + 1)); t.CA = ws.take(nlr * 64 * NG); t.BA = ws.take(nlr * 64); t.RB = ws.take(npix * 64); t.BO = ws.take(npix * 64);
   for (int l = 0; l < NLAYER; ++l) {
-    t.ScLo[l] = ws.take(tr3_floats()); t.ScHi[l] = ws.take(tr3_floats()); t.AcT[l] = ws.take(128 * 64);
+    t.ScLo[l] = ws.take(lfsr_tr3_floats()); t.ScHi[l] = ws.take(lfsr_tr3_floats()); t.AcT[l] = ws.take(128 * 64);
     t.A2sT[l] = ws.take((size_t)AA * 64 * 64); t.S2aT[l] = ws.take((size_t)AA * 64 * 64);
   }
-  for (int j = 0; j <= NG; ++j) t.SbT[j] = ws.take(tr3_floats());
+  for (int j = 0; j <= NG; ++j) t.SbT[j] = ws.take(lfsr_tr3_floats());
   t.AbT = ws.take(64 * NG * 64); t.BA2sT = ws.take((size_t)AA * 64 * 64); t.FoldT = ws.take(9 * 64 * 16);
   t.G16 = ws.take(npix * 16); t.dBO = ws.take(npix * 64); t.dZ = ws.take(npix * 64); t.dCS = ws.take(npix * 64 * (NG + 1));
   t.dOs[0] = ws.take(npix * 64); t.dOs[1] = ws.take(npix * 64); t.dSP = ws.take(npix * 64);
@@ -208,7 +202,7 @@ std::string chain_key(int g, int l, const char* leaf) {
 }  // namespace
 
 int lfsr_pack_T_from_fwd(const float* Wp, float* out, int T, int Npad_in, int C, int O, int k0, int Kc, int flip, hipStream_t st) {
-  hipLaunchKernelGGL(k_pack_T_from_fwd, dim3(cap_grid((long long)T * Kc * O)), dim3(256), 0, st, Wp, out, T, Npad_in, C, O, k0, Kc, flip);
+  hipLaunchKernelGGL(k_pack_T_from_fwd, dim3(lfsr_cap_grid((long long)T * Kc * O)), dim3(256), 0, st, Wp, out, T, Npad_in, C, O, k0, Kc, flip);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }
@@ -273,7 +267,7 @@ int lfsr_internet_forward_train(lfsr_internet* c, const float* x, float* out, in
   };
   // ---- the packs only the backward reads, transposed from the forward's packs (which the runtime refreshes before every training forward)
   auto packT = [&](const std::string& key, float* o, int T, int Npad_in, int C, int O, int k0, int Kc, int flip) -> int {
-    hipLaunchKernelGGL(k_pack_T_from_fwd, dim3(cap_grid((long long)T * Kc * O)), dim3(256), 0, st, P.w(key), o, T, Npad_in, C, O, k0, Kc, flip);
+    hipLaunchKernelGGL(k_pack_T_from_fwd, dim3(lfsr_cap_grid((long long)T * Kc * O)), dim3(256), 0, st, P.w(key), o, T, Npad_in, C, O, k0, Kc, flip);
     LFSR_CHECK_LAUNCH();
     if (T == 9 && O == 64 && Kc == 64) return lfsr_pack_wino_m(o, o + LFSR_CONV3_WINO2_OFF, LFSR_W_ALL, st);   // the 64 -> 64 3x3 data gradient's Winograd copies
     return LFSR_OK;
@@ -351,7 +345,7 @@ int lfsr_internet_backward(lfsr_internet* c, const float* x, const float* dout, 
   };
 
   // ---- ReconBlock (folded 3x3 conv 64 -> s^2 + MacPI2SAI + PixelShuffle(s)) ----------------------------------------------------------
-  hipLaunchKernelGGL(k_unshuffle_hr, dim3(cap_grid((long long)npix * 16)), dim3(256), 0, st, dout, t.G16, B, A, h, w, c->s);
+  hipLaunchKernelGGL(k_unshuffle_hr, dim3(lfsr_cap_grid((long long)npix * 16)), dim3(256), 0, st, dout, t.G16, B, A, h, w, c->s);
   LFSR_CHECK_LAUNCH();
   LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 16, 2>, t.G16, 16, 0, t.FoldT, t.dBO, 64, 0, nullptr, 0, 0, nullptr, 0, 0, npix, 64, 9, 64));
   LFSR_RC(wgrad(LFSR_IN_SAME, LFSR_IN_CONV3, t.G16, 16, 0, t.BO, 64, 0, npix, 16, 64, 9, t.dWf, 16, 64, 9, 0, 0, 0, 0));
@@ -408,7 +402,7 @@ int lfsr_internet_backward(lfsr_internet* c, const float* x, const float* dout, 
   LFSR_RC(lfsr_init_gather9(x, t.XG9, B, A, h, w, st));
   LFSR_RC(wgrad(LFSR_IN_SAME, LFSR_IN_SAME, t.dOs[cur], 64, 0, t.XG9, 16, 0, npix, 64, 16, 1, G("SpaFE.0.weight"), 64, 16, 1, 0, 0, 9, 0));
   const int kp = angfe_kpad(A);
-  hipLaunchKernelGGL(k_angfe_gather, dim3(cap_grid((long long)nlr * kp)), dim3(256), 0, st, x, t.XA, B, A, h, w, kp);
+  hipLaunchKernelGGL(k_angfe_gather, dim3(lfsr_cap_grid((long long)nlr * kp)), dim3(256), 0, st, x, t.XA, B, A, h, w, kp);
   LFSR_CHECK_LAUNCH();
   LFSR_RC(wgrad(LFSR_IN_SAME, LFSR_IN_SAME, t.dOa[cur], 64, 0, t.XA, kp, 0, nlr, 64, kp, 1, G("AngFE.0.weight"), 64, kp, 1, 0, 0, AA, 0));
   return LFSR_OK;

@@ -29,6 +29,10 @@ static inline unsigned lfsr_blocks(long long n, int per) {
   long long b = (n + per - 1) / per;
   return (unsigned)(b < 1 ? 1 : b);
 }
+static inline unsigned lfsr_cap_grid(long long total, unsigned cap = 8192) {   // blocks of 256 for a grid-stride loop over `total`
+  unsigned g = lfsr_blocks(total, 256);
+  return g > cap ? cap : g;
+}
 
 // Host-side layout of a workspace: buffers one after another in 64-float (256-B) granules.  A null base is the sizing pass (every pointer
 // null, `floats` exact); offsets() lays out on a stand-in base that is never dereferenced, so that offset(p) tells where a buffer lies.

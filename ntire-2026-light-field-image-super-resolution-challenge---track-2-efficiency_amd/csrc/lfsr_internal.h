@@ -1,5 +1,6 @@
 // Internal (non-ABI) entry points shared between the translation units of liblfsr_hip.so.
 #pragma once
+#include <functional>
 #include <string>
 
 #include "lfsr_common.h"
@@ -291,3 +292,55 @@ int lfsr_trans_ffn_presplit(const LfsrParamTable& P, const std::string& pre, int
 // upsampling.0 / .3 and the bicubic skip: the fused tail at scales 2 and 4, else the HR map in hr and the two-kernel tail
 int lfsr_trans_tail(const LfsrTransSel& sel, const LfsrParamTable& P, const float* f, const float* x, float* out, float* hr, int B, int A, int h, int w, int s,
                     void* stream);
+
+// trans_bwd.hip: what the EPIT and LFT backwards share above the kernels, the mirror of the four forward stages above.
+inline size_t lfsr_tr3_floats() { return lfsr_packed_weight_tr_floats(64, 64, 9); }   // the 64 -> 64 3x3 data gradient's pack
+// geometry the training paths cover: every activation below 2 GiB (the widest rows: the 256-float q | k, and the HR map of 64 s^2 floats per LR pixel)
+bool lfsr_trans_train_geometry_ok(int A, int s, int B, int h, int w);
+size_t lfsr_trans_wgrad_partial_max(int B, int A, int h, int w);   // the largest partial slab of the weight gradients over all B A^2 h w pixels
+// the scratch of the shared stages (rows = VCL pixels): the tail's hr / du (64 s^2), ptail and up0T; the head's r4 / d64 / t64 (64), xg9 (16) and
+// initT; a sublayer's lnt / dln / dsm / dso / dv (128), dh / dqk (256); part / pln: the weight gradients' and the LayerNorm backward's partials
+struct LfsrTransBwdWs {
+  float *hr, *du, *ptail, *up0T, *r4, *d64, *t64, *xg9, *initT[3], *lnt, *dh, *dln, *dsm, *dso, *dqk, *dv, *part, *pln;
+};
+// One backward's context and the launches its driver and the stages below are written in.
+struct LfsrTransBwd {
+  static constexpr float L = 0.2f;   // every LeakyReLU of both models
+  const LfsrParamTable& P;
+  float* gbase;                      // where G() points: the gradient bucket (EPIT's horizontal pass redirects it)
+  const LfsrTransBwdWs& ws;
+  int B, A, h, w, S, nimg, npix;
+  hipStream_t st;
+  LfsrTransBwd(const LfsrParamTable& P_, float* grads, const LfsrTransBwdWs& ws_, int B_, int A_, int h_, int w_, int S_, hipStream_t st_)
+      : P(P_), gbase(grads), ws(ws_), B(B_), A(A_), h(h_), w(w_), S(S_), nimg(B_ * A_ * A_), npix(B_ * A_ * A_ * h_ * w_), st(st_) {}
+  float* G(const std::string& k) const;
+  // 1x1 data gradient Y (N columns) = X (dense rows of cin in {64, 128, 256, 576, 1024}) . WT, then * (Mk > 0 ? 1 : 0) (ReLU'), then + R1 (may alias Y)
+  int dgemm(const float* X, int cin, const float* WT, float* Y, int ys, const float* R1, int r1s, const float* Mk, int mks, int N) const;
+  // weight gradient of output rows [n0, n0 + N) (N <= 64) of a raw (O, C, T) weight: partial slabs, then the fixed-order reduce
+  int wgrad(int xm, const float* Gr, int gs, int go, const float* X, int xs, int M, int N, int K, int ntaps, float* dW, int accumulate, int c_valid = 0) const;
+  // every 64-row slice of a (O, K) linear weight's gradient: Gr (O columns, stride gs) against X (K columns), over all pixels
+  int wgrad_lin(const float* Gr, int gs, int O, const float* X, int xs, int K, float* dW) const;
+  int ew(int C, const float* a, const float* b, const float* mk, float slope, float* d) const;   // lfsr_ew_launch on dense rows of C, over all pixels
+  // LayerNorm backward with the gradients of its affine parameters written to G(gkey) / G(bkey); no position embedding: pe = nullptr, pe_rows = pe_div = 1
+  int ln_bwd(int C, const float* X, const float* pe, long long pe_rows, long long pe_div, const std::string& gkey, const std::string& bkey, const float* dy,
+             const float* r, float* dxo) const;
+  // 64 -> 64 3x3 data gradient into dense rows of 64: dxo = conv^T(dy) * lrelu'(mk) + r1 (mk, r1 optional)
+  int dgrad3(const float* dy, int dys, int dyo, const float* wT, float* dxo, const float* r1, const float* mk) const;
+  int packT(const float* Wp, int n0, int C, int O, float* o) const;   // 1x1 dgrad pack of rows [n0, n0 + O) of a (Npad_in, C) forward pack: [C][O]
+  int pack3T(const std::string& key, float* o) const;                 // dgrad pack of a 64 -> 64 3x3 weight, with its Winograd copies
+};
+// lfsr_trans_tail in reverse: from dout and the tail's input xin to dX = dL/d xin; writes the upsampling.3 and upsampling.0 gradients
+int lfsr_trans_tail_bwd(const LfsrTransBwd& k, const float* dout, const float* xin, float* dX);
+// lfsr_trans_head in reverse: from dbuf0 = dL/d buf0 and the saved f0 / c1 / c2; writes the four conv_init* gradients
+int lfsr_trans_head_bwd(const LfsrTransBwd& k, const float* x, const float* f0, const float* c1, const float* c2, const float* dbuf0);
+// the attention backward of a sublayer, the driver's choice of kernel and geometry: (q | k, v, o, d_o) -> (dqk, dv)
+using LfsrAttnBwd = std::function<int(const float* qk, const float* v, const float* o, const float* d_o, float* dqk, float* dv)>;
+// lfsr_trans_ffn and lfsr_trans_qkv in reverse, one attention + feed-forward sublayer of width E (key prefix `pre`), from dy = dL/d y to the token:
+//   y = x2 + FFN(LayerNorm(x2)), x2 = out_proj(ao) + tok, ao = attention(q | k, v), q | k = LayerNorm(tok + pe) W[0:2E]^T, v = tok W[2E:3E]^T.
+// hid (2E) receives the hidden rows after the ReLU, rebuilt; lin: the five dgrad packs of lfsr_trans_sublayer_packs.  dtok = dL/d x2 + the v path's
+// share of dL/d tok; ln_dx = the norm's share (+ ln_r, which may alias it).
+int lfsr_trans_sublayer_bwd(const LfsrTransBwd& k, const std::string& pre, int E, const float* dy, const float* x2, const float* ao, const float* qk,
+                            const float* v, const float* tok, const float* pe, long long pe_rows, long long pe_div, float* hid, float* const* lin,
+                            const LfsrAttnBwd& attn, float* dtok, const float* ln_r, float* ln_dx);
+// ... and its 1x1 dgrad packs [C_in][O]: feed_forward.4, feed_forward.1, out_proj and the q | k and v rows of in_proj_weight into lin[0..4]
+int lfsr_trans_sublayer_packs(const LfsrTransBwd& k, const std::string& pre, int E, float* const* lin);

@@ -8,12 +8,12 @@
 // Backward: data gradients are gather-GEMMs over transposed packs (gemm_gather_kernel.h) and the 64 -> 64 3x3 data-gradient kernel;
 // weight gradients are the two-pass partial-slab reduction of wgrad.hip.  The windowed attention backward (two gathers, one per query and one
 // per key: no float atomics), the LayerNorm backward with the position embedding added to its input, the tail's LeakyReLU / 3x3 conv backward
-// with the HR -> LR un-shuffle and the small fixed-order reductions are the kernels of trans_bwd.hip, which EPIT's backward shares.  Buckets
-// are bitwise reproducible.
+// with the HR -> LR un-shuffle and the small fixed-order reductions are the kernels of trans_bwd.hip, which EPIT's backward shares, as it does
+// the launch helpers (LfsrTransBwd) and the tail, head and sublayer stages the driver below is written in.  Buckets are bitwise reproducible.
+#include <algorithm>
 #include <string>
 #include <vector>
 
-#include "gemm_gather_kernel.h"
 #include "lft_ctx.h"
 
 namespace {
@@ -28,39 +28,17 @@ __global__ __launch_bounds__(256) void k_pe_reduce(const float* __restrict__ dln
 }
 
 // ---- workspace ------------------------------------------------------------------------------------------------------------------
-inline size_t tr3_floats() { return lfsr_packed_weight_tr_floats(64, 64, 9); }
-
-struct LftTrainWs {
+struct LftTrainWs : LfsrTransBwdWs {  // the base: the scratch of the stages EPIT shares
   LftFwdBufs f;                       // saved by forward_train (the scratch members point into the backward scratch below)
-  // backward scratch
-  float *hr, *du, *dx[2], *dbuf0, *dsf, *dh, *dln, *dln2, *dsm, *dso, *dqk, *dv, *dst, *lnt, *hid, *d64, *t64, *dspe, *xg9, *r4;
+  // backward scratch of the driver's own
+  float *dx[2], *dbuf0, *dsf, *dln2, *dst, *hid, *dspe;
   std::vector<float*> hid_a, hid_s;   // the feed-forward hidden rows (after the ReLU) the backward rebuilt, per layer: its ReLU decisions
   float4* stats;
-  float *part, *pln, *ptail;
-  // transposed packs, rebuilt from the current packed weights by every backward
-  float *up0T, *initT[3];
-  std::vector<float*> mloT, mhiT;
+  std::vector<float*> mloT, mhiT;     // transposed packs, rebuilt from the current packed weights by every backward
   float* lin[11];                     // one layer's 1x1 dgrad packs (rebuilt for every layer): see the backward
 };
 
-size_t wgrad_partial_max(int B, int A, int h, int w) {
-  const size_t npix = (size_t)B * A * A * h * w;
-  size_t m = 0;
-  auto up = [&](size_t v) { if (v > m) m = v; };
-  for (int K : {16, 64, 128, 256}) up(lfsr_wgrad_partial_floats((int)npix, 1, 64, K));
-  up(lfsr_wgrad_partial_floats((int)npix, 9, 64, 64));
-  up(lfsr_wgrad_partial_floats(h * w, 9, 64, 64));
-  return m;
-}
-
-// geometry the training path covers: every activation below 2 GiB (the forward's bound on the 256-float q | k rows, and the HR map of 64 s^2
-// floats per LR pixel that the backward rebuilds)
-bool train_geometry_ok(const lfsr_lft* c, int B, int h, int w) {
-  if (!c || B <= 0 || h <= 0 || w <= 0 || c->s < 2 || c->s > 4) return false;
-  const long long npix = (long long)B * c->A * c->A * h * w;
-  const long long widest = 64LL * c->s * c->s > 256 ? 64LL * c->s * c->s : 256;
-  return npix * widest * 4 < (1LL << 31);
-}
+bool train_geometry_ok(const lfsr_lft* c, int B, int h, int w) { return c && lfsr_trans_train_geometry_ok(c->A, c->s, B, h, w); }
 
 void train_layout(const lfsr_lft* c, int B, int h, int w, LfsrArena& ws, LftTrainWs& t) {
   const int nl = c->nlayer, s2 = c->s * c->s;
@@ -85,14 +63,26 @@ void train_layout(const lfsr_lft* c, int B, int h, int w, LfsrArena& ws, LftTrai
   t.stats = reinterpret_cast<float4*>(ws.take(npix * 8 * 4));
   t.hid_a.clear(); t.hid_s.clear();
   for (int b = 0; b < nl; ++b) { t.hid_a.push_back(ws.take(npix * 128)); t.hid_s.push_back(ws.take(npix * 256)); }
-  t.part = ws.take(wgrad_partial_max(B, c->A, h, w)); t.pln = ws.take((size_t)LFSR_RED_BLOCKS * 256); t.ptail = ws.take((size_t)LFSR_RED_BLOCKS * 9 * 64);
+  // part: the position map's share of MLP.weight runs over the h w pixels of one view
+  t.part = ws.take(std::max(lfsr_trans_wgrad_partial_max(B, c->A, h, w), lfsr_wgrad_partial_floats(h * w, 9, 64, 64)));
+  t.pln = ws.take((size_t)LFSR_RED_BLOCKS * 256); t.ptail = ws.take((size_t)LFSR_RED_BLOCKS * 9 * 64);
   // the forward body's scratch (unfused LayerNorm outputs, two-launch feed-forward hidden rows, the unfused tail's HR map)
   f.n64 = t.t64; f.tn = t.lnt; f.lnf = t.dln2; f.ha = t.dh; f.hs = t.hid; f.hr = t.hr;
   t.up0T = ws.take((size_t)64 * 64 * s2);
-  for (int i = 0; i < 3; ++i) t.initT[i] = ws.take(tr3_floats());
+  for (int i = 0; i < 3; ++i) t.initT[i] = ws.take(lfsr_tr3_floats());
   t.mloT.clear(); t.mhiT.clear();
-  for (int b = 0; b < nl; ++b) { t.mloT.push_back(ws.take(tr3_floats())); t.mhiT.push_back(ws.take(tr3_floats())); }
+  for (int b = 0; b < nl; ++b) { t.mloT.push_back(ws.take(lfsr_tr3_floats())); t.mhiT.push_back(ws.take(lfsr_tr3_floats())); }
   for (float*& l : t.lin) l = ws.take(256 * 128);       // the largest: [128][256]
+}
+
+// a sublayer's attention backward: the VALU pair on rows of width E (q | k in rows of 2 E, 8 heads of hd floats), with the sequence / window
+// geometry of the forward's launch
+LfsrAttnBwd attn_bwd(int E, int hd, float4* stats, hipStream_t st, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2, int n1, int n2,
+                     long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2) {
+  return [=](const float* qk, const float* v, const float* o, const float* d_o, float* dqk, float* dv) {
+    return lfsr_attn_bwd_valu_launch(hd, qk, 2 * E, 0, E, v, E, o, d_o, E, dqk, dv, reinterpret_cast<float*>(stats), 8, ns0, ns1, ns2, bs0, bs1, bs2,
+                                     n1, n2, st1, st2, l1, r1, l2, r2, clip2, st);
+  };
 }
 
 }  // namespace
@@ -162,164 +152,59 @@ int lfsr_lft_backward(lfsr_lft* c, const float* x, const float* dout, int B, int
   LftTrainWs t;
   train_layout(c, B, h, w, ws, t);
   if (workspace_bytes < ws.bytes()) return LFSR_E_WS;
-  const int A = c->A, AA = A * A, S = c->s, s2 = S * S, nimg = B * AA, HW = h * w, nl = c->nlayer;
-  const int npix = nimg * HW;
-  const float L = 0.2f;
+  const int A = c->A, AA = A * A, HW = h * w, nl = c->nlayer;
   const LfsrParamTable& P = c->P;
   const LftFwdBufs& f = t.f;
   hipStream_t st = lfsr_stream(stream);
-  auto G = [&](const std::string& k) -> float* { return grads + P.grad_off(k); };
-  auto launched = [&]() -> int { LFSR_CHECK_LAUNCH(); return LFSR_OK; };
-  // 1x1 data gradient Y (N columns) = X (CIN columns) . WT, then * (Mk > 0 ? 1 : 0) (ReLU'), then + R1 (may alias Y)
-  auto dgemm = [&](auto launcher, const float* X, int xs, const float* WT, float* Y, int ys, const float* R1, int r1s, const float* Mk, int mks, int N) -> int {
-    GemmArgs p{};
-    p.X = X; p.x_stride = xs; p.Wp = WT; p.Y = Y; p.y_stride = ys; p.R1 = R1; p.r1_stride = r1s; p.Mk = Mk; p.mk_stride = mks; p.mk_slope = 0.0f;
-    p.M = npix; p.N = N; p.Npad = npad32(N); p.A = A; p.H = h; p.W = w; p.ntaps = 1; p.CH = N; p.slope = 1.0f; p.S = S;
-    return launcher(p, st);
-  };
-  // weight gradient of output rows [n0, n0 + N) (N <= 64) of a raw (O, C, T) weight: partial slabs, then the fixed-order reduce
-  auto wgrad = [&](int xm, const float* Gr, int gs, int go, const float* X, int xs, int M, int N, int K, int ntaps, float* dW, int accumulate,
-                   int c_valid = 0) -> int {
-    int r = lfsr_wgrad_launch(LFSR_IN_SAME, xm, Gr, gs, go, X, xs, 0, t.part, M, N, K, A, h, w, ntaps, st);
-    if (!r) r = lfsr_wgrad_reduce(t.part, lfsr_wgrad_splits(M, ntaps, K), nullptr, 0, dW, N, K, ntaps, 0, 0, accumulate, c_valid, 0, st);
-    return r;
-  };
-  // every 64-row slice of a (O, K) linear weight's gradient: G (O columns, stride gs) against X (K columns)
-  auto wgrad_lin = [&](const float* Gr, int gs, int O, const float* X, int xs, int K, float* dW) -> int {
-    for (int n0 = 0; n0 < O; n0 += 64) {
-      const int r = wgrad(LFSR_IN_SAME, Gr, gs, n0, X, xs, npix, 64, K, 1, dW + (size_t)n0 * K, 0);
-      if (r) return r;
-    }
-    return LFSR_OK;
-  };
-  auto ew = [&](const float* a, int as, const float* b, int bs, const float* mk, int ms, float slope, float* d, int ds, int C, long long M) -> int {
-    return lfsr_ew_launch(a, as, b, bs, mk, ms, slope, d, ds, C, M, st);
-  };
-  // LayerNorm backward with the gradients of its affine parameters written to dg / dbeta
-  auto ln_bwd = [&](int C, const float* X, const float* pe, long long pe_rows, long long pe_div, const std::string& gkey, const std::string& bkey,
-                    const float* dy, const float* r, float* dxo) -> int {
-    return lfsr_ln_bwd_launch(C, X, pe, pe_rows, pe_div, P.w(gkey), dy, r, dxo, t.pln, npix, G(gkey), G(bkey), st);
-  };
-  auto attn_bwd = [&](int hd, const float* qk, int qks, int kchoff, const float* V, int vs, const float* O, const float* dO, int os, float* dqk, float* dv,
-                      int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2, int n1, int n2, long long st1, long long st2,
-                      int l1, int r1, int l2, int r2, int clip2) -> int {
-    return lfsr_attn_bwd_valu_launch(hd, qk, qks, 0, kchoff, V, vs, O, dO, os, dqk, dv, reinterpret_cast<float*>(t.stats), 8, ns0, ns1, ns2, bs0, bs1, bs2,
-                                     n1, n2, st1, st2, l1, r1, l2, r2, clip2, st);
-  };
-  auto dgrad3 = [&](const float* dy, int dys, int dyo, const float* wT, float* dxo, const float* r1, const float* mk) -> int {
-    return lfsr_conv3x3_bwd_data(dy, dys, dyo, wT, dxo, 64, 0, r1, 64, 0, mk, 64, 0, L, nimg, h, w, st);
-  };
-  // 1x1 dgrad pack of rows [n0, n0 + O) of a (Npad_in, C) forward pack: [C][O]
-  auto packT = [&](const float* Wp, int n0, int C, int O, float* o) -> int { return lfsr_pack_T_from_fwd(Wp + (size_t)n0 * C, o, 1, O, C, O, 0, C, 0, st); };
-  auto pack3T = [&](const std::string& key, float* o) -> int {
-    LFSR_RC(lfsr_pack_T_from_fwd(P.w(key), o, 9, 64, 64, 64, 0, 64, 1, st));
-    return lfsr_pack_wino_m(o, o + LFSR_CONV3_WINO2_OFF, LFSR_W_ALL, st);   // the 64 -> 64 3x3 data gradient's Winograd copies
-  };
+  const LfsrTransBwd k(P, grads, t, B, A, h, w, c->s, st);
+  const int nimg = k.nimg, npix = k.npix;
 
-  // ---- tail: upsampling.0 (1x1 64 -> 64 s^2), PixelShuffle(s), LeakyReLU 0.2, 3x3 conv 64 -> 1, + bicubic skip (no parameters) ----------
-  LFSR_RC(lfsr_upsample_ps_fwd(f.x[nl], 64, 0, P.w("upsampling.0.weight"), t.hr, B, A, h, w, S, stream));   // the HR pre-activation, rebuilt
-  LFSR_RC(lfsr_tail_bwd_launch(dout, P.w("upsampling.3.weight"), t.hr, t.du, t.ptail, G("upsampling.3.weight"), B, A, h, w, S, L, st));
-  LFSR_RC(lfsr_pack_up0_T_launch(P.w("upsampling.0.weight"), t.up0T, s2, st));
+  // ---- tail ---------------------------------------------------------------------------------------------------------------------------
   float* dX = t.dx[0];   // the gradient at the altblock output (+ its skip): dL/d x[nl]
-  if (s2 == 4) LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 256, 2>, t.du, 256, t.up0T, dX, 64, nullptr, 0, nullptr, 0, 64));
-  else if (s2 == 9) LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 576, 2>, t.du, 576, t.up0T, dX, 64, nullptr, 0, nullptr, 0, 64));
-  else LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 1024, 2>, t.du, 1024, t.up0T, dX, 64, nullptr, 0, nullptr, 0, 64));
-  LFSR_RC(wgrad_lin(t.du, 64 * s2, 64 * s2, f.x[nl], 64, 64, G("upsampling.0.weight")));
+  LFSR_RC(lfsr_trans_tail_bwd(k, dout, f.x[nl], dX));
 
   // ---- altblock, reversed.  LFT.py:91 buffer = altblock(buffer) + buffer: dX also reaches buf0 directly ----------------------------------
-  LFSR_RC(ew(dX, 64, nullptr, 0, nullptr, 0, 1.0f, t.dbuf0, 64, 64, npix));
+  LFSR_RC(k.ew(64, dX, nullptr, nullptr, 1.0f, t.dbuf0));
   for (int b = nl - 1; b >= 0; --b) {
     const std::string sp = "altblock." + std::to_string(b) + ".spa_trans.", an = "altblock." + std::to_string(b) + ".ang_trans.";
     float** lin = t.lin;
-    // the layer's 1x1 dgrad packs: [C_in][O] of every linear weight (q | k and v as separate row ranges of in_proj)
-    LFSR_RC(packT(P.w(sp + "linear.0.weight"), 0, 128, 64, lin[0]));
-    LFSR_RC(packT(P.w(sp + "feed_forward.4.weight"), 0, 256, 128, lin[1]));
-    LFSR_RC(packT(P.w(sp + "feed_forward.1.weight"), 0, 128, 256, lin[2]));
-    LFSR_RC(packT(P.w(sp + "attention.out_proj.weight"), 0, 128, 128, lin[3]));
-    LFSR_RC(packT(P.w(sp + "attention.in_proj_weight"), 0, 128, 256, lin[4]));
-    LFSR_RC(packT(P.w(sp + "attention.in_proj_weight"), 256, 128, 128, lin[5]));
-    LFSR_RC(packT(P.w(an + "feed_forward.4.weight"), 0, 128, 64, lin[6]));
-    LFSR_RC(packT(P.w(an + "feed_forward.1.weight"), 0, 64, 128, lin[7]));
-    LFSR_RC(packT(P.w(an + "attention.out_proj.weight"), 0, 64, 64, lin[8]));
-    LFSR_RC(packT(P.w(an + "attention.in_proj_weight"), 0, 64, 128, lin[9]));
-    LFSR_RC(packT(P.w(an + "attention.in_proj_weight"), 128, 64, 64, lin[10]));
-    LFSR_RC(pack3T(sp + "MLP.weight#lo", t.mloT[b]));
-    LFSR_RC(pack3T(sp + "MLP.weight#hi", t.mhiT[b]));
+    // the layer's 1x1 dgrad packs: linear.0, then the five of either sublayer
+    LFSR_RC(k.packT(P.w(sp + "linear.0.weight"), 0, 128, 64, lin[0]));
+    LFSR_RC(lfsr_trans_sublayer_packs(k, sp, 128, lin + 1));
+    LFSR_RC(lfsr_trans_sublayer_packs(k, an, 64, lin + 6));
+    LFSR_RC(k.pack3T(sp + "MLP.weight#lo", t.mloT[b]));
+    LFSR_RC(k.pack3T(sp + "MLP.weight#hi", t.mhiT[b]));
 
     // ---- SpaTrans (LFT.py:188-203): x[b+1] = linear.0(sf), sf = sm + FFN(LN(sm)), sm = out_proj(attn) + st ----------------------
-    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, dX, 64, lin[0], t.dsf, 128, nullptr, 0, nullptr, 0, 128));
-    LFSR_RC(wgrad_lin(dX, 64, 64, f.sf[b], 128, 128, G(sp + "linear.0.weight")));
-    LFSR_RC(lfsr_layernorm_fwd(f.sm[b], 128, 0, nullptr, 0, 0, 1, P.w(sp + "feed_forward.0.weight"), P.w(sp + "feed_forward.0.bias"), t.lnt, 128, 0, npix, 128, 1e-5f, stream));
-    LFSR_RC(lfsr_linear_fwd(t.lnt, 128, 0, 128, P.w(sp + "feed_forward.1.weight"), nullptr, nullptr, 0, 0, t.hid_s[b], 256, 0, npix, 256, 0.0f, stream));   // ReLU(hidden)
-    LFSR_RC(wgrad_lin(t.dsf, 128, 128, t.hid_s[b], 256, 256, G(sp + "feed_forward.4.weight")));
-    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dsf, 128, lin[1], t.dh, 256, nullptr, 0, t.hid_s[b], 256, 256));
-    LFSR_RC(wgrad_lin(t.dh, 256, 256, t.lnt, 128, 128, G(sp + "feed_forward.1.weight")));
-    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 256, 2>, t.dh, 256, lin[2], t.dln, 128, nullptr, 0, nullptr, 0, 128));
-    LFSR_RC(ln_bwd(128, f.sm[b], nullptr, 1, 1, sp + "feed_forward.0.weight", sp + "feed_forward.0.bias", t.dln, t.dsf, t.dsm));
-    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dsm, 128, lin[3], t.dso, 128, nullptr, 0, nullptr, 0, 128));
-    LFSR_RC(wgrad_lin(t.dsm, 128, 128, f.so[b], 128, 128, G(sp + "attention.out_proj.weight")));
-    // window [i-2, i+3) x [j-2, min(h, j+3)): the column clamp uses h (LFT.py:168), as the forward
-    LFSR_RC(attn_bwd(16, f.sqk[b], 256, 128, f.sv[b], 128, f.so[b], t.dso, 128, t.dqk, t.dv, nimg, 1, 1, HW, 0, 0, h, w, w, 1, 2, 3, 2, 3, h));
-    // q | k = LN(st + spe) W[0:256]^T, v = st W[256:384]^T
-    LFSR_RC(lfsr_layernorm_fwd(f.st[b], 128, 0, f.spe[b], 128, HW, 1, P.w(sp + "norm.weight"), P.w(sp + "norm.bias"), t.lnt, 128, 0, npix, 128, 1e-5f, stream));
-    float* dWin = G(sp + "attention.in_proj_weight");
-    LFSR_RC(wgrad_lin(t.dqk, 256, 256, t.lnt, 128, 128, dWin));
-    LFSR_RC(wgrad_lin(t.dv, 128, 128, f.st[b], 128, 128, dWin + 256 * 128));
-    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 256, 2>, t.dqk, 256, lin[4], t.dln, 128, nullptr, 0, nullptr, 0, 128));
-    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dv, 128, lin[5], t.dst, 128, t.dsm, 128, nullptr, 0, 128));
-    LFSR_RC(ln_bwd(128, f.st[b], f.spe[b], HW, 1, sp + "norm.weight", sp + "norm.bias", t.dln, nullptr, t.dln2));
-    LFSR_RC(ew(t.dst, 128, t.dln2, 128, nullptr, 0, 1.0f, t.dst, 128, 128, npix));
+    LFSR_RC(k.dgemm(dX, 64, lin[0], t.dsf, 128, nullptr, 0, nullptr, 0, 128));
+    LFSR_RC(k.wgrad_lin(dX, 64, 64, f.sf[b], 128, 128, k.G(sp + "linear.0.weight")));
+    // window [i-2, i+3) x [j-2, min(h, j+3)): the column clamp uses h (LFT.py:168), as the forward.  q | k = LN(st + spe) W[0:256]^T: the
+    // LayerNorm's input gradient goes to dln2, dst = the rest of dL/d st
+    LFSR_RC(lfsr_trans_sublayer_bwd(k, sp, 128, t.dsf, f.sm[b], f.so[b], f.sqk[b], f.sv[b], f.st[b], f.spe[b], HW, 1, t.hid_s[b], lin + 1,
+                                    attn_bwd(128, 16, t.stats, st, nimg, 1, 1, HW, 0, 0, h, w, w, 1, 2, 3, 2, 3, h), t.dst, nullptr, t.dln2));
+    LFSR_RC(k.ew(128, t.dst, t.dln2, nullptr, 1.0f, t.dst));
     // st = MLP(unfold(ay)), spe = MLP(unfold(spa_position)): MLP.weight also gets the LayerNorm-input gradient summed over the images
     hipLaunchKernelGGL(k_pe_reduce, dim3(lfsr_blocks((long long)HW * 128, 256)), dim3(256), 0, st, t.dln2, t.dspe, nimg, HW);
-    LFSR_RC(launched());
-    float* dWm = G(sp + "MLP.weight");
+    LFSR_CHECK_LAUNCH();
+    float* dWm = k.G(sp + "MLP.weight");
     for (int half = 0; half < 2; ++half) {
-      LFSR_RC(wgrad(LFSR_IN_CONV3, t.dst, 128, 64 * half, f.ay[b], 64, npix, 64, 64, 9, dWm + half * 64 * 576, 0));
+      LFSR_RC(k.wgrad(LFSR_IN_CONV3, t.dst, 128, 64 * half, f.ay[b], 64, npix, 64, 64, 9, dWm + half * 64 * 576, 0));
       LFSR_RC(lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_CONV3, t.dspe, 128, 64 * half, f.spos, 64, 0, t.part, HW, 64, 64, 1, h, w, 9, st));
       LFSR_RC(lfsr_wgrad_reduce(t.part, lfsr_wgrad_splits(HW, 9, 64), nullptr, 0, dWm + half * 64 * 576, 64, 64, 9, 0, 0, 1, 0, 0, st));
     }
-    LFSR_RC(dgrad3(t.dst, 128, 0, t.mloT[b], t.d64, nullptr, nullptr));
-    LFSR_RC(dgrad3(t.dst, 128, 64, t.mhiT[b], t.t64, t.d64, nullptr));   // t64 = dL/d ay
+    LFSR_RC(k.dgrad3(t.dst, 128, 0, t.mloT[b], t.d64, nullptr, nullptr));
+    LFSR_RC(k.dgrad3(t.dst, 128, 64, t.mhiT[b], t.t64, t.d64, nullptr));   // t64 = dL/d ay
 
-    // ---- AngTrans (LFT.py:233-246): ay = am + FFN(LN(am)), am = out_proj(attn) + x[b] ---------------------------------------------
-    LFSR_RC(lfsr_layernorm_fwd(f.am[b], 64, 0, nullptr, 0, 0, 1, P.w(an + "feed_forward.0.weight"), P.w(an + "feed_forward.0.bias"), t.lnt, 64, 0, npix, 64, 1e-5f, stream));
-    LFSR_RC(lfsr_linear_fwd(t.lnt, 64, 0, 64, P.w(an + "feed_forward.1.weight"), nullptr, nullptr, 0, 0, t.hid_a[b], 128, 0, npix, 128, 0.0f, stream));
-    LFSR_RC(wgrad_lin(t.t64, 64, 64, t.hid_a[b], 128, 128, G(an + "feed_forward.4.weight")));
-    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.t64, 64, lin[6], t.dh, 128, nullptr, 0, t.hid_a[b], 128, 128));
-    LFSR_RC(wgrad_lin(t.dh, 128, 128, t.lnt, 64, 64, G(an + "feed_forward.1.weight")));
-    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dh, 128, lin[7], t.dln, 64, nullptr, 0, nullptr, 0, 64));
-    LFSR_RC(ln_bwd(64, f.am[b], nullptr, 1, 1, an + "feed_forward.0.weight", an + "feed_forward.0.bias", t.dln, t.t64, t.dsm));   // dsm: dL/d am (64)
-    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dsm, 64, lin[8], t.dso, 64, nullptr, 0, nullptr, 0, 64));
-    LFSR_RC(wgrad_lin(t.dsm, 64, 64, f.ao[b], 64, 64, G(an + "attention.out_proj.weight")));
-    LFSR_RC(attn_bwd(8, f.aqk[b], 128, 64, f.av[b], 64, f.ao[b], t.dso, 64, t.dqk, t.dv, B, h, w, (long long)AA * HW, w, 1, AA, 1, HW, 0, AA, AA, 0, 1, 0));
-    LFSR_RC(lfsr_layernorm_fwd(f.x[b], 64, 0, f.ape, 64, AA, HW, P.w(an + "norm.weight"), P.w(an + "norm.bias"), t.lnt, 64, 0, npix, 64, 1e-5f, stream));
-    dWin = G(an + "attention.in_proj_weight");
-    LFSR_RC(wgrad_lin(t.dqk, 128, 128, t.lnt, 64, 64, dWin));
-    LFSR_RC(wgrad_lin(t.dv, 64, 64, f.x[b], 64, 64, dWin + 128 * 64));
-    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 128, 2>, t.dqk, 128, lin[9], t.dln, 64, nullptr, 0, nullptr, 0, 64));
+    // ---- AngTrans (LFT.py:233-246): ay = am + FFN(LN(am)), am = out_proj(attn) + x[b], q | k = LN(x[b] + ape) W[0:128]^T ------------------
     float* dXp = t.dx[(nl - b) & 1];
-    LFSR_RC(dgemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dv, 64, lin[10], dXp, 64, t.dsm, 64, nullptr, 0, 64));
-    LFSR_RC(ln_bwd(64, f.x[b], f.ape, AA, HW, an + "norm.weight", an + "norm.bias", t.dln, dXp, dXp));
+    LFSR_RC(lfsr_trans_sublayer_bwd(k, an, 64, t.t64, f.am[b], f.ao[b], f.aqk[b], f.av[b], f.x[b], f.ape, AA, HW, t.hid_a[b], lin + 6,
+                                    attn_bwd(64, 8, t.stats, st, B, h, w, (long long)AA * HW, w, 1, AA, 1, HW, 0, AA, AA, 0, 1, 0), dXp, dXp, dXp));
     dX = dXp;
   }
 
-  // ---- init: buf0 = lrelu(conv_init.4(c2)) + f0, c2 = lrelu(conv_init.2(c1)), c1 = lrelu(conv_init.0(f0)), f0 = conv_init0(x) ------------
-  LFSR_RC(ew(t.dbuf0, 64, dX, 64, nullptr, 0, 1.0f, t.dbuf0, 64, 64, npix));
-  LFSR_RC(pack3T("conv_init.0.weight", t.initT[0]));
-  LFSR_RC(pack3T("conv_init.2.weight", t.initT[1]));
-  LFSR_RC(pack3T("conv_init.4.weight", t.initT[2]));
-  // conv_init.4's LeakyReLU output without the residual, for its mask (the forward's launch minus r1)
-  LFSR_RC(lfsr_conv3x3_fwd(f.c2, 64, 0, P.w("conv_init.4.weight"), t.r4, 64, 0, nullptr, 0, 0, nullptr, 0, 0, nimg, h, w, L, stream));
-  LFSR_RC(ew(t.dbuf0, 64, nullptr, 0, t.r4, 64, L, t.d64, 64, 64, npix));
-  LFSR_RC(wgrad(LFSR_IN_CONV3, t.d64, 64, 0, f.c2, 64, npix, 64, 64, 9, G("conv_init.4.weight"), 0));
-  LFSR_RC(dgrad3(t.d64, 64, 0, t.initT[2], t.t64, nullptr, f.c2));
-  LFSR_RC(wgrad(LFSR_IN_CONV3, t.t64, 64, 0, f.c1, 64, npix, 64, 64, 9, G("conv_init.2.weight"), 0));
-  LFSR_RC(dgrad3(t.t64, 64, 0, t.initT[1], t.d64, nullptr, f.c1));
-  LFSR_RC(wgrad(LFSR_IN_CONV3, t.d64, 64, 0, f.f0, 64, npix, 64, 64, 9, G("conv_init.0.weight"), 0));
-  LFSR_RC(dgrad3(t.d64, 64, 0, t.initT[0], t.t64, t.dbuf0, nullptr));
-  LFSR_RC(lfsr_init_gather9(x, t.xg9, B, A, h, w, st));
-  LFSR_RC(wgrad(LFSR_IN_SAME, t.t64, 64, 0, t.xg9, 16, npix, 64, 16, 1, G("conv_init0.0.weight"), 0, 9));
-  return LFSR_OK;
+  // ---- init -----------------------------------------------------------------------------------------------------------------------------
+  LFSR_RC(k.ew(64, t.dbuf0, dX, nullptr, 1.0f, t.dbuf0));
+  return lfsr_trans_head_bwd(k, x, f.f0, f.c1, f.c2, t.dbuf0);
 }
 
 }  // extern "C"

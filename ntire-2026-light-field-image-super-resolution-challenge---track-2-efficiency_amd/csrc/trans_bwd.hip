@@ -1,17 +1,17 @@
 // What the backward drivers of LFT (lft_train.hip) and EPIT (epit_train.hip) share beyond the gather-GEMMs and wgrad.hip: the elementwise
 // add / mask, the LayerNorm backward, the up-sampling tail's backward, and the windowed attention backward -- the operator entry
 // lfsr_window_attn_bwd and the VALU pair every geometry can run on (LFT's angular and spatial attention; EPIT's EPI attention outside the
-// coverage of attn_bwd_mfma.hip).  Every reduction runs in a fixed order: gradient buckets are bitwise reproducible.
+// coverage of attn_bwd_mfma.hip).  Every reduction runs in a fixed order: gradient buckets are bitwise reproducible.  After the kernels
+// and their launchers comes the drivers' shared host code: the context the two drivers are written in (LfsrTransBwd) and the three stages that
+// are the same graph in both models, the mirror of transformer.hip's lfsr_trans_head / _qkv / _ffn / _tail.
 #include <math.h>
 
-#include "lfsr_internal.h"
+#include <algorithm>
+
+#include "gemm_gather_kernel.h"
+#include "param_table.h"
 
 namespace {
-
-inline unsigned cap_grid(long long total, unsigned cap = 8192) {
-  unsigned g = lfsr_blocks(total, 256);
-  return g > cap ? cap : g;
-}
 
 // d = (a (+ b)) * (mk > 0 ? 1 : slope)  over C columns (C % 4 == 0); b, mk optional; a and d may alias
 __global__ __launch_bounds__(256) void k_ew(const float* a, int as, const float* __restrict__ b, int bs, const float* __restrict__ mk, int ms, float slope,
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_kv(AttnBwdArgs p) {
 }  // namespace
 
 int lfsr_ew_launch(const float* a, int as, const float* b, int bs, const float* mk, int ms, float slope, float* d, int ds, int C, long long M, hipStream_t st) {
-  hipLaunchKernelGGL(k_ew, dim3(cap_grid(M * C / 4)), dim3(256), 0, st, a, as, b, bs, mk, ms, slope, d, ds, C, M);
+  hipLaunchKernelGGL(k_ew, dim3(lfsr_cap_grid(M * C / 4)), dim3(256), 0, st, a, as, b, bs, mk, ms, slope, d, ds, C, M);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }
@@ -390,4 +390,130 @@ extern "C" int lfsr_window_attn_bwd(const float* qk, int qk_stride, int q_choff,
   }
   return lfsr_attn_bwd_valu_launch(hd, qk, qk_stride, q_choff, k_choff, v, v_stride, o, d_o, o_stride, dqk, dv, stats, nheads, ns0, ns1, ns2, bs0, bs1, bs2,
                                    n1, n2, st1, st2, l1, r1, l2, r2, clip2, lfsr_stream(stream));
+}
+
+// ---- the drivers' shared host code ---------------------------------------------------------------------------------------------------
+bool lfsr_trans_train_geometry_ok(int A, int s, int B, int h, int w) {
+  if (B <= 0 || h <= 0 || w <= 0 || s < 2 || s > 4) return false;
+  const long long npix = (long long)B * A * A * h * w;
+  const long long widest = 64LL * s * s > 256 ? 64LL * s * s : 256;
+  return npix * widest * 4 < (1LL << 31);
+}
+
+size_t lfsr_trans_wgrad_partial_max(int B, int A, int h, int w) {
+  const size_t npix = (size_t)B * A * A * h * w;
+  size_t m = lfsr_wgrad_partial_floats((int)npix, 9, 64, 64);
+  for (int K : {16, 64, 128, 256}) m = std::max(m, lfsr_wgrad_partial_floats((int)npix, 1, 64, K));
+  return m;
+}
+
+float* LfsrTransBwd::G(const std::string& k) const { return gbase + P.grad_off(k); }
+
+int LfsrTransBwd::dgemm(const float* X, int cin, const float* WT, float* Y, int ys, const float* R1, int r1s, const float* Mk, int mks, int N) const {
+  GemmArgs p{};
+  p.X = X; p.x_stride = cin; p.Wp = WT; p.Y = Y; p.y_stride = ys; p.R1 = R1; p.r1_stride = r1s; p.Mk = Mk; p.mk_stride = mks; p.mk_slope = 0.0f;
+  p.M = npix; p.N = N; p.Npad = npad32(N); p.A = A; p.H = h; p.W = w; p.ntaps = 1; p.CH = N; p.slope = 1.0f; p.S = S;
+  switch (cin) {
+    case 64: return launch_gemm<IN_SAME, OUT_SAME, 64, 2>(p, st);
+    case 128: return launch_gemm<IN_SAME, OUT_SAME, 128, 2>(p, st);
+    case 256: return launch_gemm<IN_SAME, OUT_SAME, 256, 2>(p, st);
+    case 576: return launch_gemm<IN_SAME, OUT_SAME, 576, 2>(p, st);
+    case 1024: return launch_gemm<IN_SAME, OUT_SAME, 1024, 2>(p, st);
+  }
+  return LFSR_E_ARG;
+}
+
+int LfsrTransBwd::wgrad(int xm, const float* Gr, int gs, int go, const float* X, int xs, int M, int N, int K, int ntaps, float* dW, int accumulate,
+                        int c_valid) const {
+  LFSR_RC(lfsr_wgrad_launch(LFSR_IN_SAME, xm, Gr, gs, go, X, xs, 0, ws.part, M, N, K, A, h, w, ntaps, st));
+  return lfsr_wgrad_reduce(ws.part, lfsr_wgrad_splits(M, ntaps, K), nullptr, 0, dW, N, K, ntaps, 0, 0, accumulate, c_valid, 0, st);
+}
+
+int LfsrTransBwd::wgrad_lin(const float* Gr, int gs, int O, const float* X, int xs, int K, float* dW) const {
+  for (int n0 = 0; n0 < O; n0 += 64) LFSR_RC(wgrad(LFSR_IN_SAME, Gr, gs, n0, X, xs, npix, 64, K, 1, dW + (size_t)n0 * K, 0));
+  return LFSR_OK;
+}
+
+int LfsrTransBwd::ew(int C, const float* a, const float* b, const float* mk, float slope, float* d) const {
+  return lfsr_ew_launch(a, C, b, C, mk, C, slope, d, C, C, npix, st);
+}
+
+int LfsrTransBwd::ln_bwd(int C, const float* X, const float* pe, long long pe_rows, long long pe_div, const std::string& gkey, const std::string& bkey,
+                         const float* dy, const float* r, float* dxo) const {
+  return lfsr_ln_bwd_launch(C, X, pe, pe_rows, pe_div, P.w(gkey), dy, r, dxo, ws.pln, npix, G(gkey), G(bkey), st);
+}
+
+int LfsrTransBwd::dgrad3(const float* dy, int dys, int dyo, const float* wT, float* dxo, const float* r1, const float* mk) const {
+  return lfsr_conv3x3_bwd_data(dy, dys, dyo, wT, dxo, 64, 0, r1, 64, 0, mk, 64, 0, L, nimg, h, w, st);
+}
+
+int LfsrTransBwd::packT(const float* Wp, int n0, int C, int O, float* o) const { return lfsr_pack_T_from_fwd(Wp + (size_t)n0 * C, o, 1, O, C, O, 0, C, 0, st); }
+
+int LfsrTransBwd::pack3T(const std::string& key, float* o) const {
+  LFSR_RC(lfsr_pack_T_from_fwd(P.w(key), o, 9, 64, 64, 64, 0, 64, 1, st));
+  return lfsr_pack_wino_m(o, o + LFSR_CONV3_WINO2_OFF, LFSR_W_ALL, st);   // the 64 -> 64 3x3 data gradient's Winograd copies
+}
+
+// upsampling.0 (1x1 64 -> 64 s^2), PixelShuffle(s), LeakyReLU 0.2, 3x3 conv 64 -> 1, + bicubic skip (no parameters)
+int lfsr_trans_tail_bwd(const LfsrTransBwd& k, const float* dout, const float* xin, float* dX) {
+  const LfsrTransBwdWs& s = k.ws;
+  const int s2 = k.S * k.S;
+  LFSR_RC(lfsr_upsample_ps_fwd(xin, 64, 0, k.P.w("upsampling.0.weight"), s.hr, k.B, k.A, k.h, k.w, k.S, k.st));   // the HR pre-activation, rebuilt
+  LFSR_RC(lfsr_tail_bwd_launch(dout, k.P.w("upsampling.3.weight"), s.hr, s.du, s.ptail, k.G("upsampling.3.weight"), k.B, k.A, k.h, k.w, k.S, k.L, k.st));
+  LFSR_RC(lfsr_pack_up0_T_launch(k.P.w("upsampling.0.weight"), s.up0T, s2, k.st));
+  LFSR_RC(k.dgemm(s.du, 64 * s2, s.up0T, dX, 64, nullptr, 0, nullptr, 0, 64));
+  return k.wgrad_lin(s.du, 64 * s2, 64 * s2, xin, 64, 64, k.G("upsampling.0.weight"));
+}
+
+// buf0 = lrelu(conv_init.4(c2)) + f0, c2 = lrelu(conv_init.2(c1)), c1 = lrelu(conv_init.0(f0)), f0 = conv_init0(x)
+int lfsr_trans_head_bwd(const LfsrTransBwd& k, const float* x, const float* f0, const float* c1, const float* c2, const float* dbuf0) {
+  const LfsrTransBwdWs& s = k.ws;
+  LFSR_RC(k.pack3T("conv_init.0.weight", s.initT[0]));
+  LFSR_RC(k.pack3T("conv_init.2.weight", s.initT[1]));
+  LFSR_RC(k.pack3T("conv_init.4.weight", s.initT[2]));
+  // conv_init.4's LeakyReLU output without the residual, for its mask (the forward's launch minus r1)
+  LFSR_RC(lfsr_conv3x3_fwd(c2, 64, 0, k.P.w("conv_init.4.weight"), s.r4, 64, 0, nullptr, 0, 0, nullptr, 0, 0, k.nimg, k.h, k.w, k.L, k.st));
+  LFSR_RC(k.ew(64, dbuf0, nullptr, s.r4, k.L, s.d64));
+  LFSR_RC(k.wgrad(LFSR_IN_CONV3, s.d64, 64, 0, c2, 64, k.npix, 64, 64, 9, k.G("conv_init.4.weight"), 0));
+  LFSR_RC(k.dgrad3(s.d64, 64, 0, s.initT[2], s.t64, nullptr, c2));
+  LFSR_RC(k.wgrad(LFSR_IN_CONV3, s.t64, 64, 0, c1, 64, k.npix, 64, 64, 9, k.G("conv_init.2.weight"), 0));
+  LFSR_RC(k.dgrad3(s.t64, 64, 0, s.initT[1], s.d64, nullptr, c1));
+  LFSR_RC(k.wgrad(LFSR_IN_CONV3, s.d64, 64, 0, f0, 64, k.npix, 64, 64, 9, k.G("conv_init.0.weight"), 0));
+  LFSR_RC(k.dgrad3(s.d64, 64, 0, s.initT[0], s.t64, dbuf0, nullptr));
+  LFSR_RC(lfsr_init_gather9(x, s.xg9, k.B, k.A, k.h, k.w, k.st));
+  return k.wgrad(LFSR_IN_SAME, s.t64, 64, 0, s.xg9, 16, k.npix, 64, 16, 1, k.G("conv_init0.0.weight"), 0, 9);
+}
+
+int lfsr_trans_sublayer_packs(const LfsrTransBwd& k, const std::string& pre, int E, float* const* lin) {
+  LFSR_RC(k.packT(k.P.w(pre + "feed_forward.4.weight"), 0, 2 * E, E, lin[0]));
+  LFSR_RC(k.packT(k.P.w(pre + "feed_forward.1.weight"), 0, E, 2 * E, lin[1]));
+  LFSR_RC(k.packT(k.P.w(pre + "attention.out_proj.weight"), 0, E, E, lin[2]));
+  LFSR_RC(k.packT(k.P.w(pre + "attention.in_proj_weight"), 0, E, 2 * E, lin[3]));
+  return k.packT(k.P.w(pre + "attention.in_proj_weight"), 2 * E, E, E, lin[4]);
+}
+
+int lfsr_trans_sublayer_bwd(const LfsrTransBwd& k, const std::string& pre, int E, const float* dy, const float* x2, const float* ao, const float* qk,
+                            const float* v, const float* tok, const float* pe, long long pe_rows, long long pe_div, float* hid, float* const* lin,
+                            const LfsrAttnBwd& attn, float* dtok, const float* ln_r, float* ln_dx) {
+  const LfsrParamTable& P = k.P;
+  const LfsrTransBwdWs& s = k.ws;
+  // the feed-forward: its LayerNorm (into lnt) and hidden rows are recomputed
+  LFSR_RC(lfsr_layernorm_fwd(x2, E, 0, nullptr, 0, 0, 1, P.w(pre + "feed_forward.0.weight"), P.w(pre + "feed_forward.0.bias"), s.lnt, E, 0, k.npix, E, 1e-5f, k.st));
+  LFSR_RC(lfsr_linear_fwd(s.lnt, E, 0, E, P.w(pre + "feed_forward.1.weight"), nullptr, nullptr, 0, 0, hid, 2 * E, 0, k.npix, 2 * E, 0.0f, k.st));   // ReLU(hidden)
+  LFSR_RC(k.wgrad_lin(dy, E, E, hid, 2 * E, 2 * E, k.G(pre + "feed_forward.4.weight")));
+  LFSR_RC(k.dgemm(dy, E, lin[0], s.dh, 2 * E, nullptr, 0, hid, 2 * E, 2 * E));
+  LFSR_RC(k.wgrad_lin(s.dh, 2 * E, 2 * E, s.lnt, E, E, k.G(pre + "feed_forward.1.weight")));
+  LFSR_RC(k.dgemm(s.dh, 2 * E, lin[1], s.dln, E, nullptr, 0, nullptr, 0, E));
+  LFSR_RC(k.ln_bwd(E, x2, nullptr, 1, 1, pre + "feed_forward.0.weight", pre + "feed_forward.0.bias", s.dln, dy, s.dsm));   // dsm = dL/d x2
+  LFSR_RC(k.dgemm(s.dsm, E, lin[2], s.dso, E, nullptr, 0, nullptr, 0, E));
+  LFSR_RC(k.wgrad_lin(s.dsm, E, E, ao, E, E, k.G(pre + "attention.out_proj.weight")));
+  LFSR_RC(attn(qk, v, ao, s.dso, s.dqk, s.dv));
+  // the in-projection: its LayerNorm is recomputed
+  LFSR_RC(lfsr_layernorm_fwd(tok, E, 0, pe, pe ? E : 0, pe ? pe_rows : 0, pe_div, P.w(pre + "norm.weight"), P.w(pre + "norm.bias"), s.lnt, E, 0, k.npix, E, 1e-5f, k.st));
+  float* dWin = k.G(pre + "attention.in_proj_weight");
+  LFSR_RC(k.wgrad_lin(s.dqk, 2 * E, 2 * E, s.lnt, E, E, dWin));
+  LFSR_RC(k.wgrad_lin(s.dv, E, E, tok, E, E, dWin + 2 * E * E));
+  LFSR_RC(k.dgemm(s.dqk, 2 * E, lin[3], s.dln, E, nullptr, 0, nullptr, 0, E));
+  LFSR_RC(k.dgemm(s.dv, E, lin[4], dtok, E, s.dsm, E, nullptr, 0, E));
+  return k.ln_bwd(E, tok, pe, pe_rows, pe_div, pre + "norm.weight", pre + "norm.bias", s.dln, ln_r, ln_dx);
 }
