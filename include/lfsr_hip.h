@@ -456,7 +456,8 @@ int lfsr_epiconv_hv_bwd(const float* dy, int dy_stride, int choff_h, int choff_v
  * hence every such conv of the four model drivers' forward and forward_train) changes: its activations and weights are rounded to bf16 (nearest even), the products
  * are exact and accumulation, LeakyReLU and residual adds are fp32; activations stay fp32 in memory.  Everything else runs exactly as under LFSR_ARITH_DEFAULT (the
  * GEMMs keep their exact three-term bf16 form, lfsr_distg_branch_tail_fwd covers what it covers there): lfsr_conv3x3_n_fwd, LF_InterNet's 128 -> 64 convs, the
- * angular branch, the attention kernels, unaligned conv operands (fp32 gather-GEMM) and every data- and weight-gradient kernel do not change.  A backward after a
+ * angular branch, the attention kernels, unaligned conv operands (fp32 gather-GEMM) and every data- and weight-gradient kernel do not change (the gradients have a
+ * switch of their own: lfsr_set_grad_arithmetic below).  A backward after a
  * forward_train in this mode differentiates the fp32 layers at that forward's activations, as autocast does; parity with the reference's gradients is claimed only
  * in the other two modes. */
 #define LFSR_ARITH_DEFAULT 0
@@ -464,6 +465,26 @@ int lfsr_epiconv_hv_bwd(const float* dy, int dy_stride, int choff_h, int choff_v
 #define LFSR_ARITH_BF16 2
 int lfsr_set_arithmetic(int mode);
 int lfsr_get_arithmetic(void);
+
+/* ---- arithmetic of the 64 -> 64 per-view 3x3 conv's GRADIENTS: a second process-wide selection, independent of lfsr_set_arithmetic, read at every launch ----
+ * LFSR_GRAD_ARITH_DEFAULT: every gradient kernel as it is (fp32 MFMA, Winograd forms), bit for bit.
+ * LFSR_GRAD_ARITH_BF16: opt-in, the backward counterpart of LFSR_ARITH_BF16.  Two operators change:
+ *  - the data gradient of that conv (lfsr_conv3x3_dgrad, and inside the drivers every call of the 3x3 dispatcher in its gradient direction, both with one and with
+ *    two residuals, on 16-B aligned operands: the 64 -> 64 3x3 data gradients of lfsr_distgssr_backward, lfsr_epit_backward, lfsr_lft_backward and
+ *    lfsr_internet_backward all follow the mode): dy and the transposed weight are rounded to bf16 (nearest even), the products are exact, accumulation, the
+ *    LeakyReLU mask and the residual adds are fp32;
+ *  - the weight gradient of that conv where it runs on the tile kernel (lfsr_conv3x3_wgrad and lfsr_distgssr_backward): dy and x are rounded to bf16, products
+ *    exact, fp32 accumulation into the same per-block partial slabs, the same reduction.  lfsr_conv3x3_wgrad_workspace_floats does not depend on the mode.
+ * What does not change: gradients, activations and slabs stay fp32 in memory; the forward (it does not read this switch); the EPI, angular, fuse.0, 1x1,
+ * 128 -> 64 and up-sampling gradients; the transformers' GEMM gradients; unaligned data-gradient operands (fp32 gather-GEMM); strides the bf16 weight-gradient
+ * kernel does not cover (the default kernel); and the 3x3 weight gradients of the EPIT, LFT and LF_InterNet drivers, which run through the generic gather
+ * weight-gradient kernel.  bf16 keeps fp32's exponent range: no loss scaling is needed.  Both kernels are free of atomics: two runs give the same bits, and an
+ * image's data gradient does not depend on how many images the launch has.  Parity with the reference's fp32 gradients is claimed only in the default mode
+ * (error against fp64 autograd under the mode: below torch.autocast(bfloat16)'s on every parameter, tests/test_gpu_grad_bf16.py). */
+#define LFSR_GRAD_ARITH_DEFAULT 0
+#define LFSR_GRAD_ARITH_BF16 1
+int lfsr_set_grad_arithmetic(int mode);   /* LFSR_E_ARG for any other value, nothing changed */
+int lfsr_get_grad_arithmetic(void);
 
 /* ---- operator-level timing hooks (measurement aid; the reference times whole forwards only: check_efficiency_official.py:306-330) ----
  * lfsr_op_profile(1): from now on every instrumented operator entry point brackets its launches with a hipEvent pair on its launch stream (and any

@@ -82,6 +82,8 @@ SIGNATURES = {
     "lfsr_epiconv_hv_bwd": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_i, c_i, c_i, c_i, c_f, c_p]),
     "lfsr_set_arithmetic": (c_i, [c_i]),
     "lfsr_get_arithmetic": (c_i, []),
+    "lfsr_set_grad_arithmetic": (c_i, [c_i]),
+    "lfsr_get_grad_arithmetic": (c_i, []),
     "lfsr_op_profile": (c_i, [c_i]),
     "lfsr_op_profile_read": (C.c_longlong, [C.c_char_p, c_sz]),
     "lfsr_distgssr_profile": (c_i, [c_p, c_i]),
@@ -182,6 +184,20 @@ def set_arithmetic(mode):
 def get_arithmetic():
     """lfsr_get_arithmetic: the mode the next launch runs in"""
     return int(load().lfsr_get_arithmetic())
+
+
+GRAD_ARITH_DEFAULT, GRAD_ARITH_BF16 = 0, 1
+
+
+def set_grad_arithmetic(mode):
+    """lfsr_set_grad_arithmetic: GRAD_ARITH_DEFAULT (every gradient kernel as it is) or GRAD_ARITH_BF16 (the 64 -> 64 per-view 3x3 conv's data and weight
+    gradients round their operands to bf16, fp32 accumulation); process-wide, independent of set_arithmetic"""
+    check(load().lfsr_set_grad_arithmetic(int(mode)), "set_grad_arithmetic")
+
+
+def get_grad_arithmetic():
+    """lfsr_get_grad_arithmetic: the mode the next gradient launch runs in"""
+    return int(load().lfsr_get_grad_arithmetic())
 
 
 def op_profile(enable):

@@ -1,6 +1,7 @@
 // The 64 -> 64 3x3 conv as one operator: which of its kernels runs a given call (forward: lfsr_conv3x3_fwd; data gradient: lfsr_conv3x3_bwd_data / _bwd_data_r2).
 // The kernels and their launchers are conv3x3_wino4.hip (F(4x4,3x3), the product path), conv3x3_wino.hip (F(2x2,3x3)), conv3x3_halo.hip (direct 9-tap), the
-// gather-GEMM of gemm_gather.hip, and conv3x3_bf16.hip (direct 9-tap on bf16 operands: the forward under LFSR_ARITH_BF16).  Host code only.
+// gather-GEMM of gemm_gather.hip, and conv3x3_bf16.hip / conv3x3_bf16_dgrad.hip (direct 9-tap on bf16 operands: the forward under LFSR_ARITH_BF16, the data gradient
+// under LFSR_GRAD_ARITH_BF16).  Host code only.
 #include "lfsr_internal.h"
 
 namespace {
@@ -48,6 +49,8 @@ int lfsr_conv3x3_run(const LfsrConv3& c, bool dgrad, hipStream_t st) {
   int rc = LFSR_E_ARG;
   // lfsr_set_arithmetic(LFSR_ARITH_BF16): a forward call with nothing selected runs on bf16 operands; what that launcher does not cover goes down the chain in fp32
   if (!dgrad && lfsr_arith_bf16() && lfsr_conv3_fwd_sel() == LFSR_C3_DEFAULT) rc = lfsr_conv3x3_bf16_launch(c, st);
+  // lfsr_set_grad_arithmetic(LFSR_GRAD_ARITH_BF16): likewise a data gradient (with one or two residuals) with nothing selected
+  if (dgrad && lfsr_grad_arith_bf16() && lfsr_conv3_dgrad_sel() == LFSR_C3_DEFAULT) rc = lfsr_conv3x3_bf16_dgrad_launch(c, st);
   for (int i = 0; i < 2 && chain[i] != END && rc == LFSR_E_ARG; ++i)
     rc = chain[i] == WINO4 ? lfsr_conv3x3_wino4_launch(c, st) : chain[i] == WINO2 ? lfsr_conv3x3_wino2_launch(c, st)
        : chain[i] == HALO ? lfsr_conv3x3_halo_launch(c, st) : lfsr_conv3x3_gather_launch(c, st);

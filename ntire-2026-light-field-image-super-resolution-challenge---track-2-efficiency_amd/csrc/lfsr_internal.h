@@ -91,6 +91,7 @@ int lfsr_conv3x3_halo_tail_launch(const LfsrConv3& c, int tile_begin, int tile_c
 int lfsr_conv3x3_wino2_launch(const LfsrConv3& c, hipStream_t st);                                     // conv3x3_wino.hip: F(2x2,3x3); operand spans below 2 GiB
 int lfsr_conv3x3_wino4_launch(const LfsrConv3& c, hipStream_t st);                                     // conv3x3_wino4.hip: F(4x4,3x3); operand spans below 1 GiB
 int lfsr_conv3x3_bf16_launch(const LfsrConv3& c, hipStream_t st);                                      // conv3x3_bf16.hip: direct 9-tap form on bf16 operands, forward only (LFSR_ARITH_BF16)
+int lfsr_conv3x3_bf16_dgrad_launch(const LfsrConv3& c, hipStream_t st);                                // conv3x3_bf16_dgrad.hip: ... with the gradient's mask operand (LFSR_GRAD_ARITH_BF16)
 int lfsr_conv3x3_gather_launch(const LfsrConv3& c, hipStream_t st);                                    // gemm_gather.hip: gather-GEMM, no alignment demand on y / r1 / r2 / mk
 // conv3x3.cpp: which kernel runs.  LFSR_CONV3X3 selects the forward kernel, LFSR_DGRAD3 (same vocabulary) the data-gradient kernel, which otherwise follows
 // LFSR_CONV3X3.  The selection is read when weights are packed AND at every launch: set it before loading a model.
@@ -243,6 +244,9 @@ int lfsr_wgrad_epi0_blocks(int B, int A, int h, int w, int vert);
 int lfsr_ang0_dgrad_launch(const float* dA16, const float* w_direct, float* dx, int dx_stride, int dx_choff, int B, int A, int h, int w, hipStream_t st);
 int lfsr_epi0_dgrad_launch(const float* dE, const float* w_direct, float* dx, int dx_stride, int dx_choff, int B, int A, int h, int w, int vert, hipStream_t st);
 int lfsr_wgrad_epi0_launch(const float* dE, const float* dE_v, const float* X, int x_stride, int x_choff, float* P, int B, int A, int h, int w, int vert, hipStream_t st);
+// wgrad_bf16.hip: the same contract on bf16-rounded operands (LFSR_GRAD_ARITH_BF16); writes all `blocks` slabs; LFSR_E_ARG = not covered, the fp32 kernel runs
+int lfsr_wgrad_conv3_bf16_launch(const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff, float* P,
+                                 int n_img, int h, int w, int blocks, hipStream_t st);
 int lfsr_wgrad_conv3_launch(const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff, float* P,
                             int n_img, int h, int w, hipStream_t st);
 // c_valid < C: only the first c_valid input channels are written, with row length c_valid (init_conv's 9 taps)

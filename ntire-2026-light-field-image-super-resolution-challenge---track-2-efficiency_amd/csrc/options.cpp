@@ -1,5 +1,6 @@
 // Library-wide options of liblfsr_hip.so.
 //  * lfsr_set_arithmetic: which arithmetic the GEMMs that have two forms run in, or bf16 operands for the 64 -> 64 3x3 forward conv (the product-level choice);
+//  * lfsr_set_grad_arithmetic: bf16 operands for the 64 -> 64 3x3 conv's data and weight gradients, independent of the first;
 //  * lfsr_sel: the A/B selectors of the measurement / parity tooling (LFSR_* environment variables), live only in a process started with LFSR_LAB set.
 #include <stdlib.h>
 
@@ -7,6 +8,7 @@
 
 namespace {
 std::atomic<int> g_arith{LFSR_ARITH_DEFAULT};
+std::atomic<int> g_grad_arith{LFSR_GRAD_ARITH_DEFAULT};
 std::atomic<int> g_lab{-1};
 }  // namespace
 
@@ -21,6 +23,7 @@ const char* lfsr_sel(const char* name) {
 
 bool lfsr_arith_f32() { return g_arith.load(std::memory_order_relaxed) == LFSR_ARITH_F32; }
 bool lfsr_arith_bf16() { return g_arith.load(std::memory_order_relaxed) == LFSR_ARITH_BF16; }
+bool lfsr_grad_arith_bf16() { return g_grad_arith.load(std::memory_order_relaxed) == LFSR_GRAD_ARITH_BF16; }
 
 extern "C" {
 
@@ -31,5 +34,13 @@ int lfsr_set_arithmetic(int mode) {
 }
 
 int lfsr_get_arithmetic(void) { return g_arith.load(); }
+
+int lfsr_set_grad_arithmetic(int mode) {
+  if (mode != LFSR_GRAD_ARITH_DEFAULT && mode != LFSR_GRAD_ARITH_BF16) return LFSR_E_ARG;
+  g_grad_arith.store(mode);
+  return LFSR_OK;
+}
+
+int lfsr_get_grad_arithmetic(void) { return g_grad_arith.load(); }
 
 }  // extern "C"

@@ -697,6 +697,11 @@ int lfsr_wgrad_conv3_launch(const float* G, int g_stride, int g_choff, const flo
     if (e != hipSuccess) return LFSR_HIP_ERR(e);
     attr_set[dev] = true;
   }
+  // lfsr_set_grad_arithmetic(LFSR_GRAD_ARITH_BF16) with nothing selected: bf16 operands, the same slabs; what that kernel does not cover runs below in fp32
+  if (lfsr_grad_arith_bf16() && !lfsr_sel("LFSR_WGRAD3")) {
+    const int rc = lfsr_wgrad_conv3_bf16_launch(G, g_stride, g_choff, X, x_stride, x_choff, P, n_img, h, w, lfsr_wgrad_conv3_blocks(n_img, h, w), st);
+    if (rc != LFSR_E_ARG) return rc;
+  }
   if (wgrad3_wino()) {
     Wgrad3Args q{};
     q.G = G; q.g_stride = g_stride; q.g_choff = g_choff; q.X = X; q.x_stride = x_stride; q.x_choff = x_choff; q.P = P;
