@@ -84,6 +84,8 @@ SIGNATURES = {
     "lfsr_get_arithmetic": (c_i, []),
     "lfsr_set_grad_arithmetic": (c_i, [c_i]),
     "lfsr_get_grad_arithmetic": (c_i, []),
+    "lfsr_set_gemm_arithmetic": (c_i, [c_i]),
+    "lfsr_get_gemm_arithmetic": (c_i, []),
     "lfsr_op_profile": (c_i, [c_i]),
     "lfsr_op_profile_read": (C.c_longlong, [C.c_char_p, c_sz]),
     "lfsr_distgssr_profile": (c_i, [c_p, c_i]),
@@ -198,6 +200,20 @@ def set_grad_arithmetic(mode):
 def get_grad_arithmetic():
     """lfsr_get_grad_arithmetic: the mode the next gradient launch runs in"""
     return int(load().lfsr_get_grad_arithmetic())
+
+
+GEMM_ARITH_DEFAULT, GEMM_ARITH_BF16 = 0, 1
+
+
+def set_gemm_arithmetic(mode):
+    """lfsr_set_gemm_arithmetic: GEMM_ARITH_DEFAULT (the transformer GEMMs as they are) or GEMM_ARITH_BF16 (the K = 64 / 128 bias-free linears, the LayerNorm + q | k | v
+    projections and the feed-forward blocks round their operands to bf16, fp32 accumulation); process-wide, independent of set_arithmetic and set_grad_arithmetic"""
+    check(load().lfsr_set_gemm_arithmetic(int(mode)), "set_gemm_arithmetic")
+
+
+def get_gemm_arithmetic():
+    """lfsr_get_gemm_arithmetic: the mode the next linear / feed-forward launch runs in"""
+    return int(load().lfsr_get_gemm_arithmetic())
 
 
 def op_profile(enable):
@@ -385,7 +401,7 @@ class GraphedForward:
         self.graphs = {}
 
     def __call__(self, x):
-        key = (tuple(x.shape), x.device, x.dtype, get_arithmetic())      # the arithmetic is read at launch: a graph holds the kernels of the mode it was captured in
+        key = (tuple(x.shape), x.device, x.dtype, get_arithmetic(), get_gemm_arithmetic())      # both are read at launch: a graph holds the kernels of the modes it was captured in
         g = self.graphs.get(key)
         if g is None:
             static_x = x.clone()

@@ -243,6 +243,10 @@ int lfsr_ffn_ln_launch(const float* x, int x_stride, int x_choff, const float* l
   {   // default: the three-term bf16 form (ffn_b3.hip); LFSR_FFN=f32 keeps this file's fp32-MFMA kernel (A/B runs)
     const char* fsel = lfsr_sel("LFSR_FFN");
     if (!(fsel && fsel[0] == 'f') && !lfsr_arith_f32()) {
+      if (lfsr_gemm_arith_bf16()) {   // lfsr_set_gemm_arithmetic(bf16): bf16 operands (gemm_bf16.hip) where the shape is covered
+        const int rq = lfsr_ffn_bf16_launch(x, x_stride, x_choff, ln_g, ln_b, ln_eps, w1_packed, w2_packed, res, res_stride, res_choff, y, y_stride, y_choff, M, K1, H, N2, slope, st);
+        if (rq != LFSR_E_ARG) return rq;
+      }
       const int rc = lfsr_ffn_b3_launch(x, x_stride, x_choff, ln_g, ln_b, ln_eps, w1_packed, w2_packed, res, res_stride, res_choff, y, y_stride, y_choff, M, K1, H, N2, slope, st, wsplit);
       if (rc != LFSR_E_ARG) return rc;
     }

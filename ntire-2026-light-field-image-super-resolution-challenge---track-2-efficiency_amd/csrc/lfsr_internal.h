@@ -188,6 +188,15 @@ int lfsr_rowgemm_b3_dgrad_launch(const float* dy, int dy_stride, int dy_choff, c
                                  float* dx, int dx_stride, int dx_choff, long long M, int N, hipStream_t st);
 int lfsr_rowgemm_b3_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* res, int res_stride, int res_choff,
                            float* y, int y_stride, int y_choff, long long M, int N, float slope, hipStream_t st);
+// gemm_bf16.hip: the same three operators on bf16 operands (lfsr_set_gemm_arithmetic(LFSR_GEMM_ARITH_BF16)); LFSR_E_ARG = not covered, nothing written
+int lfsr_gemm_bf16_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* res, int res_stride, int res_choff,
+                          float* y, int y_stride, int y_choff, long long M, int N, float slope, hipStream_t st);
+int lfsr_gemm_bf16_ln_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* ln_g, const float* ln_b, float ln_eps, int ln_cols,
+                             const float* pe, int pe_stride, int pe_rows, int pe_div, float* y, int y_stride, int y_choff,
+                             float* y2, int y2_stride, int y2_choff, int split_n, long long M, int N, hipStream_t st);
+int lfsr_ffn_bf16_launch(const float* x, int x_stride, int x_choff, const float* ln_g, const float* ln_b, float ln_eps, const float* w1_packed, const float* w2_packed,
+                         const float* res, int res_stride, int res_choff, float* y, int y_stride, int y_choff,
+                         long long M, int K1, int H, int N2, float slope, hipStream_t st);
 int lfsr_rowgemm_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* bias,
                         const float* res, int res_stride, int res_choff, float* y, int y_stride, int y_choff, long long M, int N, float slope, hipStream_t st);
 

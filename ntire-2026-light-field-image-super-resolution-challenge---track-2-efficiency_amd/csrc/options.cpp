@@ -1,6 +1,7 @@
 // Library-wide options of liblfsr_hip.so.
 //  * lfsr_set_arithmetic: which arithmetic the GEMMs that have two forms run in, or bf16 operands for the 64 -> 64 3x3 forward conv (the product-level choice);
 //  * lfsr_set_grad_arithmetic: bf16 operands for the 64 -> 64 3x3 conv's data and weight gradients, independent of the first;
+//  * lfsr_set_gemm_arithmetic: bf16 operands for the transformer linears, LayerNorm + q | k | v projections and feed-forward blocks (gemm_bf16.hip), independent of both;
 //  * lfsr_sel: the A/B selectors of the measurement / parity tooling (LFSR_* environment variables), live only in a process started with LFSR_LAB set.
 #include <stdlib.h>
 
@@ -9,6 +10,7 @@
 namespace {
 std::atomic<int> g_arith{LFSR_ARITH_DEFAULT};
 std::atomic<int> g_grad_arith{LFSR_GRAD_ARITH_DEFAULT};
+std::atomic<int> g_gemm_arith{LFSR_GEMM_ARITH_DEFAULT};
 std::atomic<int> g_lab{-1};
 }  // namespace
 
@@ -24,6 +26,7 @@ const char* lfsr_sel(const char* name) {
 bool lfsr_arith_f32() { return g_arith.load(std::memory_order_relaxed) == LFSR_ARITH_F32; }
 bool lfsr_arith_bf16() { return g_arith.load(std::memory_order_relaxed) == LFSR_ARITH_BF16; }
 bool lfsr_grad_arith_bf16() { return g_grad_arith.load(std::memory_order_relaxed) == LFSR_GRAD_ARITH_BF16; }
+bool lfsr_gemm_arith_bf16() { return g_gemm_arith.load(std::memory_order_relaxed) == LFSR_GEMM_ARITH_BF16; }
 
 extern "C" {
 
@@ -42,5 +45,13 @@ int lfsr_set_grad_arithmetic(int mode) {
 }
 
 int lfsr_get_grad_arithmetic(void) { return g_grad_arith.load(); }
+
+int lfsr_set_gemm_arithmetic(int mode) {
+  if (mode != LFSR_GEMM_ARITH_DEFAULT && mode != LFSR_GEMM_ARITH_BF16) return LFSR_E_ARG;
+  g_gemm_arith.store(mode);
+  return LFSR_OK;
+}
+
+int lfsr_get_gemm_arithmetic(void) { return g_gemm_arith.load(); }
 
 }  // extern "C"

@@ -273,6 +273,11 @@ int lfsr_rowgemm_ln_launch(const float* x, int x_stride, int x_choff, int K, con
   {   // default: the three-term bf16 form (rowgemm_b3.hip); LFSR_ROWGEMM=f32 keeps the fp32-MFMA kernel below (bit-identical to LayerNorm launch + fp32 row-GEMM)
     const char* rsel = lfsr_sel("LFSR_ROWGEMM");
     if (!(rsel && (rsel[0] == 'f' || rsel[0] == '1')) && !lfsr_arith_f32()) {
+      if (lfsr_gemm_arith_bf16()) {   // lfsr_set_gemm_arithmetic(bf16): bf16 operands (gemm_bf16.hip) where the shape is covered
+        const int rq = lfsr_gemm_bf16_ln_launch(x, x_stride, x_choff, K, w_packed, ln_g, ln_b, ln_eps, ln_cols, pe, pe_stride, pe_rows, pe_div, y, y_stride, y_choff,
+                                                y2, y2_stride, y2_choff, split_n, M, N, st);
+        if (rq != LFSR_E_ARG) return rq;
+      }
       const int rc = lfsr_rowgemm_b3_ln_launch(x, x_stride, x_choff, K, w_packed, ln_g, ln_b, ln_eps, ln_cols, pe, pe_stride, pe_rows, pe_div, y, y_stride, y_choff,
                                                y2, y2_stride, y2_choff, split_n, M, N, st);
       if (rc != LFSR_E_ARG) return rc;
@@ -310,6 +315,10 @@ int lfsr_rowgemm_launch(const float* x, int x_stride, int x_choff, int K, const 
   // the bias-free K = 64 / 128 linears (the transformers' projections) run on the bf16 MFMA pipe with their fp32 operands split EXACTLY into three bf16 terms
   // (rowgemm_b3.hip; error against fp64 below this file's fp32-MFMA kernel: tools/b3_accuracy.py); LFSR_ROWGEMM=f32 keeps the fp32-MFMA form (A/B runs), 128 its wide tiles
   if (!(rsel && (rsel[0] == 'f' || rsel[0] == '1')) && !lfsr_arith_f32() && !bias && (K == 64 || K == 128 || K == 144)) {
+    if (lfsr_gemm_arith_bf16() && K != 144) {   // lfsr_set_gemm_arithmetic(bf16): bf16 operands (gemm_bf16.hip); K = 144 (DistgSSR's fuse.0) keeps the default
+      const int rq = lfsr_gemm_bf16_launch(x, x_stride, x_choff, K, w_packed, res, res_stride, res_choff, y, y_stride, y_choff, M, N, slope, st);
+      if (rq != LFSR_E_ARG) return rq;
+    }
     const int rc = lfsr_rowgemm_b3_launch(x, x_stride, x_choff, K, w_packed, res, res_stride, res_choff, y, y_stride, y_choff, M, N, slope, st);
     if (rc != LFSR_E_ARG) return rc;
   }
