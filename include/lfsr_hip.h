@@ -303,6 +303,31 @@ int lfsr_window_attn_bwd(const float* qk, int qk_stride, int q_choff, int k_chof
                          const float* o, const float* d_o, int o_stride, int o_choff, float* dqk, float* dv, float* stats,
                          int nheads, int hd, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
                          int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, void* stream);
+/* ---- the backward operators the LFT and EPIT training drivers share (the launchers those drivers call).  No float atomics: two runs give the same bits. ----
+ * LayerNorm backward of y = LN(x + pe[(row / pe_div) % pe_rows]) gamma + beta, eps 1e-5, over M rows; C in {64,128}.  x, dy, r, dx: dense rows of C floats;
+ * pe (NULL: none; else pe_rows > 0, pe_div > 0): dense rows of C; every pointer 16-byte aligned.  Writes dx = dL/dx (+ r if r is not NULL; r may be dx itself,
+ * no other operands may overlap), dgamma (C) and dbeta (C), both overwritten, and the workspace (lfsr_layernorm_bwd_workspace_floats(C) = 1024 * 2 C
+ * floats of per-block partials; 0 for an unsupported C).  LFSR_E_ARG / LFSR_E_WS before any launch. */
+size_t lfsr_layernorm_bwd_workspace_floats(int C);
+int lfsr_layernorm_bwd(const float* x, const float* pe, long long pe_rows, long long pe_div, const float* gamma, const float* dy, const float* r, float* dx,
+                       float* dgamma, float* dbeta, float* workspace, size_t workspace_floats, long long M, int C, void* stream);
+/* Data gradient of nn.Linear y = x W^T, W (cout, cin), with the extras of the transformer sublayers:  dx = (dy W) * (act > 0 ? 1 : 0) + r1.
+ * dy: M dense rows of cout in {64,128,256,576,1024}, 16-byte aligned; wT_packed from lfsr_pack_conv_weight_tr(W, cout, cin, 1); cin in {64,128,256}.
+ * dx, r1 (NULL: none), act (NULL: no mask; the saved ReLU output): rows of cin floats at row strides >= cin that are multiples of 4; r1 may be dx itself.
+ * Writes columns [0, cin) of the M rows of dx and nothing else.  M < 2^31 - 128.  LFSR_E_ARG before any launch. */
+int lfsr_linear_dgrad(const float* dy, int cout, const float* wT_packed, float* dx, int dx_stride, const float* r1, int r1_stride, const float* act, int act_stride,
+                      long long M, int cin, void* stream);
+/* Backward of lfsr_hr_tail_fwd's LeakyReLU(slope) + 3x3 conv 64 -> 1 (zero pad 1 over the whole mosaic), s in {2,3,4}:
+ * dout (B, 1, A h s, A w s); w3 (1, 64, 3, 3) raw; hr: the channel-last HR pre-activation (B, A h s, A w s, 64) of lfsr_upsample_ps_fwd.
+ * Writes du (B A^2 h w, 64 s^2), the gradient of upsampling.0's output un-shuffled to VCL rows p = (b, u, v, y, x) with columns c s^2 + i s + j
+ * (= dHR[b][(u h + y) s + i][(v w + x) s + j][c], LeakyReLU' = 1 for hr > 0, slope otherwise), dw3 (1, 64, 3, 3) overwritten, and the workspace
+ * (lfsr_up_tail_bwd_workspace_floats() = 1024 * 576 floats).  Every pointer 16-byte aligned; no overlap.  LFSR_E_ARG / LFSR_E_WS before any launch. */
+size_t lfsr_up_tail_bwd_workspace_floats(void);
+int lfsr_up_tail_bwd(const float* dout, const float* w3, const float* hr, float* du, float* dw3, float* workspace, size_t workspace_floats, int B, int A, int h, int w,
+                     int s, float slope, void* stream);
+/* the data-gradient pack of upsampling.0 (64 s^2, 64) from its forward pack (lfsr_pack_conv_weight perm 1, ch 64: row ij * 64 + c, 64 floats):
+ * out[k][c s^2 + ij] = w_packed[(ij * 64 + c) * 64 + k], 64 rows of 64 s^2 -- what lfsr_linear_dgrad(du, 64 s^2, out, ..., cin = 64) reads; s in {2,3,4} */
+int lfsr_pack_up0_weight_tr(const float* w_packed, float* out, int s, void* stream);
 /* per-view 3x3 conv 64 -> N for any N (gather-GEMM): LFT's unfold(3x3) + Linear(576 -> 128) token embedding (LFT.py:176-182) */
 int lfsr_conv3x3_n_fwd(const float* x, int x_stride, int x_choff, const float* w_packed, float* y, int y_stride, int y_choff,
                        int n_img, int h, int w, int N, float slope, void* stream);

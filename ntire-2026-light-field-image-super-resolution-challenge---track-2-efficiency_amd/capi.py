@@ -59,6 +59,12 @@ SIGNATURES = {
                                    C.c_longlong, C.c_longlong, C.c_longlong, c_i, c_i, C.c_longlong, C.c_longlong, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_window_attn_bwd": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i,
                                    C.c_longlong, C.c_longlong, C.c_longlong, c_i, c_i, C.c_longlong, C.c_longlong, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "lfsr_layernorm_bwd_workspace_floats": (c_sz, [c_i]),
+    "lfsr_layernorm_bwd": (c_i, [c_p, c_p, C.c_longlong, C.c_longlong, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_sz, C.c_longlong, c_i, c_p]),
+    "lfsr_linear_dgrad": (c_i, [c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_i, C.c_longlong, c_i, c_p]),
+    "lfsr_up_tail_bwd_workspace_floats": (c_sz, []),
+    "lfsr_up_tail_bwd": (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_sz, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "lfsr_pack_up0_weight_tr": (c_i, [c_p, c_p, c_i, c_p]),
     "lfsr_upsample_ps_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_up_tail_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
     "lfsr_hr_tail_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),

@@ -234,7 +234,9 @@ int lfsr_epi_attn_bwd_mfma_launch(const float* qk, int qk_stride, int q_choff, i
                                   int o_stride, float* dqk, float* dv, int nheads, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
                                   int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, hipStream_t st) {
   const long long Lll = (long long)n1 * n2;
-  if (nheads % 4 || Lll > 160 || Lll < 1 || l1 < n1 - 1 || r1 < n1) return LFSR_E_ARG;    // every angular position visible; <= 10 tiles of 16 tokens
+  // every angular position visible; <= 10 tiles of 16 tokens.  A one-token sequence goes to the VALU pair: the softmax over a single key is constant, dQ = dK = 0
+  // and dV = dO exactly, which the pair returns, while dP - D here (two differently ordered sums of the same products) leaves rounding residue in their place
+  if (nheads % 4 || Lll > 160 || Lll < 2 || l1 < n1 - 1 || r1 < n1) return LFSR_E_ARG;
   EpiAttnBwdArgs p{};
   p.QK = qk; p.qk_stride = qk_stride; p.q_choff = q_choff; p.k_choff = k_choff; p.V = v; p.v_stride = v_stride; p.O = o; p.dO = d_o; p.o_stride = o_stride;
   p.dQK = dqk; p.dV = dv; p.nheads = nheads; p.ns1 = ns1; p.ns2 = ns2; p.bs0 = bs0; p.bs1 = bs1; p.bs2 = bs2;

@@ -392,6 +392,59 @@ extern "C" int lfsr_window_attn_bwd(const float* qk, int qk_stride, int q_choff,
                                    n1, n2, st1, st2, l1, r1, l2, r2, clip2, lfsr_stream(stream));
 }
 
+namespace {
+// Y (N columns) = X (M dense rows of cin) . WT, then * (Mk > 0 ? 1 : 0), then + R1: the 1x1 data gradient of the drivers and of lfsr_linear_dgrad
+int dgemm_launch(const float* X, int cin, const float* WT, float* Y, int ys, const float* R1, int r1s, const float* Mk, int mks, int M, int N, int A, int h, int w,
+                 int S, hipStream_t st) {
+  GemmArgs p{};
+  p.X = X; p.x_stride = cin; p.Wp = WT; p.Y = Y; p.y_stride = ys; p.R1 = R1; p.r1_stride = r1s; p.Mk = Mk; p.mk_stride = mks; p.mk_slope = 0.0f;
+  p.M = M; p.N = N; p.Npad = npad32(N); p.A = A; p.H = h; p.W = w; p.ntaps = 1; p.CH = N; p.slope = 1.0f; p.S = S;
+  switch (cin) {
+    case 64: return launch_gemm<IN_SAME, OUT_SAME, 64, 2>(p, st);
+    case 128: return launch_gemm<IN_SAME, OUT_SAME, 128, 2>(p, st);
+    case 256: return launch_gemm<IN_SAME, OUT_SAME, 256, 2>(p, st);
+    case 576: return launch_gemm<IN_SAME, OUT_SAME, 576, 2>(p, st);
+    case 1024: return launch_gemm<IN_SAME, OUT_SAME, 1024, 2>(p, st);
+  }
+  return LFSR_E_ARG;
+}
+}  // namespace
+
+// ---- operator-level entry points over the launchers above (what the drivers call; tests/test_gpu_trans_bwd_ops.py) -------------------------
+extern "C" size_t lfsr_layernorm_bwd_workspace_floats(int C) { return (C == 64 || C == 128) ? (size_t)LFSR_RED_BLOCKS * 2 * C : 0; }
+
+extern "C" int lfsr_layernorm_bwd(const float* x, const float* pe, long long pe_rows, long long pe_div, const float* gamma, const float* dy, const float* r, float* dx,
+                                  float* dgamma, float* dbeta, float* workspace, size_t workspace_floats, long long M, int C, void* stream) {
+  if (!x || !gamma || !dy || !dx || !dgamma || !dbeta || !workspace || M <= 0 || (C != 64 && C != 128)) return LFSR_E_ARG;
+  if (pe && (pe_rows <= 0 || pe_div <= 0)) return LFSR_E_ARG;
+  if (workspace_floats < lfsr_layernorm_bwd_workspace_floats(C)) return LFSR_E_WS;
+  return lfsr_ln_bwd_launch(C, x, pe, pe ? pe_rows : 1, pe ? pe_div : 1, gamma, dy, r, dx, workspace, M, dgamma, dbeta, lfsr_stream(stream));
+}
+
+extern "C" int lfsr_linear_dgrad(const float* dy, int cout, const float* wT_packed, float* dx, int dx_stride, const float* r1, int r1_stride, const float* act,
+                                 int act_stride, long long M, int cin, void* stream) {
+  if (!dy || !wT_packed || !dx || M <= 0 || M > 0x7fffffffLL - BM) return LFSR_E_ARG;      // the gather-GEMM counts rows, padded to its 128-row tile, in an int
+  if (cout != 64 && cout != 128 && cout != 256 && cout != 576 && cout != 1024) return LFSR_E_ARG;
+  if (cin != 64 && cin != 128 && cin != 256) return LFSR_E_ARG;
+  if (dx_stride < cin || (dx_stride & 3) || (r1 && (r1_stride < cin || (r1_stride & 3))) || (act && (act_stride < cin || (act_stride & 3)))) return LFSR_E_ARG;
+  return dgemm_launch(dy, cout, wT_packed, dx, dx_stride, r1, r1 ? r1_stride : 0, act, act ? act_stride : 0, (int)M, cin, 1, 1, 1, 1, lfsr_stream(stream));
+}
+
+extern "C" size_t lfsr_up_tail_bwd_workspace_floats(void) { return (size_t)LFSR_RED_BLOCKS * 9 * 64; }
+
+extern "C" int lfsr_up_tail_bwd(const float* dout, const float* w3, const float* hr, float* du, float* dw3, float* workspace, size_t workspace_floats, int B, int A,
+                                int h, int w, int s, float slope, void* stream) {
+  if (!dout || !w3 || !hr || !du || !dw3 || !workspace || B <= 0 || A <= 0 || h <= 0 || w <= 0 || s < 2 || s > 4) return LFSR_E_ARG;
+  if ((long long)A * h * s > 0x7fffffffLL || (long long)A * w * s > 0x7fffffffLL || (long long)A * A > 0x7fffffffLL) return LFSR_E_ARG;   // k_tail_bwd keeps the mosaic's sides in ints
+  if (workspace_floats < lfsr_up_tail_bwd_workspace_floats()) return LFSR_E_WS;
+  return lfsr_tail_bwd_launch(dout, w3, hr, du, workspace, dw3, B, A, h, w, s, slope, lfsr_stream(stream));
+}
+
+extern "C" int lfsr_pack_up0_weight_tr(const float* w_packed, float* out, int s, void* stream) {
+  if (!w_packed || !out || s < 2 || s > 4) return LFSR_E_ARG;
+  return lfsr_pack_up0_T_launch(w_packed, out, s * s, lfsr_stream(stream));
+}
+
 // ---- the drivers' shared host code ---------------------------------------------------------------------------------------------------
 bool lfsr_trans_train_geometry_ok(int A, int s, int B, int h, int w) {
   if (B <= 0 || h <= 0 || w <= 0 || s < 2 || s > 4) return false;
@@ -410,17 +463,7 @@ size_t lfsr_trans_wgrad_partial_max(int B, int A, int h, int w) {
 float* LfsrTransBwd::G(const std::string& k) const { return gbase + P.grad_off(k); }
 
 int LfsrTransBwd::dgemm(const float* X, int cin, const float* WT, float* Y, int ys, const float* R1, int r1s, const float* Mk, int mks, int N) const {
-  GemmArgs p{};
-  p.X = X; p.x_stride = cin; p.Wp = WT; p.Y = Y; p.y_stride = ys; p.R1 = R1; p.r1_stride = r1s; p.Mk = Mk; p.mk_stride = mks; p.mk_slope = 0.0f;
-  p.M = npix; p.N = N; p.Npad = npad32(N); p.A = A; p.H = h; p.W = w; p.ntaps = 1; p.CH = N; p.slope = 1.0f; p.S = S;
-  switch (cin) {
-    case 64: return launch_gemm<IN_SAME, OUT_SAME, 64, 2>(p, st);
-    case 128: return launch_gemm<IN_SAME, OUT_SAME, 128, 2>(p, st);
-    case 256: return launch_gemm<IN_SAME, OUT_SAME, 256, 2>(p, st);
-    case 576: return launch_gemm<IN_SAME, OUT_SAME, 576, 2>(p, st);
-    case 1024: return launch_gemm<IN_SAME, OUT_SAME, 1024, 2>(p, st);
-  }
-  return LFSR_E_ARG;
+  return dgemm_launch(X, cin, WT, Y, ys, R1, r1s, Mk, mks, npix, N, A, h, w, S, st);
 }
 
 int LfsrTransBwd::wgrad(int xm, const float* Gr, int gs, int go, const float* X, int xs, int M, int N, int K, int ntaps, float* dW, int accumulate,

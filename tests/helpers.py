@@ -948,9 +948,10 @@ def op_output_read(buf, choff, c, holes=()):
     return buf.t[:buf.rows, choff:choff + c].cpu().contiguous()
 
 
-def fwd_op_gate(got, ref, cpu, op, form, row, tol=1e-4, relative=True):
+def op_gate(got, ref, cpu, op, form, row, tol=1e-4, relative=True, tag="FWDOP"):
     """the two gates of an operator output against its fp64 reference: max|err| <= tol * max(1, max|ref|) (relative=False: tol itself), and mean|err| <= YARDSTICK x
-    the mean error of `cpu`, the same operator in fp32 on the CPU with stock torch ops.  Prints the figures first"""
+    the mean error of `cpu`, the same operator in fp32 on the CPU with stock torch ops.  Prints the figures first (`tag`: the first column of that line)
+    -> (max error / gate, yardstick ratio)"""
     import torch
     got, ref, cpu = got.detach().double().cpu(), ref.detach().double().cpu(), cpu.detach().double().cpu()
     assert got.shape == ref.shape == cpu.shape, (op, form, row, got.shape, ref.shape, cpu.shape)
@@ -959,7 +960,138 @@ def fwd_op_gate(got, ref, cpu, op, form, row, tol=1e-4, relative=True):
     e_max, e_mean, e_cpu = float(err.max()), float(err.mean()), float((cpu - ref).abs().mean())
     gate = tol * max(1.0, float(ref.abs().max())) if relative else tol
     ratio = e_mean / e_cpu if e_cpu > 0 else (0.0 if e_mean == 0 else float("inf"))
-    print(f"FWDOP | {op} | {form} | {row} | max {e_max:.3e} | mean {e_mean:.3e} | e_cpu {e_cpu:.3e} | ratio {ratio:.2f} | gate {gate:.3e}")
+    print(f"{tag} | {op} | {form} | {row} | max {e_max:.3e} | mean {e_mean:.3e} | e_cpu {e_cpu:.3e} | ratio {ratio:.2f} | gate {gate:.3e}")
     assert e_max <= gate, (op, form, row, e_max, gate)
     if (op, form, row) not in YARDSTICK_EXEMPT:
         assert e_mean <= YARDSTICK * e_cpu, (op, form, row, e_mean, e_cpu, ratio)
+    return e_max / gate, ratio
+
+
+fwd_op_gate = op_gate        # the name the forward operator tests call it by
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# operator-level tests of lfsr_window_attn_bwd (tests/test_gpu_epit_attn_bwd.py, tests/test_gpu_trans_bwd_ops.py): q | k, v, o / dO in wider rows at
+# non-zero channel offsets, dQ | dK and dV into sentinel-filled buffers with two rows behind the last pixel
+# ---------------------------------------------------------------------------------------------------------------------
+ATTN_SENTINEL = -777.25
+
+
+def rel_l2(a, b):
+    """rel-L2 of a against the fp64 reference b.  A reference that is exactly zero (the softmax over a single key is constant: dQ = dK = 0) asks for exact zeros"""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    num, den = float(np.linalg.norm(a - b)), float(np.linalg.norm(b))
+    return num / den if den > 0 else (0.0 if num == 0 else float("inf"))
+
+
+def attn_bwd_layout(E):
+    """(qk_stride, q_choff, k_choff, v_stride, v_choff, o_stride, o_choff) of these tests for heads that fill E columns"""
+    return (2 * E + 32, 16, E + 20, E + 16, 8, E + 8, 4)
+
+
+def attn_bwd_run(lib, q, k, v, o, d_o, nheads, geometry):
+    """lfsr_window_attn_bwd on (npix, E) numpy operands laid out by attn_bwd_layout; geometry: its arguments from ns0 to clip2 -> (dqk, dv), device buffers"""
+    import torch
+    from lfsr_amd import capi
+    npix, E = q.shape
+    qs, qo, ko, vs, vo, os_, oo = attn_bwd_layout(E)
+
+    def wide(a, stride, off):
+        return torch.from_numpy(np.pad(a, ((0, 0), (off, stride - off - a.shape[1])))).cuda()
+    qk = wide(np.concatenate([q, np.zeros((npix, ko - qo - E), np.float32), k], 1), qs, qo)
+    vd, od, dod = wide(v, vs, vo), wide(o, os_, oo), wide(d_o, os_, oo)
+    dqk = torch.full((npix + 2, qs), ATTN_SENTINEL, device="cuda")
+    dv = torch.full((npix + 2, vs), ATTN_SENTINEL, device="cuda")
+    stats = torch.empty(npix * nheads * 4, device="cuda")
+    capi.check(lib.lfsr_window_attn_bwd(capi.dev_ptr(qk), qs, qo, ko, capi.dev_ptr(vd), vs, vo, capi.dev_ptr(od), capi.dev_ptr(dod), os_, oo, capi.dev_ptr(dqk),
+                                        capi.dev_ptr(dv), capi.dev_ptr(stats), nheads, E // nheads, *geometry, capi.stream_ptr()), "attn_bwd")
+    torch.cuda.synchronize()
+    return dqk, dv
+
+
+def attn_bwd_untouched(dqk, dv, npix, E):
+    """every float outside the dQ | dK and dV column ranges of rows [0, npix) still holds the sentinel"""
+    import torch
+    qs, qo, ko, vs, vo, _, _ = attn_bwd_layout(E)
+    keep = torch.ones(qs, dtype=torch.bool)
+    keep[qo:qo + E] = False
+    keep[ko:ko + E] = False
+    keepv = torch.ones(vs, dtype=torch.bool)
+    keepv[vo:vo + E] = False
+    return (bool((dqk[:, keep.cuda()] == ATTN_SENTINEL).all()) and bool((dqk[npix:] == ATTN_SENTINEL).all()) and bool((dv[npix:] == ATTN_SENTINEL).all())
+            and bool((dv[:, keepv.cuda()] == ATTN_SENTINEL).all()))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# fp64 references of the backward operators the LFT and EPIT training drivers share (tests/test_gpu_trans_bwd_ops.py; checked on their own, without
+# a GPU, by tests/test_trans_bwd_refs_cpu.py)
+# ---------------------------------------------------------------------------------------------------------------------
+LFT_NH = 8
+# (n, h, w) of the spatial attention cases: every query sees at least one key (w <= h + 2), tests/test_trans_bwd_refs_cpu.py asserts it on the mask
+LFT_SPA_GEOMS = ((3, 6, 8), (2, 13, 7), (2, 7, 9), (1, 1, 1), (4, 3, 5))
+
+
+def ln_bwd_ref(x, pe_rows_of_x, gamma, dy, dtype):
+    """autograd of torch.nn.functional.layer_norm(x + pe rows) * gamma (+ beta) in `dtype` -> (dx, dgamma, dbeta); pe_rows_of_x: (M, C) or None"""
+    import torch
+    xt = torch.as_tensor(x).detach().to(dtype).clone().requires_grad_(True)
+    g = torch.as_tensor(gamma).detach().to(dtype).clone().requires_grad_(True)
+    b = torch.zeros_like(g).requires_grad_(True)
+    xin = xt if pe_rows_of_x is None else xt + torch.as_tensor(pe_rows_of_x).to(dtype)
+    torch.nn.functional.layer_norm(xin, xin.shape[-1:], g, b, 1e-5).backward(torch.as_tensor(dy).to(dtype))
+    return xt.grad, g.grad, b.grad
+
+
+def ln_bwd_closed_form(x, gamma, dy, eps=1e-5):
+    """the closed form trans_bwd.hip quotes: dx = rstd (dy g - mean(dy g) - xhat mean(dy g xhat)), dgamma = sum dy xhat, dbeta = sum dy (torch, the dtype of x)"""
+    mu = x.mean(-1, keepdim=True)
+    rstd = 1.0 / ((x - mu).pow(2).mean(-1, keepdim=True) + eps).sqrt()
+    xh = (x - mu) * rstd
+    gy = dy * gamma
+    dx = rstd * (gy - gy.mean(-1, keepdim=True) - xh * (gy * xh).mean(-1, keepdim=True))
+    return dx, (dy * xh).sum(0), dy.sum(0)
+
+
+def tail_du_rows(d_hr, B, A, h, w, s):
+    """dHR (B, 64, A h s, A w s) -> the rows lfsr_up_tail_bwd writes: p = (b, u, v, y, x), column c s^2 + i s + j = dHR[b][c][(u h + y) s + i][(v w + x) s + j]"""
+    return d_hr.reshape(B, 64, A, h, s, A, w, s).permute(0, 2, 5, 3, 6, 1, 4, 7).reshape(B * A * A * h * w, 64 * s * s)
+
+
+def tail_bwd_ref(hr_rows, w3, dout, B, A, h, w, s, slope, dtype):
+    """autograd of conv2d(leaky_relu(HR, slope), w3, padding=1) on the (B, A h s, A w s) mosaic in `dtype`; hr_rows: the channel-last HR map (pixels, 64)
+    -> (du rows, dw3 (576,)).  At HR == 0 (and -0) torch's leaky_relu backward takes the slope (`x > 0 ? g : g * slope`): the project's convention"""
+    import torch
+    Hs, Ws = A * h * s, A * w * s
+    hr = torch.as_tensor(hr_rows).detach().to(dtype).reshape(B, Hs, Ws, 64).permute(0, 3, 1, 2).clone(memory_format=torch.contiguous_format).requires_grad_(True)
+    wt = torch.as_tensor(w3).detach().to(dtype).reshape(1, 64, 3, 3).clone().requires_grad_(True)
+    out = torch.nn.functional.conv2d(torch.nn.functional.leaky_relu(hr, slope), wt, padding=1)
+    out.backward(torch.as_tensor(dout).to(dtype).reshape(B, 1, Hs, Ws))
+    return tail_du_rows(hr.grad, B, A, h, w, s), wt.grad.reshape(-1)
+
+
+def _attn_autograd(q, k, v, d_o, to_heads, mask):
+    """fp64 autograd of softmax(q k^T / sqrt(hd) + mask) v; to_heads: pixel rows (npix, E) -> (..., tokens, hd), a permutation -> (o, dq, dk, dv) in pixel rows"""
+    import torch
+    qt, kt, vt = (torch.tensor(a, dtype=torch.float64, requires_grad=True) for a in (q, k, v))
+    hd = to_heads(qt).shape[-1]
+    S = to_heads(qt) @ to_heads(kt).transpose(-1, -2) / np.sqrt(hd)
+    out = torch.softmax(S if mask is None else S + mask, -1) @ to_heads(vt)
+    dq, dk, dv = torch.autograd.grad((out * to_heads(torch.tensor(d_o, dtype=torch.float64))).sum(), (qt, kt, vt))
+    ot = torch.zeros(q.shape, dtype=torch.float64, requires_grad=True)       # the output back in pixel rows: through the same (linear) rearrangement
+    o_rows, = torch.autograd.grad((to_heads(ot) * out.detach()).sum(), ot)
+    return o_rows.numpy(), dq.numpy(), dk.numpy(), dv.numpy()
+
+
+def lft_ang_attn_ref(q, k, v, d_o, B, A, h, w):
+    """LFT's angular attention (LFT.py:233-246): dense over the A^2 views of each pixel, 8 heads of 8; rows (b, u, v, y, x) x 64"""
+    E = q.shape[1]
+    return _attn_autograd(q, k, v, d_o, lambda t: t.reshape(B, A * A, h * w, LFT_NH, E // LFT_NH).permute(0, 2, 3, 1, 4), None)
+
+
+def lft_spa_attn_ref(q, k, v, d_o, n, h, w):
+    """LFT's spatial attention (LFT.py:161-199) in the reference's own dense form: O.lft_gen_mask(h, w, 5) added to the (h w, h w) scores; 8 heads of 16"""
+    import torch
+    from oracle import lfsr_oracle as O
+    E = q.shape[1]
+    mask = torch.from_numpy(O.lft_gen_mask(h, w, 5, np.float64))
+    return _attn_autograd(q, k, v, d_o, lambda t: t.reshape(n, h * w, LFT_NH, E // LFT_NH).permute(0, 2, 1, 3), mask)

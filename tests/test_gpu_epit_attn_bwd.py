@@ -10,14 +10,13 @@ import torch
 
 from lfsr_amd import capi
 from oracle import lfsr_oracle as O
+from tests.helpers import ATTN_SENTINEL, attn_bwd_layout, attn_bwd_run, rel_l2
 
 pytestmark = pytest.mark.gpu
 E, NH = 128, 8
 # the operands sit inside wider rows at non-zero channel offsets: everything outside them must be left alone
-QK_STRIDE, Q_OFF, K_OFF = 288, 16, 148
-V_STRIDE, V_OFF = 144, 8
-O_STRIDE, O_OFF = 136, 4
-SENTINEL = -777.25
+QK_STRIDE, Q_OFF, K_OFF, V_STRIDE, V_OFF, O_STRIDE, O_OFF = attn_bwd_layout(E)      # 288, 16, 148; 144, 8; 136, 4
+SENTINEL = ATTN_SENTINEL
 
 # (B, A, h, w): the sequence is A x h (horizontal pass) or A x w (vertical pass) tokens
 GEOMS = [(2, 3, 6, 8),       # L = 18 / 24: window wider than the sequence, run-time n1
@@ -67,22 +66,10 @@ def reference(q, k, v, d_o, B, A, h, w, vertical):
 
 def run(lib, q, k, v, o, d_o, geom, vertical):
     B, A, h, w = geom
-    npix = q.shape[0]
-    wide = lambda a, stride, off: torch.from_numpy(np.pad(a, ((0, 0), (off, stride - off - a.shape[1])))).cuda()
-    qk = wide(np.concatenate([q, np.zeros((npix, K_OFF - Q_OFF - E), np.float32), k], 1), QK_STRIDE, Q_OFF)
-    vd, od, dod = wide(v, V_STRIDE, V_OFF), wide(o, O_STRIDE, O_OFF), wide(d_o, O_STRIDE, O_OFF)
-    dqk = torch.full((npix + 2, QK_STRIDE), SENTINEL, device="cuda")      # two rows beyond the last pixel
-    dv = torch.full((npix + 2, V_STRIDE), SENTINEL, device="cuda")
-    stats = torch.empty(npix * NH * 4, device="cuda")
-    capi.check(lib.lfsr_window_attn_bwd(capi.dev_ptr(qk), QK_STRIDE, Q_OFF, K_OFF, capi.dev_ptr(vd), V_STRIDE, V_OFF, capi.dev_ptr(od), capi.dev_ptr(dod),
-                                        O_STRIDE, O_OFF, capi.dev_ptr(dqk), capi.dev_ptr(dv), capi.dev_ptr(stats), NH, E // NH,
-                                        *geometry(B, A, h, w, vertical), A, A, 5, 6, 0, capi.stream_ptr()), "attn_bwd")
-    torch.cuda.synchronize()
-    return dqk, dv
+    return attn_bwd_run(lib, q, k, v, o, d_o, NH, geometry(B, A, h, w, vertical) + (A, A, 5, 6, 0))
 
 
-def rel(a, b):
-    return float(np.linalg.norm(a.astype(np.float64) - b) / np.linalg.norm(b))
+rel = rel_l2
 
 
 @pytest.mark.parametrize("vertical", [0, 1])
