@@ -664,14 +664,16 @@ def epiconv_hv(x, w1p, w2p, B, A, h, w, slope, out, choff_h, choff_v):
     return out
 
 
-def distg_branch_tail(x, spa, w_ang0, w_ang2, w_epi0, w_epi2, w_fuse0, B, A, h, w, slope):
+def distg_branch_tail(x, spa, w_ang0, w_ang2, w_epi0, w_epi2, w_fuse0, B, A, h, w, slope, out=None):
     """DisentgBlock tail (lfsr_distg_branch_tail_fwd): lrelu(fuse.0(spa | ang | epiH | epiV)) of the block input x and the SpaConv.2 output spa, both VCL 64-ch.
-    Weights packed as angconv / epiconv_hv / pointwise take them.  Returns (y (B*A*A*h*w, 64), t_a, t_h, t_v)."""
+    Weights packed as angconv / epiconv_hv / pointwise take them.  Returns (y (B*A*A*h*w, 64), t_a, t_h, t_v); out = those four, preallocated (contiguous)."""
     lib = load()
-    y = torch.empty((x.shape[0], 64), dtype=torch.float32, device=x.device)
-    t_a = torch.empty((B * h * w, 16), dtype=torch.float32, device=x.device)
-    t_h = torch.empty((B * A * h * w, 32), dtype=torch.float32, device=x.device)
-    t_v = torch.empty((B * A * h * w, 32), dtype=torch.float32, device=x.device)
+    shapes = ((x.shape[0], 64), (B * h * w, 16), (B * A * h * w, 32), (B * A * h * w, 32))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.float32, device=x.device) for s in shapes)
+    if len(out) != 4 or any(tuple(o.shape) != s or o.dtype != torch.float32 for o, s in zip(out, shapes)):
+        raise LfsrError("distg_branch_tail: out must be four float32 tensors of shapes %r" % (shapes,))
+    y, t_a, t_h, t_v = out
     check(lib.lfsr_distg_branch_tail_fwd(dev_ptr(x), x.shape[1], 0, dev_ptr(spa), spa.shape[1], 0, dev_ptr(w_ang0), dev_ptr(w_ang2), dev_ptr(w_epi0),
                                          dev_ptr(w_epi2), dev_ptr(w_fuse0), dev_ptr(t_a), dev_ptr(t_h), dev_ptr(t_v), dev_ptr(y), 64, 0, B, A, h, w, slope,
                                          stream_ptr()), "distg_branch_tail_fwd")

@@ -16,6 +16,11 @@
 // the output is bit-identical to the three-launch sequence.  The weights of all three GEMMs stay in LDS for the life of the block: fuse.0 60 KB (split
 // once per block as k_rowgemm_b3 does), EPIConv.2 planes 30 KB (lfsr_pack_epi_b3), AngConv.2 25 KB; plus 8 x 5.25 KB of concat tiles.
 #include "lfsr_internal.h"
+#include <type_traits>
+
+#ifndef DT_ABL
+#define DT_ABL 0   // diagnostic timing build (WRONG results; tools/build_abl.sh, tools/tail_ab.py): 1 = every view's S / t_V / t_H loads go to the tile's view-0 rows (cache hits)
+#endif
 
 namespace {
 
@@ -79,6 +84,61 @@ __global__ __launch_bounds__(512) void k_distg_tail(DistgTailArgs p) {
   const int HW = p.H * p.W, M = p.B * HW;
   const int ntiles = (M + 15) / 16;
 
+  const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.S), 0, p.s_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.TA), 0, p.ta_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.TH), 0, p.te_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.TV), 0, p.te_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(p.Y, 0, p.y_bytes, 0x00020000);
+
+  // A tile's place in the three operands.  lane (l15, g): macro-pixel m = 16 tile + l15 -- the B-operand column of the bf16 MFMAs (and the A row of the fp32
+  // ones).  A tile past the end (a wave without work, the hand-over behind a wave's last tile) has no row in range: every load of it moves no data.
+  struct Tile { bool ok; int ao, tb, pb; };      // t_A byte offset; t_H / t_V row of (b, 0, y, x); VCL pixel of view 0
+  auto place = [&](int tile) {
+    const int m = tile * 16 + l15;
+    Tile c;
+    c.ok = tile < ntiles && m < M;
+    const int mb = c.ok ? m / HW : 0, myx = c.ok ? m - mb * HW : 0;
+    c.ao = c.ok ? (m * 16 + 4 * g) * 4 : EOOB;
+    c.tb = mb * A * HW + myx;
+    c.pb = mb * AA * HW + myx;
+    return c;
+  };
+  auto tro = [&](const Tile& c, int q) {        // t_H / t_V row (b, q, y, x): channels 4 g .. + 3 (+ 64 B: 16 + 4 g)
+    if (DT_ABL & 1) q = 0;
+    return c.ok ? ((c.tb + q * HW) * 32 + 4 * g) * 4 : EOOB;
+  };
+  auto pixo = [&](const Tile& c, int view) { return c.ok ? c.pb + view * HW : -1; };            // VCL pixel of this lane's row in a view
+
+  // raw operands of one view: the SpaConv.2 row (K steps 0, 1: lo / hi four floats) and the t_V row, double-buffered: a body requests the next view's rows
+  // first and waits only for its own (requested one body earlier), so six to eight loads and the previous body's four stores stay outstanding under its
+  // MFMAs.  No load sits behind a run-time branch: a row that is not wanted gets an out-of-range offset (no data moves), so the compiler counts every wait.
+  f32x4t sr0[2][2], sr1[2][2], vr0[2], vr1[2], hr[2], a2n;
+  auto load_view = [&](const Tile& c, int view, f32x4t (&sr)[2][2], f32x4t (&vr)[2]) {
+    const int pix = pixo(c, (DT_ABL & 1) ? 0 : view);
+    const int so = pix >= 0 ? (pix * p.s_stride + p.s_choff + 8 * g) * 4 : EOOB;
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) sr[s][e] = __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(rsS, so == EOOB ? EOOB : so + (32 * s + 4 * e) * 4, 0, 0));
+    const int vo = tro(c, view % A);
+    vr[0] = __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(rsV, vo, 0, 0));
+    vr[1] = __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(rsV, vo == EOOB ? EOOB : vo + 64, 0, 0));
+  };
+  auto load_h = [&](int ho) {
+    hr[0] = __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(rsH, ho, 0, 0));
+    hr[1] = __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(rsH, ho == EOOB ? EOOB : ho + 64, 0, 0));
+  };
+  auto load_first = [&](const Tile& c) {        // what a tile needs before its first view: t_A, view 0, t_H row 0
+    a2n = __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(rsA, c.ao, 0, 0));   // t_A row m, k = 4 g .. + 3
+    load_view(c, 0, sr0, vr0);
+    load_h(tro(c, 0));
+  };
+
+  // the wave's first tile is requested before the weights: the staging and its barrier no longer sit in front of every byte the wave streams
+  int tile = (int)blockIdx.x * DT_WAVES + wave;
+  Tile nx = place(tile);
+  load_first(nx);
+
   // ---- weights, once per block ----
   for (int i = tid; i < 64 * 20; i += 512) {       // fuse.0: split into planes as k_rowgemm_b3 (KV = 144 of K = 160; columns >= 144 zero)
     const int r = i / 20, c = i - r * 20;
@@ -97,56 +157,30 @@ __global__ __launch_bounds__(512) void k_distg_tail(DistgTailArgs p) {
   for (int i = tid; i < DT_AFLOATS / 4; i += 512) reinterpret_cast<float4*>(sA)[i] = reinterpret_cast<const float4*>(p.WA2)[i];
   __syncthreads();
 
-  const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.S), 0, p.s_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.TA), 0, p.ta_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsH = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.TH), 0, p.te_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.TV), 0, p.te_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(p.Y, 0, p.y_bytes, 0x00020000);
   float* const st = sC + wave * 16 * DT_CROW;                          // this wave's concat tile [row][DT_CROW]
   const unsigned char* const wE = sE + (g * 160 + l15) * 16;           // EPIConv.2 A operand: k-group g, row l15 (+ 16 per row tile, + 640 slots per plane)
   const unsigned short* const wF = sF + (g * 64 + l15) * 8;            // fuse.0 A operand: k-group g, row l15 (+ 16 rows per column tile, + 256 slots per K step)
   const float* const bA = sA + l15 * 16 + 4 * g;                       // AngConv.2 B operand (+ 256 per view)
 
-  for (int tile = (int)blockIdx.x * DT_WAVES + wave; tile < ntiles; tile += (int)gridDim.x * DT_WAVES) {
-    // lane (l15, g): macro-pixel m = 16 tile + l15 -- the B-operand column of the bf16 MFMAs (and the A row of the fp32 ones)
-    const int m = tile * 16 + l15;
-    const bool ok = m < M;
-    const int mb = ok ? m / HW : 0, myx = ok ? m - mb * HW : 0;
-    auto tro = [&](int q) { return ok ? (((mb * A + q) * HW + myx) * 32 + 4 * g) * 4 : EOOB; };   // t_H / t_V row (b, q, y, x): channels 4 g .. + 3 (+ 64 B: 16 + 4 g)
-    auto pixo = [&](int view) { return ok ? ((mb * AA + view) * HW + myx) : -1; };              // VCL pixel of this lane's row in a view
-    const f32x4t a2 = __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(rsA, ok ? (m * 16 + 4 * g) * 4 : EOOB, 0, 0));   // t_A row m, k = 4 g .. + 3
-
-    // raw operands of one view: the SpaConv.2 row (K steps 0, 1: lo / hi four floats) and the t_V row; double-buffered so a view's loads fly under the previous view
-    f32x4t sr0[2][2], sr1[2][2], vr0[2], vr1[2], hr[2];
-    auto load_view = [&](int view, f32x4t (&sr)[2][2], f32x4t (&vr)[2]) {
-      const int pix = pixo(view);
-      const int so = pix >= 0 ? (pix * p.s_stride + p.s_choff + 8 * g) * 4 : EOOB;
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int e = 0; e < 2; ++e) sr[s][e] = __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(rsS, so == EOOB ? EOOB : so + (32 * s + 4 * e) * 4, 0, 0));
-      const int vo = tro(view % A);
-      vr[0] = __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(rsV, vo, 0, 0));
-      vr[1] = __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(rsV, vo == EOOB ? EOOB : vo + 64, 0, 0));
-    };
-    auto load_h = [&](int u) {
-      const int ho = tro(u);
-      hr[0] = __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(rsH, ho, 0, 0));
-      hr[1] = __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(rsH, ho == EOOB ? EOOB : ho + 64, 0, 0));
-    };
-    load_h(0);
-    load_view(0, sr0, vr0);
+  for (; tile < ntiles; tile += (int)gridDim.x * DT_WAVES) {
+    const Tile cur = nx;
+    const f32x4t a2 = a2n;
     u32x4t hp[3];                        // planes of t_H (row u of the current view)
 
-    auto body = [&](int view, f32x4t (&sr)[2][2], f32x4t (&vr)[2], f32x4t (&srn)[2][2], f32x4t (&vrn)[2]) {
+    // LAST is a property of the body's copy, not of the view: the two bodies of the loop always have a next view in their own tile, the trailing one requests
+    // the first rows of the wave's next tile (out of range when there is none) once its own are split.
+    auto body = [&](int view, f32x4t (&sr)[2][2], f32x4t (&vr)[2], f32x4t (&srn)[2][2], f32x4t (&vrn)[2], auto last) {
+      constexpr bool LAST = decltype(last)::value;
       const int u = view / A, v = view - A * u;
-      if (view + 1 < AA) load_view(view + 1, srn, vrn);
-      if (v == 0) dt_split8(hr[0], hr[1], hp[0], hp[1], hp[2]);
-      if (v == A - 1 && u + 1 < A) load_h(u + 1);
-
+      // LDS operands are read one MFMA group ahead of their use (an LDS read stays where the source puts it between the asm MFMAs): read in front of its own
+      // group, every one of the 13 groups of a view began with an LDS round trip that nothing covered
+      const float4 b = *reinterpret_cast<const float4*>(bA + view * 256);      // AngConv.2 B operand
+      if constexpr (LAST) a2n = __builtin_bit_cast(f32x4t, __builtin_amdgcn_raw_buffer_load_b128(rsA, nx.ao, 0, 0));
+      else load_view(cur, view + 1, srn, vrn);
+      if (v == 0) dt_split8(hr[0], hr[1], hp[0], hp[1], hp[2]);        // (before the t_H request below: that one lands in hr)
+      load_h(LAST ? tro(nx, 0) : v == A - 1 && u + 1 < A ? tro(cur, u + 1) : EOOB);      // row u + 1 during the last view of row u; nothing otherwise
       // ---- AngConv.2 of this view (k_ang_fused stage 2): D[macro-pixel 4 g + r][channel l15] ----
       {
-        const float4 b = *reinterpret_cast<const float4*>(bA + view * 256);
         f32x4t o = {0.f, 0.f, 0.f, 0.f};
         o = __builtin_amdgcn_mfma_f32_16x16x4f32(a2.x, b.x, o, 0, 0, 0);
         o = __builtin_amdgcn_mfma_f32_16x16x4f32(a2.y, b.y, o, 0, 0, 0);
@@ -162,6 +196,15 @@ __global__ __launch_bounds__(512) void k_distg_tail(DistgTailArgs p) {
 
       // ---- EPIConv.2 of both passes (k_epi_b3 stage 2): horizontal = chunk v of t_H (row u), vertical = chunk u of t_V (column v) ----
       {
+        u32x4t aH[2][3], aV[2][3];
+        auto load_we = [&](int h) {
+#pragma unroll
+          for (int pl = 0; pl < 3; ++pl) {
+            aH[h][pl] = *reinterpret_cast<const u32x4t*>(wE + ((pl * 4) * 160 + 16 * (2 * v + h)) * 16);
+            aV[h][pl] = *reinterpret_cast<const u32x4t*>(wE + ((pl * 4) * 160 + 16 * (2 * u + h)) * 16);
+          }
+        };
+        load_we(0);
         u32x4t vp[3];
         dt_split8(vr[0], vr[1], vp[0], vp[1], vp[2]);
         asm volatile("s_nop 4" : "+v"(hp[0]), "+v"(hp[1]), "+v"(hp[2]), "+v"(vp[0]), "+v"(vp[1]), "+v"(vp[2]));
@@ -169,16 +212,9 @@ __global__ __launch_bounds__(512) void k_distg_tail(DistgTailArgs p) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) { e[i][0] = f32x4t{0.f, 0.f, 0.f, 0.f}; e[i][1] = e[i][0]; }
         asm volatile("s_nop 1" : "+v"(e[0][0]), "+v"(e[0][1]), "+v"(e[1][0]), "+v"(e[1][1]));
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          u32x4t aH[3], aV[3];
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl) {
-            aH[pl] = *reinterpret_cast<const u32x4t*>(wE + ((pl * 4) * 160 + 16 * (2 * v + h)) * 16);
-            aV[pl] = *reinterpret_cast<const u32x4t*>(wE + ((pl * 4) * 160 + 16 * (2 * u + h)) * 16);
-          }
-          dt_six2(e[0][h], aH, hp, e[1][h], aV, vp);
-        }
+        load_we(1);
+        dt_six2(e[0][0], aH[0], hp, e[1][0], aV[0], vp);
+        dt_six2(e[0][1], aH[1], hp, e[1][1], aV[1], vp);
         asm volatile("s_nop 15\n\ts_nop 15" : "+v"(e[0][0]), "+v"(e[0][1]), "+v"(e[1][0]), "+v"(e[1][1]));
 #pragma unroll
         for (int i = 0; i < 2; ++i)
@@ -193,6 +229,16 @@ __global__ __launch_bounds__(512) void k_distg_tail(DistgTailArgs p) {
       __builtin_amdgcn_wave_barrier();
 
       // ---- fuse.0 (k_rowgemm_b3<160, false, 64, 144>): B operand = row l15, channels 32 s + 8 g .. + 7 ----
+      u32x4t wa[2][3], wb[2][3];         // fuse.0 A operands of group gi = 2 s + t / 2 (K step s, column tiles t, t + 1), double-buffered
+      auto load_wf = [&](int gi) {
+        const int s = gi >> 1, t = 2 * (gi & 1);
+#pragma unroll
+        for (int pl = 0; pl < 3; ++pl) {
+          wa[gi & 1][pl] = *reinterpret_cast<const u32x4t*>(wF + pl * DT_FPLANE + (4 * s * 64 + t * 16) * 8);
+          wb[gi & 1][pl] = *reinterpret_cast<const u32x4t*>(wF + pl * DT_FPLANE + (4 * s * 64 + (t + 1) * 16) * 8);
+        }
+      };
+      load_wf(0);
       u32x4t x0[5], x1[5], x2[5];
 #pragma unroll
       for (int s = 0; s < 2; ++s) dt_split8(sr[s][0], sr[s][1], x0[s], x1[s], x2[s]);
@@ -210,22 +256,16 @@ __global__ __launch_bounds__(512) void k_distg_tail(DistgTailArgs p) {
 #pragma unroll
       for (int s = 0; s < 5; ++s) asm volatile("s_nop 4" : "+v"(x0[s]), "+v"(x1[s]), "+v"(x2[s]));
       asm volatile("s_nop 1" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
+      if constexpr (LAST) load_view(nx, 0, sr, vr);      // 25 views: the next tile starts in the set this view has just split, so its rows fly under fuse.0
 #pragma unroll
-      for (int s = 0; s < 5; ++s) {
+      for (int gi = 0; gi < 10; ++gi) {
+        const int s = gi >> 1, t = 2 * (gi & 1);
         const u32x4t xs[3] = {x0[s], x1[s], x2[s]};
-#pragma unroll
-        for (int t = 0; t < 4; t += 2) {
-          u32x4t wa[3], wb[3];
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl) {
-            wa[pl] = *reinterpret_cast<const u32x4t*>(wF + pl * DT_FPLANE + (4 * s * 64 + t * 16) * 8);
-            wb[pl] = *reinterpret_cast<const u32x4t*>(wF + pl * DT_FPLANE + (4 * s * 64 + (t + 1) * 16) * 8);
-          }
-          dt_six2(acc[t], wa, xs, acc[t + 1], wb, xs);
-        }
+        if (gi + 1 < 10) load_wf(gi + 1);
+        dt_six2(acc[t], wa[gi & 1], xs, acc[t + 1], wb[gi & 1], xs);
       }
       asm volatile("s_nop 15\n\ts_nop 15" : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
-      const int pix = pixo(view);
+      const int pix = pixo(cur, view);
       const int yo = pix >= 0 ? (pix * p.y_stride + p.y_choff + 4 * g) * 4 : EOOB;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -238,10 +278,11 @@ __global__ __launch_bounds__(512) void k_distg_tail(DistgTailArgs p) {
     };
 #pragma unroll 1
     for (int view = 0; view < AA - 1; view += 2) {
-      body(view, sr0, vr0, sr1, vr1);
-      body(view + 1, sr1, vr1, sr0, vr0);
+      body(view, sr0, vr0, sr1, vr1, std::false_type{});
+      body(view + 1, sr1, vr1, sr0, vr0, std::false_type{});
     }
-    body(AA - 1, sr0, vr0, sr1, vr1);
+    nx = place(tile + (int)gridDim.x * DT_WAVES);
+    body(AA - 1, sr0, vr0, sr1, vr1, std::true_type{});
   }
 }
 

@@ -181,7 +181,8 @@ __global__ __launch_bounds__(512) void k_epi_b3(EpiB3Args p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int idx = tid + 512 * i;
-      wr[i] = idx < EB_STAGE_SLOTS ? src[idx] : make_uint4(0u, 0u, 0u, 0u);
+      const uint4 q = src[idx < EB_STAGE_SLOTS ? idx : EB_STAGE_SLOTS - 1];      // (no branch around the load: store_w drops the slots past the end)
+      wr[i] = make_uint4(q.x, q.y, q.z, q.w);                                    // (member by member: assigned whole from global memory, wr went to scratch)
     }
   };
   auto store_w = [&](int buf, int ks) {
@@ -231,11 +232,14 @@ __global__ __launch_bounds__(512) void k_epi_b3(EpiB3Args p) {
     auto step = [&](int j, u32x4e (&u0)[2], u32x4e (&u1)[2], u32x4e (&u2)[2], f32x4e (&rs)[2][2], u32x4e (&d0)[2], u32x4e (&d1)[2], u32x4e (&d2)[2],
                     f32x4e (&rd)[2][2]) {
       const int vv = j >> 1, ks = j & 1;
-      if (!(EB_ABL & 8)) {
-        if (j + 2 < 10) load_x(L, j + 2, rd);
-        else load_x(Ln, j + 2 - 10, rd);
-      }
+      // the weights first: the memory counter retires in order, so the wait in front of store_w at the end of the step leaves the four X loads behind it in flight
       if (!(EB_ABL & 4)) load_w(2 * (vv + 1 < A ? vv + 1 : 0) + ks);
+      if (!(EB_ABL & 8)) {              // (the line picked by selects: a branch here would put the loads behind it and cost the counted waits below)
+        const bool nl = j + 2 >= 10;
+        Line Lx;      // (only the four fields load_x reads)
+        Lx.base = nl ? Ln.base : L.base; Lx.len = nl ? Ln.len : L.len; Lx.vstride = nl ? Ln.vstride : L.vstride; Lx.pstride = nl ? Ln.pstride : L.pstride;
+        load_x(Lx, nl ? j + 2 - 10 : j + 2, rd);
+      }
       asm volatile("s_nop 4" : "+v"(u0[0]), "+v"(u1[0]), "+v"(u2[0]), "+v"(u0[1]), "+v"(u1[1]), "+v"(u2[1]));
       const unsigned char* wb = sW + (cur * 2 + ks) * EB_STAGE_BYTES + aoff;
       // A operands (the weights' planes of tap dx, row tile mt) one group ahead of their MFMAs
