@@ -520,7 +520,7 @@ int lfsr_get_grad_arithmetic(void);
  *  - the feed-forward block, lfsr_ffn_fwd / lfsr_ffn_ln_fwd, at (K1, H, N2) = (128, 256, 128) and (64, 128, 64).
  * Every other shape, unaligned operands and spans of 2 GiB or more run exactly as under the default.  LFSR_ARITH_F32 wins over this mode.  What follows: the forward
  * and forward_train of lfsr_epit_* and lfsr_lft_*, LF_InterNet's 128 -> 64 angular squeeze, and the training backward's recomputation of the feed-forward hidden
- * rows (so that it equals what the forward computed).  What does not: K = 144 (DistgSSR's fuse.0, hence all of DistgSSR), linears below 2048 rows, biased linears,
+ * rows (so that it equals what the forward computed).  What does not: K = 144 (DistgSSR's fuse.0, hence all of DistgSSR, which has its own switch: lfsr_set_branch_arithmetic below), linears below 2048 rows, biased linears,
  * the attention kernels, the up-sampling tail, the 3x3 convs and every gradient kernel.  No atomics: two runs give the same bits and a row's result does not depend
  * on the number of rows.  Parity with the reference's fp32 results is claimed only in the default mode (error against fp64 under the mode: below
  * torch.autocast(bfloat16)'s, tests/test_gpu_gemm_bf16.py). */
@@ -528,6 +528,26 @@ int lfsr_get_grad_arithmetic(void);
 #define LFSR_GEMM_ARITH_BF16 1
 int lfsr_set_gemm_arithmetic(int mode);   /* LFSR_E_ARG for any other value, nothing changed */
 int lfsr_get_gemm_arithmetic(void);
+
+/* ---- arithmetic of DistgSSR's EPI branch and block tail: a fourth process-wide selection, independent of the three above, read at every launch ----
+ * LFSR_BRANCH_ARITH_DEFAULT: every kernel as it is, bit for bit.
+ * LFSR_BRANCH_ARITH_BF16: opt-in.  Where the DistgSSR forward at angRes 5 runs its fused block tail (stage 1 of the branches, then AngConv.2, EPIConv.2 of both
+ * passes, the concat and fuse.0 in one launch), three GEMMs round their operands to bf16 (nearest even) once instead of carrying them as three bf16 terms:
+ *  - EPIConv.0 of both passes: x and the weight;
+ *  - EPIConv.2 of both passes: the fp32 post-LeakyReLU stage-1 results as they lie in memory, and the weight;
+ *  - fuse.0: all 144 concat channels (the SpaConv.2 rows, the post-LeakyReLU AngConv.2 and EPIConv.2 results) and the weight.
+ * The products are exact; accumulation, LeakyReLU and stores are fp32; every intermediate stays fp32 in memory; the weights are rounded from their fp32 packs
+ * while a block stages them, so the packs, lfsr_distgssr_packed_bytes and the workspace do not change.  AngConv.0 and AngConv.2 keep their fp32-MFMA
+ * arithmetic.  What follows: lfsr_distgssr_forward (and _taps) and the operator lfsr_distg_branch_tail_fwd.  What does not, with its bits unchanged:
+ * LFSR_ARITH_F32 (which wins), angRes other than 5, inputs of fewer than 2048 pixels, block (0,0) when the concat tap is requested, the LFSR_LAB selectors,
+ * lfsr_distgssr_forward_train and every backward kernel (the training forward keeps the three-kernel sequence whose intermediates the backward reads: training
+ * under the mode is not its aim), and EPIT, LFT and LF_InterNet.  No atomics: two runs give the same bits, and a macro-pixel's result depends neither on B nor on
+ * the grid.  Parity with the reference's fp32 results is claimed only in the default mode (error against fp64 under the mode: below
+ * torch.autocast(bfloat16)'s, tests/test_gpu_branch_bf16.py). */
+#define LFSR_BRANCH_ARITH_DEFAULT 0
+#define LFSR_BRANCH_ARITH_BF16 1
+int lfsr_set_branch_arithmetic(int mode);   /* LFSR_E_ARG for any other value, nothing changed */
+int lfsr_get_branch_arithmetic(void);
 
 /* ---- operator-level timing hooks (measurement aid; the reference times whole forwards only: check_efficiency_official.py:306-330) ----
  * lfsr_op_profile(1): from now on every instrumented operator entry point brackets its launches with a hipEvent pair on its launch stream (and any

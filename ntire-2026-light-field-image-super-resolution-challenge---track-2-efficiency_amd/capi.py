@@ -92,6 +92,8 @@ SIGNATURES = {
     "lfsr_get_grad_arithmetic": (c_i, []),
     "lfsr_set_gemm_arithmetic": (c_i, [c_i]),
     "lfsr_get_gemm_arithmetic": (c_i, []),
+    "lfsr_set_branch_arithmetic": (c_i, [c_i]),
+    "lfsr_get_branch_arithmetic": (c_i, []),
     "lfsr_op_profile": (c_i, [c_i]),
     "lfsr_op_profile_read": (C.c_longlong, [C.c_char_p, c_sz]),
     "lfsr_distgssr_profile": (c_i, [c_p, c_i]),
@@ -220,6 +222,20 @@ def set_gemm_arithmetic(mode):
 def get_gemm_arithmetic():
     """lfsr_get_gemm_arithmetic: the mode the next linear / feed-forward launch runs in"""
     return int(load().lfsr_get_gemm_arithmetic())
+
+
+BRANCH_ARITH_DEFAULT, BRANCH_ARITH_BF16 = 0, 1
+
+
+def set_branch_arithmetic(mode):
+    """lfsr_set_branch_arithmetic: BRANCH_ARITH_DEFAULT (DistgSSR's branches and block tail as they are) or BRANCH_ARITH_BF16 (EPIConv.0, EPIConv.2 and fuse.0 of the
+    fused block tail at angRes 5 round their operands to bf16, fp32 accumulation); process-wide, independent of the other three switches"""
+    check(load().lfsr_set_branch_arithmetic(int(mode)), "set_branch_arithmetic")
+
+
+def get_branch_arithmetic():
+    """lfsr_get_branch_arithmetic: the mode the next DistgSSR branch / block-tail launch runs in"""
+    return int(load().lfsr_get_branch_arithmetic())
 
 
 def op_profile(enable):
@@ -407,7 +423,7 @@ class GraphedForward:
         self.graphs = {}
 
     def __call__(self, x):
-        key = (tuple(x.shape), x.device, x.dtype, get_arithmetic(), get_gemm_arithmetic())      # both are read at launch: a graph holds the kernels of the modes it was captured in
+        key = (tuple(x.shape), x.device, x.dtype, get_arithmetic(), get_gemm_arithmetic(), get_branch_arithmetic())      # all are read at launch: a graph holds the kernels of the modes it was captured in
         g = self.graphs.get(key)
         if g is None:
             static_x = x.clone()

@@ -350,7 +350,7 @@ extern "C" int lfsr_distg_branch_tail_fwd(const float* x, int x_stride, int x_ch
   if (npix * x_stride * 4 >= (1LL << 31) || npix * spa_stride * 4 >= (1LL << 31) || npix * y_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
   hipStream_t st = lfsr_stream(stream);
   int rc = lfsr_ang_fused_launch(x, x_stride, x_choff, w_ang0, nullptr, t_a, nullptr, 0, 0, B, A, h, w, slope, st);
-  if (!rc) rc = lfsr_epi_b3_launch(x, x_stride, x_choff, w_epi0 + 25 * 32 * 64 + LFSR_EPI_WINO_FLOATS, nullptr, nullptr, 0, 0, 0, t_h, t_v, B, A, h, w, 3, slope, st);
-  if (!rc) rc = lfsr_distg_tail_launch(spa, spa_stride, spa_choff, t_a, t_h, t_v, w_ang2, w_epi2 + 160 * 32, w_fuse0, y, y_stride, y_choff, B, A, h, w, slope, st);
+  if (!rc) rc = lfsr_distg_epi1_launch(x, x_stride, x_choff, w_epi0, t_h, t_v, B, A, h, w, slope, st);      // (both follow lfsr_set_branch_arithmetic)
+  if (!rc) rc = lfsr_distg_tail2_launch(spa, spa_stride, spa_choff, t_a, t_h, t_v, w_ang2, w_epi2, w_fuse0, y, y_stride, y_choff, B, A, h, w, slope, st);
   return rc;
 }

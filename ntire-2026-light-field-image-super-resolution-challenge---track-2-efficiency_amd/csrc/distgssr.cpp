@@ -291,10 +291,10 @@ int lfsr_distgssr_forward_taps(lfsr_distgssr* c, const float* x, float* out, int
         PROF(0, conv(T, p + "SpaConv.2.weight", o, 64, 0, nullptr, L));
         hipStream_t st = lfsr_stream(stream);
         PROF(1, lfsr_ang_fused_launch(cur, 64, 0, c->w(p + "AngConv.0.weight"), nullptr, A16, nullptr, 0, 0, B, A, h, w, L, st));
-        PROF(2, lfsr_epi_b3_launch(cur, 64, 0, c->w(p + "EPIConv.0.weight") + 25 * 32 * 64 + LFSR_EPI_WINO_FLOATS, nullptr, nullptr, 0, 0, 0, E32, EV32,
-                                   B, A, h, w, 3, L, st));
-        PROF(3, lfsr_distg_tail_launch(o, 64, 0, A16, E32, EV32, c->w(p + "AngConv.2.weight"), c->w(p + "EPIConv.2.weight") + 160 * 32,
-                                       c->w(p + "fuse.0.weight"), T, 64, 0, B, A, h, w, L, st));
+        // (both follow lfsr_set_branch_arithmetic: distg_bf16.hip)
+        PROF(2, lfsr_distg_epi1_launch(cur, 64, 0, c->w(p + "EPIConv.0.weight"), E32, EV32, B, A, h, w, L, st));
+        PROF(3, lfsr_distg_tail2_launch(o, 64, 0, A16, E32, EV32, c->w(p + "AngConv.2.weight"), c->w(p + "EPIConv.2.weight"), c->w(p + "fuse.0.weight"), T, 64, 0,
+                                        B, A, h, w, L, st));
         PROF(0, conv(T, p + "fuse.2.weight", o, 64, 0, cur, 1.0f));
         cur = o;
         if (g == 0 && b == 0) LFSR_RC(tap(1, cur, 64, 64));

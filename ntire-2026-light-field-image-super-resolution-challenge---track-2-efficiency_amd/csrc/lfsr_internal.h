@@ -137,6 +137,20 @@ bool lfsr_distg_tail_ok(int A, int h, int w, const float* x, int x_stride, int x
 int lfsr_distg_tail_launch(const float* spa, int spa_stride, int spa_choff, const float* t_a, const float* t_h, const float* t_v, const float* wa2_packed,
                            const float* we2_planes, const float* wf_packed, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope,
                            hipStream_t st);
+// distg_bf16.hip: the EPI stage 1 and the block tail on bf16 operands (lfsr_set_branch_arithmetic(LFSR_BRANCH_ARITH_BF16)); w1_direct / we2_direct: the fp32 direct
+// packs of EPIConv.0 / EPIConv.2 (rounded while a block stages them).  LFSR_E_ARG = not covered, nothing launched
+int lfsr_epi_bf16_launch(const float* x, int x_stride, int x_choff, const float* w1_direct, float* t_h, float* t_v, int B, int A, int h, int w, float slope,
+                         hipStream_t st);
+int lfsr_distg_tail_bf16_launch(const float* spa, int spa_stride, int spa_choff, const float* t_a, const float* t_h, const float* t_v, const float* wa2_packed,
+                                const float* we2_direct, const float* wf_packed, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope,
+                                hipStream_t st);
+// the two launches of a fused block tail as the branch arithmetic selects them (w_epi0 / w_epi2: the whole packs): the bf16 form under the mode unless
+// LFSR_ARITH_F32 is set, falling back to the default launcher where it does not cover the call
+int lfsr_distg_epi1_launch(const float* x, int x_stride, int x_choff, const float* w_epi0, float* t_h, float* t_v, int B, int A, int h, int w, float slope,
+                           hipStream_t st);
+int lfsr_distg_tail2_launch(const float* spa, int spa_stride, int spa_choff, const float* t_a, const float* t_h, const float* t_v, const float* wa2_packed,
+                            const float* w_epi2, const float* wf_packed, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope,
+                            hipStream_t st);
 // epi_fused.hip  (t_h / t_v: optional (B*A*h*w, 32) buffers receiving the post-LeakyReLU stage-1 activations for backward)
 bool lfsr_epi_fused_ok(int A, int h, int w);
 int lfsr_epi_fused_launch(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed, float* y, int y_stride,
