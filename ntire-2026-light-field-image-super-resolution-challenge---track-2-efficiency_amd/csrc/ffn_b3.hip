@@ -545,27 +545,24 @@ int launch_ffn_b3_res(const FfnB3Args& p, hipStream_t st) {
 
 }  // namespace
 
-// LFSR_E_ARG = shape not covered (the caller runs the fp32-MFMA kernel)
-int lfsr_ffn_b3_launch(const float* x, int x_stride, int x_choff, const float* ln_g, const float* ln_b, float ln_eps, const float* w1_packed, const float* w2_packed,
-                       const float* res, int res_stride, int res_choff, float* y, int y_stride, int y_choff,
-                       long long M, int K1, int H, int N2, float slope, hipStream_t st, const void* wsplit) {
-  if (!x || !w1_packed || !w2_packed || !y || M <= 0 || H <= 0 || H % 32 || ((uintptr_t)wsplit & 15)) return LFSR_E_ARG;
-  if ((x_stride | x_choff | y_stride | y_choff) & 3 || (res && ((res_stride | res_choff) & 3))) return LFSR_E_ARG;
-  if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res | (uintptr_t)w1_packed | (uintptr_t)w2_packed | (uintptr_t)ln_g | (uintptr_t)ln_b) & 15) return LFSR_E_ARG;
-  if (x_stride < x_choff + K1 || y_stride < y_choff + N2 || (res && res_stride < res_choff + N2)) return LFSR_E_ARG;
-  const long long span = (long long)(x_stride > y_stride ? (x_stride > res_stride ? x_stride : res_stride) : (y_stride > res_stride ? y_stride : res_stride));
-  if ((M + 64) * span * 4 >= (1LL << 31)) return LFSR_E_ARG;      // (32-bit byte offsets, a last partial group of rows included)
+// LFSR_E_ARG = shape not covered
+int lfsr_ffn_b3_launch(const LfsrFfn& f, hipStream_t st) {
+  if (!f.x || !f.w1_packed || !f.w2_packed || !f.y || f.M <= 0 || f.H <= 0 || f.H % 32 || ((uintptr_t)f.wsplit & 15)) return LFSR_E_ARG;
+  if ((f.x_stride | f.x_choff | f.y_stride | f.y_choff) & 3 || (f.res && ((f.res_stride | f.res_choff) & 3))) return LFSR_E_ARG;
+  if (((uintptr_t)f.x | (uintptr_t)f.y | (uintptr_t)f.res | (uintptr_t)f.w1_packed | (uintptr_t)f.w2_packed | (uintptr_t)f.ln_g | (uintptr_t)f.ln_b) & 15) return LFSR_E_ARG;
+  if (f.x_stride < f.x_choff + f.K1 || f.y_stride < f.y_choff + f.N2 || (f.res && f.res_stride < f.res_choff + f.N2)) return LFSR_E_ARG;
+  const long long span = (long long)(f.x_stride > f.y_stride ? (f.x_stride > f.res_stride ? f.x_stride : f.res_stride) : (f.y_stride > f.res_stride ? f.y_stride : f.res_stride));
+  if ((f.M + 64) * span * 4 >= (1LL << 31)) return LFSR_E_ARG;      // (32-bit byte offsets, a last partial group of rows included)
   FfnB3Args p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.W1 = w1_packed; p.W2 = w2_packed;
-  p.R = res; p.r_stride = res_stride; p.r_choff = res_choff; p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff;
-  p.M = M; p.H = H; p.slope = slope; p.ln_g = ln_g; p.ln_b = ln_b; p.ln_eps = ln_eps; p.Wsplit = (const unsigned short*)wsplit;
-  p.x_bytes = (int)(M * x_stride * 4); p.y_bytes = (int)(M * y_stride * 4); p.r_bytes = res ? (int)(M * res_stride * 4) : 0;
-  if (K1 == 128 && N2 == 128) return wsplit ? launch_ffn_b3<128, 128, true>(p, st) : launch_ffn_b3<128, 128, false>(p, st);
-  if (K1 == 64 && N2 == 64) {
+  p.X = f.x; p.x_stride = f.x_stride; p.x_choff = f.x_choff; p.W1 = f.w1_packed; p.W2 = f.w2_packed;
+  p.R = f.res; p.r_stride = f.res_stride; p.r_choff = f.res_choff; p.Y = f.y; p.y_stride = f.y_stride; p.y_choff = f.y_choff;
+  p.M = f.M; p.H = f.H; p.slope = f.slope; p.ln_g = f.ln_g; p.ln_b = f.ln_b; p.ln_eps = f.ln_eps; p.Wsplit = (const unsigned short*)f.wsplit;
+  p.x_bytes = (int)(f.M * f.x_stride * 4); p.y_bytes = (int)(f.M * f.y_stride * 4); p.r_bytes = f.res ? (int)(f.M * f.res_stride * 4) : 0;
+  if (f.K1 == 128 && f.N2 == 128) return f.wsplit ? launch_ffn_b3<128, 128, true>(p, st) : launch_ffn_b3<128, 128, false>(p, st);
+  if (f.K1 == 64 && f.N2 == 64) {
     // H = 128 with the pre-split image: all four chunks resident in LDS, no barrier in the loop (LFSR_FFN=chunks: the chunk-staging form)
-    const char* fsel = lfsr_sel("LFSR_FFN");
-    if (wsplit && H == 128 && !(fsel && fsel[0] == 'c')) return launch_ffn_b3_res<64, 64, 4>(p, st);
-    return wsplit ? launch_ffn_b3<64, 64, true>(p, st) : launch_ffn_b3<64, 64, false>(p, st);
+    if (f.wsplit && f.H == 128 && !lfsr_gemm_sel().ffn_chunks) return launch_ffn_b3_res<64, 64, 4>(p, st);
+    return f.wsplit ? launch_ffn_b3<64, 64, true>(p, st) : launch_ffn_b3<64, 64, false>(p, st);
   }
   return LFSR_E_ARG;
 }

@@ -234,47 +234,17 @@ int launch_ffn(const FfnArgs& p, hipStream_t st) {
 }  // namespace
 
 // y = res + W2 . act(W1 . LayerNorm(x)) when ln_g / ln_b are given (x the raw tokens), else the plain form
-int lfsr_ffn_ln_launch(const float* x, int x_stride, int x_choff, const float* ln_g, const float* ln_b, float ln_eps, const float* w1_packed, const float* w2_packed,
-                       const float* res, int res_stride, int res_choff, float* y, int y_stride, int y_choff,
-                       long long M, int K1, int H, int N2, float slope, hipStream_t st, const void* wsplit) {
-  LfsrOpTimer op_t("ffn", K1, H, st);
-  if (!x || !w1_packed || !w2_packed || !y || M <= 0 || H <= 0 || H % 32 || (x_stride | x_choff) & 3) return LFSR_E_ARG;
-  if ((ln_g != nullptr) != (ln_b != nullptr)) return LFSR_E_ARG;
-  {   // default: the three-term bf16 form (ffn_b3.hip); LFSR_FFN=f32 keeps this file's fp32-MFMA kernel (A/B runs)
-    const char* fsel = lfsr_sel("LFSR_FFN");
-    if (!(fsel && fsel[0] == 'f') && !lfsr_arith_f32()) {
-      if (lfsr_gemm_arith_bf16()) {   // lfsr_set_gemm_arithmetic(bf16): bf16 operands (gemm_bf16.hip) where the shape is covered
-        const int rq = lfsr_ffn_bf16_launch(x, x_stride, x_choff, ln_g, ln_b, ln_eps, w1_packed, w2_packed, res, res_stride, res_choff, y, y_stride, y_choff, M, K1, H, N2, slope, st);
-        if (rq != LFSR_E_ARG) return rq;
-      }
-      const int rc = lfsr_ffn_b3_launch(x, x_stride, x_choff, ln_g, ln_b, ln_eps, w1_packed, w2_packed, res, res_stride, res_choff, y, y_stride, y_choff, M, K1, H, N2, slope, st, wsplit);
-      if (rc != LFSR_E_ARG) return rc;
-    }
-  }
-  if (x_stride < x_choff + K1 || y_stride < y_choff + N2 || (res && res_stride < res_choff + N2)) return LFSR_E_ARG;
-  if (M * (long long)(y_stride > res_stride ? y_stride : res_stride) * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets in the epilogue
+int lfsr_ffn_launch(const LfsrFfn& f, hipStream_t st) {
+  if (!f.x || !f.w1_packed || !f.w2_packed || !f.y || f.M <= 0 || f.H <= 0 || f.H % 32 || (f.x_stride | f.x_choff) & 3) return LFSR_E_ARG;
+  if ((f.ln_g != nullptr) != (f.ln_b != nullptr) || (((uintptr_t)f.ln_g | (uintptr_t)f.ln_b) & 15)) return LFSR_E_ARG;
+  if (f.x_stride < f.x_choff + f.K1 || f.y_stride < f.y_choff + f.N2 || (f.res && f.res_stride < f.res_choff + f.N2)) return LFSR_E_ARG;
+  if (f.M * (long long)(f.y_stride > f.res_stride ? f.y_stride : f.res_stride) * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets in the epilogue
   FfnArgs p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.W1 = w1_packed; p.W2 = w2_packed;
-  p.R = res; p.r_stride = res_stride; p.r_choff = res_choff; p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff;
-  p.M = M; p.H = H; p.slope = slope; p.ln_g = ln_g; p.ln_b = ln_b; p.ln_eps = ln_eps;
-  p.y_bytes = (int)(M * y_stride * 4); p.r_bytes = res ? (int)(M * res_stride * 4) : 0;
-  if ((ln_g != nullptr) != (ln_b != nullptr) || (((uintptr_t)ln_g | (uintptr_t)ln_b) & 15)) return LFSR_E_ARG;
-  if (K1 == 128 && N2 == 128) return launch_ffn<128, 128>(p, st);
-  if (K1 == 64 && N2 == 64) return launch_ffn<64, 64>(p, st);
+  p.X = f.x; p.x_stride = f.x_stride; p.x_choff = f.x_choff; p.W1 = f.w1_packed; p.W2 = f.w2_packed;
+  p.R = f.res; p.r_stride = f.res_stride; p.r_choff = f.res_choff; p.Y = f.y; p.y_stride = f.y_stride; p.y_choff = f.y_choff;
+  p.M = f.M; p.H = f.H; p.slope = f.slope; p.ln_g = f.ln_g; p.ln_b = f.ln_b; p.ln_eps = f.ln_eps;
+  p.y_bytes = (int)(f.M * f.y_stride * 4); p.r_bytes = f.res ? (int)(f.M * f.res_stride * 4) : 0;
+  if (f.K1 == 128 && f.N2 == 128) return launch_ffn<128, 128>(p, st);
+  if (f.K1 == 64 && f.N2 == 64) return launch_ffn<64, 64>(p, st);
   return LFSR_E_ARG;
-}
-
-extern "C" int lfsr_ffn_fwd(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed,
-                            const float* res, int res_stride, int res_choff, float* y, int y_stride, int y_choff,
-                            long long M, int K1, int H, int N2, float slope, void* stream) {
-  return lfsr_ffn_ln_launch(x, x_stride, x_choff, nullptr, nullptr, 0.f, w1_packed, w2_packed, res, res_stride, res_choff, y, y_stride, y_choff, M, K1, H, N2, slope,
-                            lfsr_stream(stream));
-}
-
-extern "C" int lfsr_ffn_ln_fwd(const float* x, int x_stride, int x_choff, const float* gamma, const float* beta, float eps,
-                               const float* w1_packed, const float* w2_packed, const float* res, int res_stride, int res_choff,
-                               float* y, int y_stride, int y_choff, long long M, int K1, int H, int N2, float slope, void* stream) {
-  if (!gamma || !beta) return LFSR_E_ARG;
-  return lfsr_ffn_ln_launch(x, x_stride, x_choff, gamma, beta, eps, w1_packed, w2_packed, res, res_stride, res_choff, y, y_stride, y_choff, M, K1, H, N2, slope,
-                            lfsr_stream(stream));
 }

@@ -409,18 +409,17 @@ bool q_span_ok(long long M, int stride) { return (M + 256) * (long long)stride *
 
 }  // namespace
 
-// LFSR_E_ARG = shape or operands not covered (the caller goes on with its three-term chain); nothing is written then
-int lfsr_gemm_bf16_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* res, int res_stride, int res_choff,
-                          float* y, int y_stride, int y_choff, long long M, int N, float slope, hipStream_t st) {
-  if (!x || !w_packed || !y || M <= 0 || (K != 64 && K != 128) || (N != 64 && N != 128 && N != 256)) return LFSR_E_ARG;
-  if ((x_stride | x_choff | y_stride | y_choff) & 3 || (res && ((res_stride | res_choff) & 3))) return LFSR_E_ARG;
-  if (x_choff < 0 || y_choff < 0 || (res && res_choff < 0) || x_stride < x_choff + K || y_stride < y_choff + N || (res && res_stride < res_choff + N)) return LFSR_E_ARG;
-  if (((uintptr_t)y | (uintptr_t)x | (uintptr_t)res | (uintptr_t)w_packed) & 15) return LFSR_E_ARG;
-  if (!q_span_ok(M, x_stride) || !q_span_ok(M, y_stride) || (res && !q_span_ok(M, res_stride))) return LFSR_E_ARG;
+// LFSR_E_ARG = shape or operands not covered; nothing is written then
+int lfsr_gemm_bf16_launch(const LfsrLin& c, hipStream_t st) {
+  if (!c.x || !c.w_packed || !c.y || c.M <= 0 || (c.K != 64 && c.K != 128) || (c.N != 64 && c.N != 128 && c.N != 256)) return LFSR_E_ARG;
+  if ((c.x_stride | c.x_choff | c.y_stride | c.y_choff) & 3 || (c.res && ((c.res_stride | c.res_choff) & 3))) return LFSR_E_ARG;
+  if (c.x_choff < 0 || c.y_choff < 0 || (c.res && c.res_choff < 0) || c.x_stride < c.x_choff + c.K || c.y_stride < c.y_choff + c.N || (c.res && c.res_stride < c.res_choff + c.N)) return LFSR_E_ARG;
+  if (((uintptr_t)c.y | (uintptr_t)c.x | (uintptr_t)c.res | (uintptr_t)c.w_packed) & 15) return LFSR_E_ARG;
+  if (!q_span_ok(c.M, c.x_stride) || !q_span_ok(c.M, c.y_stride) || (c.res && !q_span_ok(c.M, c.res_stride))) return LFSR_E_ARG;
   GemmB16Args p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wp = w_packed; p.R1 = res; p.r1_stride = res_stride; p.r1_choff = res_choff;
-  p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff; p.M = M; p.slope = slope;
-  switch (K * 1000 + N) {
+  p.X = c.x; p.x_stride = c.x_stride; p.x_choff = c.x_choff; p.Wp = c.w_packed; p.R1 = c.res; p.r1_stride = c.res_stride; p.r1_choff = c.res_choff;
+  p.Y = c.y; p.y_stride = c.y_stride; p.y_choff = c.y_choff; p.M = c.M; p.slope = c.slope;
+  switch (c.K * 1000 + c.N) {
     case 64064: return launch_gemm_bf16<64, 64, false, 256>(p, st);
     case 64128: return launch_gemm_bf16<64, 128, false, 256>(p, st);
     case 64256: return launch_gemm_bf16<64, 256, false, 256>(p, st);
@@ -431,37 +430,33 @@ int lfsr_gemm_bf16_launch(const float* x, int x_stride, int x_choff, int K, cons
   }
 }
 
-// LayerNorm + q | k | v projection (argument meaning as lfsr_rowgemm_ln_launch in rowgemm.hip); (K, N) = (128, 384) or (64, 192)
-int lfsr_gemm_bf16_ln_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* ln_g, const float* ln_b, float ln_eps, int ln_cols,
-                             const float* pe, int pe_stride, int pe_rows, int pe_div, float* y, int y_stride, int y_choff,
-                             float* y2, int y2_stride, int y2_choff, int split_n, long long M, int N, hipStream_t st) {
-  if (!((K == 128 && N == 384) || (K == 64 && N == 192)) || !x || !w_packed || !ln_g || !ln_b || !y || M <= 0 || ln_cols < 0 || ln_cols > N || ln_cols % 64) return LFSR_E_ARG;
-  if (y2 && (split_n % 64 || split_n <= 0 || split_n >= N)) return LFSR_E_ARG;
-  if ((x_stride | x_choff | y_stride | y_choff) & 3 || (y2 && ((y2_stride | y2_choff) & 3)) || (pe && ((pe_stride & 3) || pe_stride < K || pe_rows <= 0 || pe_div <= 0))) return LFSR_E_ARG;
-  if (x_choff < 0 || y_choff < 0 || (y2 && y2_choff < 0)) return LFSR_E_ARG;
-  if (x_stride < x_choff + K || y_stride < y_choff + (y2 ? split_n : N) || (y2 && y2_stride < y2_choff + N - split_n)) return LFSR_E_ARG;
-  if (((uintptr_t)y | (uintptr_t)y2 | (uintptr_t)x | (uintptr_t)pe | (uintptr_t)ln_g | (uintptr_t)ln_b | (uintptr_t)w_packed) & 15) return LFSR_E_ARG;
-  if (!q_span_ok(M, x_stride) || !q_span_ok(M, y_stride) || (y2 && !q_span_ok(M, y2_stride))) return LFSR_E_ARG;
+// LayerNorm + q | k | v projection (the LN form of LfsrLin); (K, N) = (128, 384) or (64, 192)
+int lfsr_gemm_bf16_ln_launch(const LfsrLin& c, hipStream_t st) {
+  if (!((c.K == 128 && c.N == 384) || (c.K == 64 && c.N == 192)) || !c.x || !c.w_packed || !c.ln_g || !c.ln_b || !c.y || c.M <= 0 || c.ln_cols < 0 || c.ln_cols > c.N || c.ln_cols % 64) return LFSR_E_ARG;
+  if (c.y2 && (c.split_n % 64 || c.split_n <= 0 || c.split_n >= c.N)) return LFSR_E_ARG;
+  if ((c.x_stride | c.x_choff | c.y_stride | c.y_choff) & 3 || (c.y2 && ((c.y2_stride | c.y2_choff) & 3)) || (c.pe && ((c.pe_stride & 3) || c.pe_stride < c.K || c.pe_rows <= 0 || c.pe_div <= 0))) return LFSR_E_ARG;
+  if (c.x_choff < 0 || c.y_choff < 0 || (c.y2 && c.y2_choff < 0)) return LFSR_E_ARG;
+  if (c.x_stride < c.x_choff + c.K || c.y_stride < c.y_choff + (c.y2 ? c.split_n : c.N) || (c.y2 && c.y2_stride < c.y2_choff + c.N - c.split_n)) return LFSR_E_ARG;
+  if (((uintptr_t)c.y | (uintptr_t)c.y2 | (uintptr_t)c.x | (uintptr_t)c.pe | (uintptr_t)c.ln_g | (uintptr_t)c.ln_b | (uintptr_t)c.w_packed) & 15) return LFSR_E_ARG;
+  if (!q_span_ok(c.M, c.x_stride) || !q_span_ok(c.M, c.y_stride) || (c.y2 && !q_span_ok(c.M, c.y2_stride))) return LFSR_E_ARG;
   GemmB16Args p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wp = w_packed; p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff; p.M = M; p.slope = 1.0f;
-  p.ln_g = ln_g; p.ln_b = ln_b; p.ln_eps = ln_eps; p.ln_cols = ln_cols; p.pe = pe; p.pe_stride = pe_stride; p.pe_rows = pe_rows; p.pe_div = pe_div;
-  p.Y2 = y2; p.y2_stride = y2_stride; p.y2_choff = y2_choff; p.split_n = split_n;
-  return K == 128 ? launch_gemm_bf16<128, 384, true, 512>(p, st) : launch_gemm_bf16<64, 192, true, 512>(p, st);
+  p.X = c.x; p.x_stride = c.x_stride; p.x_choff = c.x_choff; p.Wp = c.w_packed; p.Y = c.y; p.y_stride = c.y_stride; p.y_choff = c.y_choff; p.M = c.M; p.slope = 1.0f;
+  p.ln_g = c.ln_g; p.ln_b = c.ln_b; p.ln_eps = c.ln_eps; p.ln_cols = c.ln_cols; p.pe = c.pe; p.pe_stride = c.pe_stride; p.pe_rows = c.pe_rows; p.pe_div = c.pe_div;
+  p.Y2 = c.y2; p.y2_stride = c.y2_stride; p.y2_choff = c.y2_choff; p.split_n = c.split_n;
+  return c.K == 128 ? launch_gemm_bf16<128, 384, true, 512>(p, st) : launch_gemm_bf16<64, 192, true, 512>(p, st);
 }
 
 // feed-forward block, (K1, H, N2) = (128, 256, 128) or (64, 128, 64); ln_g / ln_b null: x is already normalised
-int lfsr_ffn_bf16_launch(const float* x, int x_stride, int x_choff, const float* ln_g, const float* ln_b, float ln_eps, const float* w1_packed, const float* w2_packed,
-                         const float* res, int res_stride, int res_choff, float* y, int y_stride, int y_choff,
-                         long long M, int K1, int H, int N2, float slope, hipStream_t st) {
-  if (!((K1 == 128 && H == 256 && N2 == 128) || (K1 == 64 && H == 128 && N2 == 64)) || !x || !w1_packed || !w2_packed || !y || M <= 0) return LFSR_E_ARG;
-  if ((ln_g != nullptr) != (ln_b != nullptr)) return LFSR_E_ARG;
-  if ((x_stride | x_choff | y_stride | y_choff) & 3 || (res && ((res_stride | res_choff) & 3))) return LFSR_E_ARG;
-  if (x_choff < 0 || y_choff < 0 || (res && res_choff < 0) || x_stride < x_choff + K1 || y_stride < y_choff + N2 || (res && res_stride < res_choff + N2)) return LFSR_E_ARG;
-  if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)res | (uintptr_t)w1_packed | (uintptr_t)w2_packed | (uintptr_t)ln_g | (uintptr_t)ln_b) & 15) return LFSR_E_ARG;
-  if (!q_span_ok(M, x_stride) || !q_span_ok(M, y_stride) || (res && !q_span_ok(M, res_stride))) return LFSR_E_ARG;
+int lfsr_ffn_bf16_launch(const LfsrFfn& f, hipStream_t st) {
+  if (!((f.K1 == 128 && f.H == 256 && f.N2 == 128) || (f.K1 == 64 && f.H == 128 && f.N2 == 64)) || !f.x || !f.w1_packed || !f.w2_packed || !f.y || f.M <= 0) return LFSR_E_ARG;
+  if ((f.ln_g != nullptr) != (f.ln_b != nullptr)) return LFSR_E_ARG;
+  if ((f.x_stride | f.x_choff | f.y_stride | f.y_choff) & 3 || (f.res && ((f.res_stride | f.res_choff) & 3))) return LFSR_E_ARG;
+  if (f.x_choff < 0 || f.y_choff < 0 || (f.res && f.res_choff < 0) || f.x_stride < f.x_choff + f.K1 || f.y_stride < f.y_choff + f.N2 || (f.res && f.res_stride < f.res_choff + f.N2)) return LFSR_E_ARG;
+  if (((uintptr_t)f.x | (uintptr_t)f.y | (uintptr_t)f.res | (uintptr_t)f.w1_packed | (uintptr_t)f.w2_packed | (uintptr_t)f.ln_g | (uintptr_t)f.ln_b) & 15) return LFSR_E_ARG;
+  if (!q_span_ok(f.M, f.x_stride) || !q_span_ok(f.M, f.y_stride) || (f.res && !q_span_ok(f.M, f.res_stride))) return LFSR_E_ARG;
   FfnB16Args p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.W1 = w1_packed; p.W2 = w2_packed;
-  p.R = res; p.r_stride = res_stride; p.r_choff = res_choff; p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff;
-  p.M = M; p.slope = slope; p.ln_g = ln_g; p.ln_b = ln_b; p.ln_eps = ln_eps;
-  return K1 == 128 ? launch_ffn_bf16<128>(p, st) : launch_ffn_bf16<64>(p, st);
+  p.X = f.x; p.x_stride = f.x_stride; p.x_choff = f.x_choff; p.W1 = f.w1_packed; p.W2 = f.w2_packed;
+  p.R = f.res; p.r_stride = f.res_stride; p.r_choff = f.res_choff; p.Y = f.y; p.y_stride = f.y_stride; p.y_choff = f.y_choff;
+  p.M = f.M; p.slope = f.slope; p.ln_g = f.ln_g; p.ln_b = f.ln_b; p.ln_eps = f.ln_eps;
+  return f.K1 == 128 ? launch_ffn_bf16<128>(p, st) : launch_ffn_bf16<64>(p, st);
 }

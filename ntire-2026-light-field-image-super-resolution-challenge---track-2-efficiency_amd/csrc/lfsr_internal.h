@@ -185,43 +185,40 @@ int lfsr_pack_weight_chunkT(const float* w, float* out, int O, int C, int ch, in
 // internet_train.hip: dgrad pack from a forward pack Wp[T][Npad_in][C]: out[t'][k'][n] = Wp[flip ? T-1-t' : t'][n][k0 + k'] (n < O, k' < Kc)
 int lfsr_pack_T_from_fwd(const float* Wp, float* out, int T, int Npad_in, int C, int O, int k0, int Kc, int flip, hipStream_t st);
 
-// rowgemm.hip: persistent row-streaming GEMM with LDS-resident weights; LFSR_E_ARG = shape not covered (use the gather-GEMM)
-int lfsr_rowgemm_dgrad144_launch(const float* dy, int dy_stride, int dy_choff, const float* wT_packed, const float* mk, int mk_stride, int mk_choff, float mk_slope,
-                                 float* dx, int dx_stride, int dx_choff, long long M, hipStream_t st);
-int lfsr_rowgemm_ln_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* ln_g, const float* ln_b, float ln_eps, int ln_cols,
-                           const float* pe, int pe_stride, int pe_rows, int pe_div, float* y, int y_stride, int y_choff,
-                           float* y2, int y2_stride, int y2_choff, int split_n, long long M, int N, hipStream_t st);
-int lfsr_rowgemm_b3_ln_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* ln_g, const float* ln_b, float ln_eps, int ln_cols,
-                              const float* pe, int pe_stride, int pe_rows, int pe_div, float* y, int y_stride, int y_choff,
-                              float* y2, int y2_stride, int y2_choff, int split_n, long long M, int N, hipStream_t st);
-// lnlin_b3.hip: LayerNorm + q | k | v projection with the weights in registers and the token rows through LDS (K = 128, N = 384); LFSR_E_ARG = shape not covered
-int lfsr_lnlin_b3_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* ln_g, const float* ln_b, float ln_eps, int ln_cols,
-                         const float* pe, int pe_stride, int pe_rows, int pe_div, float* y, int y_stride, int y_choff,
-                         float* y2, int y2_stride, int y2_choff, int split_n, long long M, int N, hipStream_t st);
-int lfsr_rowgemm_b3_dgrad_launch(const float* dy, int dy_stride, int dy_choff, const float* wT_packed, const float* mk, int mk_stride, int mk_choff, float mk_slope,
-                                 float* dx, int dx_stride, int dx_choff, long long M, int N, hipStream_t st);
-int lfsr_rowgemm_b3_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* res, int res_stride, int res_choff,
-                           float* y, int y_stride, int y_choff, long long M, int N, float slope, hipStream_t st);
-// gemm_bf16.hip: the same three operators on bf16 operands (lfsr_set_gemm_arithmetic(LFSR_GEMM_ARITH_BF16)); LFSR_E_ARG = not covered, nothing written
-int lfsr_gemm_bf16_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* res, int res_stride, int res_choff,
-                          float* y, int y_stride, int y_choff, long long M, int N, float slope, hipStream_t st);
-int lfsr_gemm_bf16_ln_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* ln_g, const float* ln_b, float ln_eps, int ln_cols,
-                             const float* pe, int pe_stride, int pe_rows, int pe_div, float* y, int y_stride, int y_choff,
-                             float* y2, int y2_stride, int y2_choff, int split_n, long long M, int N, hipStream_t st);
-int lfsr_ffn_bf16_launch(const float* x, int x_stride, int x_choff, const float* ln_g, const float* ln_b, float ln_eps, const float* w1_packed, const float* w2_packed,
-                         const float* res, int res_stride, int res_choff, float* y, int y_stride, int y_choff,
-                         long long M, int K1, int H, int N2, float slope, hipStream_t st);
-int lfsr_rowgemm_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* bias,
-                        const float* res, int res_stride, int res_choff, float* y, int y_stride, int y_choff, long long M, int N, float slope, hipStream_t st);
-
-// ffn_fused.hip: feed-forward block with the LayerNorm in front of it formed in registers (ln_g / ln_b null: x is already normalised)
-int lfsr_ffn_ln_launch(const float* x, int x_stride, int x_choff, const float* ln_g, const float* ln_b, float ln_eps, const float* w1_packed, const float* w2_packed,
-                       const float* res, int res_stride, int res_choff, float* y, int y_stride, int y_choff,
-                       long long M, int K1, int H, int N2, float slope, hipStream_t st, const void* wsplit = nullptr);   // wsplit: the weights' pre-split image (lfsr_ffn_b3_presplit), optional
-
-int lfsr_ffn_b3_launch(const float* x, int x_stride, int x_choff, const float* ln_g, const float* ln_b, float ln_eps, const float* w1_packed, const float* w2_packed,
-                       const float* res, int res_stride, int res_choff, float* y, int y_stride, int y_choff,
-                       long long M, int K1, int H, int N2, float slope, hipStream_t st, const void* wsplit = nullptr);
+// One dense linear of the row-streaming GEMM family in every form it has: y = act(x W^T (+ bias), slope) (+ res), K -> N over M rows; optional fields null / 0 when absent.
+// mk: the data gradient of a 1x1 conv, y = (x W) * (mk > 0 ? 1 : mk_slope).  ln_g / ln_b: the weight rows n < ln_cols see LayerNorm(x (+ pe)) (pe row of token m:
+// (m / pe_div) % pe_rows), the others x itself.  y2: the columns n >= split_n go to y2 (column n - split_n).
+struct LfsrLin {
+  const float* x; int x_stride, x_choff;
+  const float *w_packed, *bias;
+  float* y; int y_stride, y_choff;
+  const float* res; int res_stride, res_choff;
+  const float* mk; int mk_stride, mk_choff; float mk_slope;
+  const float *ln_g, *ln_b, *pe; float ln_eps; int ln_cols, pe_stride, pe_rows, pe_div;
+  float* y2; int y2_stride, y2_choff, split_n;
+  long long M; int K, N; float slope;
+};
+// One feed-forward block: y = res + W2 act(W1 LayerNorm(x), slope), K1 -> H -> N2 (ln_g / ln_b null: x is already normalised); wsplit: lfsr_ffn_b3_presplit's image, optional
+struct LfsrFfn {
+  const float* x; int x_stride, x_choff;
+  const float *ln_g, *ln_b, *w1_packed, *w2_packed; float ln_eps; const void* wsplit;
+  const float* res; int res_stride, res_choff;
+  float* y; int y_stride, y_choff;
+  long long M; int K1, H, N2; float slope;
+};
+// A launcher launches its own kernel only; LFSR_E_ARG = the call is not covered and nothing was written: the dispatcher (rowgemm.cpp) goes down its chain.
+using LfsrLinFn = int(const LfsrLin& c, hipStream_t st);
+using LfsrFfnFn = int(const LfsrFfn& f, hipStream_t st);
+LfsrLinFn lfsr_rowgemm_launch, lfsr_rowgemm_ln_launch, lfsr_rowgemm_dgrad144_launch;            // rowgemm.hip, fp32 MFMA: the linear, its LN form, the 64 -> 144 data gradient
+LfsrLinFn lfsr_rowgemm_b3_launch, lfsr_rowgemm_b3_ln_launch, lfsr_rowgemm_b3_dgrad_launch, lfsr_lnlin_b3_launch;   // rowgemm_b3.hip, the exact three-term bf16 split: the same three; lnlin_b3.hip: its LN form with the weights in registers
+LfsrLinFn lfsr_gemm_bf16_launch, lfsr_gemm_bf16_ln_launch;                                      // gemm_bf16.hip, bf16 operands (LFSR_GEMM_ARITH_BF16)
+LfsrFfnFn lfsr_ffn_launch, lfsr_ffn_b3_launch, lfsr_ffn_bf16_launch;                            // ffn_fused.hip (fp32 MFMA), ffn_b3.hip (the one that reads wsplit), gemm_bf16.hip
+bool lfsr_rowgemm_ok(const LfsrLin& c), lfsr_rowgemm_ln_ok(const LfsrLin& c), lfsr_rowgemm_b3_ln_ok(const LfsrLin& c);   // the operands lfsr_rowgemm_launch / _ln_launch / _b3_ln_launch take
+// rowgemm.cpp: which kernel runs.  lfsr_gemm_sel: the family's lab selectors (LFSR_ROWGEMM, LFSR_FFN, LFSR_LNLIN, LFSR_DGRAD_PW) with lfsr_set_arithmetic(f32) folded
+// in, parsed at every call, never cached; the only reader of their characters.  f32 / ffn_f32 / dgrad_f32: the fp32-MFMA kernels; wide: LFSR_ROWGEMM=128
+struct LfsrGemmSel { bool f32, wide, ffn_f32, ffn_chunks, lnlin, dgrad_f32, dgrad_gather; };
+LfsrGemmSel lfsr_gemm_sel();
+LfsrLinFn lfsr_linear_run, lfsr_linear_ln_run, lfsr_dgrad144_run; LfsrFfnFn lfsr_ffn_run;   // lfsr_linear_run's LFSR_E_ARG: no row-streaming kernel covers the call, the caller runs its gather-GEMM
 size_t lfsr_ffn_b3_presplit_bytes(int K1, int H, int N2);
 int lfsr_ffn_b3_presplit(const float* w1_packed, const float* w2_packed, int K1, int H, int N2, void* out, hipStream_t st);
 

@@ -296,23 +296,20 @@ int launch_lnlin(const LnLinArgs& p, long long nst, hipStream_t st) {
 
 }  // namespace
 
-// LFSR_E_ARG = shape not covered (the caller keeps the panel form, rowgemm_b3.hip): (K, N) = (128, 384) or (64, 192) (waves x 3 column tiles), ln_cols / split_n multiples of 16
-int lfsr_lnlin_b3_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* ln_g, const float* ln_b, float ln_eps, int ln_cols,
-                         const float* pe, int pe_stride, int pe_rows, int pe_div, float* y, int y_stride, int y_choff,
-                         float* y2, int y2_stride, int y2_choff, int split_n, long long M, int N, hipStream_t st) {
-  if (!((K == 128 && N == 384) || (K == 64 && N == 192)) || !x || !w_packed || !ln_g || !ln_b || !y || M <= 0 || ln_cols < 0 || ln_cols > N || ln_cols % 16) return LFSR_E_ARG;
-  if (y2 && (split_n % 16 || split_n <= 0 || split_n >= N)) return LFSR_E_ARG;
-  if ((x_stride | x_choff | y_stride | y_choff) & 3 || (y2 && ((y2_stride | y2_choff) & 3)) || (pe && ((pe_stride & 3) || pe_rows <= 0 || pe_div <= 0))) return LFSR_E_ARG;
-  if (x_stride < x_choff + K || y_stride < y_choff + (y2 ? split_n : N) || (y2 && y2_stride < y2_choff + N - split_n)) return LFSR_E_ARG;
-  if (((uintptr_t)y | (uintptr_t)y2 | (uintptr_t)x | (uintptr_t)pe | (uintptr_t)ln_g | (uintptr_t)ln_b | (uintptr_t)w_packed) & 15) return LFSR_E_ARG;
-  if ((M + 64) * (long long)x_stride * 4 >= (1LL << 31) || (M + 64) * (long long)y_stride * 4 >= (1LL << 31) || (y2 && (M + 64) * (long long)y2_stride * 4 >= (1LL << 31)))
-    return LFSR_E_ARG;      // (32-bit buffer offsets, and 2^31 as the out-of-range marker)
+// LFSR_E_ARG = shape not covered: (K, N) = (128, 384) or (64, 192) (waves x 3 column tiles), ln_cols / split_n multiples of 16
+int lfsr_lnlin_b3_launch(const LfsrLin& c, hipStream_t st) {
+  if (!((c.K == 128 && c.N == 384) || (c.K == 64 && c.N == 192)) || !c.x || !c.w_packed || !c.ln_g || !c.ln_b || !c.y || c.M <= 0 || c.ln_cols < 0 || c.ln_cols > c.N || c.ln_cols % 16) return LFSR_E_ARG;
+  if (c.y2 && (c.split_n % 16 || c.split_n <= 0 || c.split_n >= c.N)) return LFSR_E_ARG;
+  if ((c.x_stride | c.x_choff | c.y_stride | c.y_choff) & 3 || (c.y2 && ((c.y2_stride | c.y2_choff) & 3)) || (c.pe && ((c.pe_stride & 3) || c.pe_rows <= 0 || c.pe_div <= 0))) return LFSR_E_ARG;
+  if (c.x_stride < c.x_choff + c.K || c.y_stride < c.y_choff + (c.y2 ? c.split_n : c.N) || (c.y2 && c.y2_stride < c.y2_choff + c.N - c.split_n)) return LFSR_E_ARG;
+  if (((uintptr_t)c.y | (uintptr_t)c.y2 | (uintptr_t)c.x | (uintptr_t)c.pe | (uintptr_t)c.ln_g | (uintptr_t)c.ln_b | (uintptr_t)c.w_packed) & 15) return LFSR_E_ARG;
+  if ((c.M + 64) * (long long)c.x_stride * 4 >= (1LL << 31) || (c.M + 64) * (long long)c.y_stride * 4 >= (1LL << 31) || (c.y2 && (c.M + 64) * (long long)c.y2_stride * 4 >= (1LL << 31))) return LFSR_E_ARG;      // (32-bit buffer offsets, and 2^31 as the out-of-range marker)
   LnLinArgs p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wp = w_packed; p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff;
-  p.Y2 = y2; p.y2_stride = y2_stride; p.y2_choff = y2_choff; p.split_n = split_n; p.M = M; p.N = N;
-  p.ln_g = ln_g; p.ln_b = ln_b; p.ln_eps = ln_eps; p.ln_cols = ln_cols; p.pe = pe; p.pe_stride = pe_stride; p.pe_rows = pe_rows; p.pe_div = pe_div;
-  const long long nst = (M + LL_ROWS - 1) / LL_ROWS;
+  p.X = c.x; p.x_stride = c.x_stride; p.x_choff = c.x_choff; p.Wp = c.w_packed; p.Y = c.y; p.y_stride = c.y_stride; p.y_choff = c.y_choff;
+  p.Y2 = c.y2; p.y2_stride = c.y2_stride; p.y2_choff = c.y2_choff; p.split_n = c.split_n; p.M = c.M; p.N = c.N;
+  p.ln_g = c.ln_g; p.ln_b = c.ln_b; p.ln_eps = c.ln_eps; p.ln_cols = c.ln_cols; p.pe = c.pe; p.pe_stride = c.pe_stride; p.pe_rows = c.pe_rows; p.pe_div = c.pe_div;
+  const long long nst = (c.M + LL_ROWS - 1) / LL_ROWS;
   if (nst > 0x7fffffffLL / LL_ROWS) return LFSR_E_ARG;
   p.nstages = (int)nst;
-  return K == 128 ? launch_lnlin<128>(p, nst, st) : launch_lnlin<64>(p, nst, st);
+  return c.K == 128 ? launch_lnlin<128>(p, nst, st) : launch_lnlin<64>(p, nst, st);
 }

@@ -237,104 +237,60 @@ int launch_rowgemm(const RowGemmArgs& p, hipStream_t st) {
 
 }  // namespace
 
-// returns LFSR_E_ARG when the shape is not covered (caller falls back to the gather-GEMM)
 // the data gradient of a 64-output 1x1 conv whose input has N = 144 channels (DistgSSR fuse.0: dCAT = (dF W) . lrelu'(CAT)): one 192-column
 // panel (the weight rows beyond N are zero-filled, stores beyond N are skipped), X streamed once, the mask applied in the epilogue
-int lfsr_rowgemm_dgrad144_launch(const float* dy, int dy_stride, int dy_choff, const float* wT_packed, const float* mk, int mk_stride, int mk_choff, float mk_slope,
-                                 float* dx, int dx_stride, int dx_choff, long long M, hipStream_t st) {
-  if ((dy_stride | dy_choff | dx_stride | dx_choff) & 3 || (mk && ((mk_stride | mk_choff) & 3))) return LFSR_E_ARG;
-  if (((uintptr_t)dy | (uintptr_t)dx | (uintptr_t)mk | (uintptr_t)wT_packed) & 15) return LFSR_E_ARG;
-  if (M * (long long)dy_stride * 4 >= (1LL << 31) || M * (long long)dx_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;
-  {   // default: the three-term bf16 form (rowgemm_b3.hip, three 64-column panels of which the last holds 16 columns); LFSR_ROWGEMM=f32 / lfsr_set_arithmetic(f32): the kernel below
-    const char* rsel = lfsr_sel("LFSR_ROWGEMM");
-    const char* dsel = lfsr_sel("LFSR_DGRAD_PW");      // "f32": the fp32-MFMA kernel for this data gradient only (A/B runs; "gather": see bwd_ops.hip)
-    if (mk && !(rsel && (rsel[0] == 'f' || rsel[0] == '1')) && !(dsel && dsel[0] == 'f') && !lfsr_arith_f32()) {
-      const int rc = lfsr_rowgemm_b3_dgrad_launch(dy, dy_stride, dy_choff, wT_packed, mk, mk_stride, mk_choff, mk_slope, dx, dx_stride, dx_choff, M, 144, st);
-      if (rc != LFSR_E_ARG) return rc;
-    }
-  }
+int lfsr_rowgemm_dgrad144_launch(const LfsrLin& c, hipStream_t st) {
+  if ((c.x_stride | c.x_choff | c.y_stride | c.y_choff) & 3 || (c.mk && ((c.mk_stride | c.mk_choff) & 3))) return LFSR_E_ARG;
+  if (((uintptr_t)c.x | (uintptr_t)c.y | (uintptr_t)c.mk | (uintptr_t)c.w_packed) & 15) return LFSR_E_ARG;
+  if (c.M * (long long)c.x_stride * 4 >= (1LL << 31) || c.M * (long long)c.y_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;
   RowGemmArgs p{};
-  p.X = dy; p.x_stride = dy_stride; p.x_choff = dy_choff; p.Wp = wT_packed; p.Mk = mk; p.mk_stride = mk_stride; p.mk_choff = mk_choff; p.mk_slope = mk_slope;
-  p.Y = dx; p.y_stride = dx_stride; p.y_choff = dx_choff; p.M = M; p.N = 144; p.slope = 1.0f;
+  p.X = c.x; p.x_stride = c.x_stride; p.x_choff = c.x_choff; p.Wp = c.w_packed; p.Mk = c.mk; p.mk_stride = c.mk_stride; p.mk_choff = c.mk_choff; p.mk_slope = c.mk_slope;
+  p.Y = c.y; p.y_stride = c.y_stride; p.y_choff = c.y_choff; p.M = c.M; p.N = 144; p.slope = 1.0f;
   return launch_rowgemm<64, 192, 64>(p, st);
 }
 
-// LayerNorm + projections in one launch (BasicTrans.forward, EPIT.py:113-121; SpaTrans / AngTrans, LFT.py:190-197 / :236-241): the weight rows n < ln_cols
-// (q | k) see LayerNorm(x (+ pe)), the rows n >= ln_cols (v) see x itself; columns n >= split_n go to y2.  K = 64 or 128, N and split_n multiples of 64.
-int lfsr_rowgemm_ln_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* ln_g, const float* ln_b, float ln_eps, int ln_cols,
-                           const float* pe, int pe_stride, int pe_rows, int pe_div, float* y, int y_stride, int y_choff,
-                           float* y2, int y2_stride, int y2_choff, int split_n, long long M, int N, hipStream_t st) {
-  LfsrOpTimer op_t("linear_ln", K, N, st);
-  if (!x || !w_packed || !ln_g || !ln_b || !y || M <= 0 || N <= 0 || N % 64 || ln_cols % 64 || (y2 && (split_n % 64 || split_n <= 0 || split_n >= N))) return LFSR_E_ARG;
-  if ((x_stride | x_choff | y_stride | y_choff) & 3 || (y2 && ((y2_stride | y2_choff) & 3)) || (pe && ((pe_stride & 3) || pe_rows <= 0 || pe_div <= 0))) return LFSR_E_ARG;
-  if (x_stride < x_choff + K || y_stride < y_choff + (y2 ? split_n : N) || (y2 && y2_stride < y2_choff + N - split_n)) return LFSR_E_ARG;
-  if (((uintptr_t)y | (uintptr_t)y2 | (uintptr_t)x | (uintptr_t)pe | (uintptr_t)ln_g | (uintptr_t)ln_b) & 15) return LFSR_E_ARG;
-  if ((M + 256) * (long long)x_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;
-  {   // default: the three-term bf16 form (rowgemm_b3.hip); LFSR_ROWGEMM=f32 keeps the fp32-MFMA kernel below (bit-identical to LayerNorm launch + fp32 row-GEMM)
-    const char* rsel = lfsr_sel("LFSR_ROWGEMM");
-    if (!(rsel && (rsel[0] == 'f' || rsel[0] == '1')) && !lfsr_arith_f32()) {
-      if (lfsr_gemm_arith_bf16()) {   // lfsr_set_gemm_arithmetic(bf16): bf16 operands (gemm_bf16.hip) where the shape is covered
-        const int rq = lfsr_gemm_bf16_ln_launch(x, x_stride, x_choff, K, w_packed, ln_g, ln_b, ln_eps, ln_cols, pe, pe_stride, pe_rows, pe_div, y, y_stride, y_choff,
-                                                y2, y2_stride, y2_choff, split_n, M, N, st);
-        if (rq != LFSR_E_ARG) return rq;
-      }
-      const int rc = lfsr_rowgemm_b3_ln_launch(x, x_stride, x_choff, K, w_packed, ln_g, ln_b, ln_eps, ln_cols, pe, pe_stride, pe_rows, pe_div, y, y_stride, y_choff,
-                                               y2, y2_stride, y2_choff, split_n, M, N, st);
-      if (rc != LFSR_E_ARG) return rc;
-    }
-  }
+// LayerNorm + projections in one launch (BasicTrans.forward, EPIT.py:113-121; SpaTrans / AngTrans, LFT.py:190-197 / :236-241): the weight rows n < ln_cols (q | k) see
+// LayerNorm(x (+ pe)), the rows n >= ln_cols (v) x itself; columns n >= split_n go to y2.  K = 64 or 128, N and split_n multiples of 64.  Bit-identical to LayerNorm + row-GEMM.
+bool lfsr_rowgemm_ln_ok(const LfsrLin& c) {
+  if (!c.x || !c.w_packed || !c.ln_g || !c.ln_b || !c.y || c.M <= 0 || c.N <= 0 || c.N % 64 || c.ln_cols % 64 || (c.y2 && (c.split_n % 64 || c.split_n <= 0 || c.split_n >= c.N))) return false;
+  if ((c.x_stride | c.x_choff | c.y_stride | c.y_choff) & 3 || (c.y2 && ((c.y2_stride | c.y2_choff) & 3)) || (c.pe && ((c.pe_stride & 3) || c.pe_rows <= 0 || c.pe_div <= 0))) return false;
+  if (c.x_stride < c.x_choff + c.K || c.y_stride < c.y_choff + (c.y2 ? c.split_n : c.N) || (c.y2 && c.y2_stride < c.y2_choff + c.N - c.split_n)) return false;
+  if (((uintptr_t)c.y | (uintptr_t)c.y2 | (uintptr_t)c.x | (uintptr_t)c.pe | (uintptr_t)c.ln_g | (uintptr_t)c.ln_b) & 15) return false;
+  return (c.M + 256) * (long long)c.x_stride * 4 < (1LL << 31);
+}
+int lfsr_rowgemm_ln_launch(const LfsrLin& c, hipStream_t st) {
+  if (!lfsr_rowgemm_ln_ok(c)) return LFSR_E_ARG;
   RowGemmArgs p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wp = w_packed; p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff; p.M = M; p.N = N; p.slope = 1.0f;
-  p.ln_g = ln_g; p.ln_b = ln_b; p.ln_eps = ln_eps; p.ln_cols = ln_cols; p.pe = pe; p.pe_stride = pe_stride; p.pe_rows = pe_rows; p.pe_div = pe_div;
-  p.Y2 = y2; p.y2_stride = y2_stride; p.y2_choff = y2_choff; p.split_n = split_n;
-  switch (K) {
+  p.X = c.x; p.x_stride = c.x_stride; p.x_choff = c.x_choff; p.Wp = c.w_packed; p.Y = c.y; p.y_stride = c.y_stride; p.y_choff = c.y_choff; p.M = c.M; p.N = c.N; p.slope = 1.0f;
+  p.ln_g = c.ln_g; p.ln_b = c.ln_b; p.ln_eps = c.ln_eps; p.ln_cols = c.ln_cols; p.pe = c.pe; p.pe_stride = c.pe_stride; p.pe_rows = c.pe_rows; p.pe_div = c.pe_div;
+  p.Y2 = c.y2; p.y2_stride = c.y2_stride; p.y2_choff = c.y2_choff; p.split_n = c.split_n;
+  switch (c.K) {
     case 64: return launch_rowgemm<64, 64, 64, true>(p, st);
     case 128: return launch_rowgemm<128, 64, 64, true>(p, st);
     default: return LFSR_E_ARG;
   }
 }
 
-int lfsr_rowgemm_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* bias,
-                        const float* res, int res_stride, int res_choff, float* y, int y_stride, int y_choff, long long M, int N, float slope, hipStream_t st) {
-  if ((x_stride | x_choff) & 3 || N % 32) return LFSR_E_ARG;
-  // the epilogue stores / loads 16 B per lane: every operand row and channel offset a multiple of four floats, 16-B aligned bases
-  if ((y_stride | y_choff) & 3 || (res && ((res_stride | res_choff) & 3))) return LFSR_E_ARG;
-  if (((uintptr_t)y | (uintptr_t)x | (uintptr_t)res | (uintptr_t)bias) & 15) return LFSR_E_ARG;
-  if ((M + 256) * (long long)x_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets into x (caller falls back to the gather-GEMM)
+// the epilogue stores / loads 16 B per lane: every operand row and channel offset a multiple of four floats, 16-B aligned bases; 32-bit byte offsets into x
+bool lfsr_rowgemm_ok(const LfsrLin& c) {
+  if ((c.x_stride | c.x_choff) & 3 || c.N % 64 || (c.y_stride | c.y_choff) & 3 || (c.res && ((c.res_stride | c.res_choff) & 3))) return false;
+  if (((uintptr_t)c.y | (uintptr_t)c.x | (uintptr_t)c.res | (uintptr_t)c.bias) & 15) return false;
+  return (c.M + 256) * (long long)c.x_stride * 4 < (1LL << 31);
+}
+int lfsr_rowgemm_launch(const LfsrLin& c, hipStream_t st) {
+  if (!lfsr_rowgemm_ok(c)) return LFSR_E_ARG;
   RowGemmArgs p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wp = w_packed; p.bias = bias; p.R1 = res; p.r1_stride = res_stride; p.r1_choff = res_choff;
-  p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff; p.M = M; p.N = N; p.slope = slope;
-  // 64-row tiles, 64-column panels: <= 76 KB of LDS -> two 256-thread blocks per CU, which is what keeps HBM loads in flight
-  // while the other block runs its MFMAs
-  if (N % 64) return LFSR_E_ARG;
-  // LFSR_ROWGEMM=128 (N a multiple of 128: the transformer projections): 128-row x 128-column tiles, one 512-thread block per CU, each wave 32 rows
-  // x 64 columns -- X streamed once per 128 output columns, a B fragment feeding two MFMA column tiles.  Measured on EPIT (B = 8, two runs each in
-  // one call, profiles/r02_logs/ab_bench_lines.json: bench11_epit*.json): 637-639 patches/s against 659-660 for the 64 x 64 form -- one block per CU hides less HBM latency
-  // than two; the 64 x 64 form stays the default
-  const char* rsel = lfsr_sel("LFSR_ROWGEMM");
-  // the bias-free K = 64 / 128 linears (the transformers' projections) run on the bf16 MFMA pipe with their fp32 operands split EXACTLY into three bf16 terms
-  // (rowgemm_b3.hip; error against fp64 below this file's fp32-MFMA kernel: tools/b3_accuracy.py); LFSR_ROWGEMM=f32 keeps the fp32-MFMA form (A/B runs), 128 its wide tiles
-  if (!(rsel && (rsel[0] == 'f' || rsel[0] == '1')) && !lfsr_arith_f32() && !bias && (K == 64 || K == 128 || K == 144)) {
-    if (lfsr_gemm_arith_bf16() && K != 144) {   // lfsr_set_gemm_arithmetic(bf16): bf16 operands (gemm_bf16.hip); K = 144 (DistgSSR's fuse.0) keeps the default
-      const int rq = lfsr_gemm_bf16_launch(x, x_stride, x_choff, K, w_packed, res, res_stride, res_choff, y, y_stride, y_choff, M, N, slope, st);
-      if (rq != LFSR_E_ARG) return rq;
-    }
-    const int rc = lfsr_rowgemm_b3_launch(x, x_stride, x_choff, K, w_packed, res, res_stride, res_choff, y, y_stride, y_choff, M, N, slope, st);
-    if (rc != LFSR_E_ARG) return rc;
-  }
-  const bool wide = N % 128 == 0 && rsel && rsel[0] == '1';
-  switch (K) {
+  p.X = c.x; p.x_stride = c.x_stride; p.x_choff = c.x_choff; p.Wp = c.w_packed; p.bias = c.bias; p.R1 = c.res; p.r1_stride = c.res_stride; p.r1_choff = c.res_choff;
+  p.Y = c.y; p.y_stride = c.y_stride; p.y_choff = c.y_choff; p.M = c.M; p.N = c.N; p.slope = c.slope;
+  // 64-row tiles, 64-column panels: <= 76 KB of LDS -> two 256-thread blocks per CU, which is what keeps HBM loads in flight while the other block runs its MFMAs
+  // LFSR_ROWGEMM=128 (N a multiple of 128: the transformer projections): 128-row x 128-column tiles, one 512-thread block per CU, each wave 32 rows x 64 columns -- X
+  // streamed once per 128 output columns, a B fragment feeding two MFMA column tiles.  Measured on EPIT (B = 8, two runs each in one call, profiles/r02_logs/
+  // ab_bench_lines.json: bench11_epit*.json): 637-639 patches/s against 659-660 for the 64 x 64 form -- one block per CU hides less HBM latency than two; 64 x 64 stays the default
+  const bool wide = c.N % 128 == 0 && lfsr_gemm_sel().wide;
+  switch (c.K) {
     case 64: return wide ? launch_rowgemm<64, 128, 128>(p, st) : launch_rowgemm<64, 64, 64>(p, st);
     case 128: return wide ? launch_rowgemm<128, 128, 128>(p, st) : launch_rowgemm<128, 64, 64>(p, st);
     case 144: return launch_rowgemm<144, 64, 64>(p, st);
     default: return LFSR_E_ARG;
   }
-}
-
-extern "C" int lfsr_linear_ln_fwd(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* gamma, const float* beta,
-                                  float eps, int ln_cols, const float* pe, int pe_stride, int pe_rows, int pe_div,
-                                  float* y, int y_stride, int y_choff, float* y2, int y2_stride, int y2_choff, int split_n,
-                                  long long M, int N, void* stream) {
-  return lfsr_rowgemm_ln_launch(x, x_stride, x_choff, K, w_packed, gamma, beta, eps, ln_cols, pe, pe_stride, pe_rows, pe_div, y, y_stride, y_choff,
-                                y2, y2_stride, y2_choff, split_n, M, N, lfsr_stream(stream));
 }

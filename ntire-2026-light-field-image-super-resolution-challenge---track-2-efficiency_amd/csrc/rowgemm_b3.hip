@@ -292,19 +292,17 @@ int launch_b3(const RowGemmB3Args& p, hipStream_t st) {
 
 }  // namespace
 
-// LFSR_E_ARG = shape not covered (the caller runs the fp32-MFMA row-GEMM)
-int lfsr_rowgemm_b3_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* res, int res_stride, int res_choff,
-                           float* y, int y_stride, int y_choff, long long M, int N, float slope, hipStream_t st) {
-  if ((x_stride | x_choff) & 3 || N % 64 || (y_stride | y_choff) & 3 || (res && ((res_stride | res_choff) & 3))) return LFSR_E_ARG;
-  if (((uintptr_t)y | (uintptr_t)x | (uintptr_t)res | (uintptr_t)w_packed) & 15) return LFSR_E_ARG;
-  if ((M + 128) * (long long)x_stride * 4 >= (1LL << 31) || (M + 128) * (long long)y_stride * 4 >= (1LL << 31) || (res && (M + 128) * (long long)res_stride * 4 >= (1LL << 31)))
-    return LFSR_E_ARG;      // (32-bit buffer offsets, and 2^31 as the out-of-range marker)
+// Each launcher: LFSR_E_ARG = shape or operands not covered
+int lfsr_rowgemm_b3_launch(const LfsrLin& c, hipStream_t st) {
+  if ((c.x_stride | c.x_choff) & 3 || c.N % 64 || (c.y_stride | c.y_choff) & 3 || (c.res && ((c.res_stride | c.res_choff) & 3))) return LFSR_E_ARG;
+  if (((uintptr_t)c.y | (uintptr_t)c.x | (uintptr_t)c.res | (uintptr_t)c.w_packed) & 15) return LFSR_E_ARG;
+  if ((c.M + 128) * (long long)c.x_stride * 4 >= (1LL << 31) || (c.M + 128) * (long long)c.y_stride * 4 >= (1LL << 31) || (c.res && (c.M + 128) * (long long)c.res_stride * 4 >= (1LL << 31))) return LFSR_E_ARG;      // (32-bit buffer offsets, and 2^31 as the out-of-range marker)
   RowGemmB3Args p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wp = w_packed; p.R1 = res; p.r1_stride = res_stride; p.r1_choff = res_choff;
-  p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff; p.M = M; p.N = N; p.slope = slope;
+  p.X = c.x; p.x_stride = c.x_stride; p.x_choff = c.x_choff; p.Wp = c.w_packed; p.R1 = c.res; p.r1_stride = c.res_stride; p.r1_choff = c.res_choff;
+  p.Y = c.y; p.y_stride = c.y_stride; p.y_choff = c.y_choff; p.M = c.M; p.N = c.N; p.slope = c.slope;
   const char* nsel = lfsr_sel("LFSR_B3_NB");       // "128": 128-column panels where N allows (A/B runs: EPIT 818 -> 800, LFT 1636 -> 1646 patches/s; not the default)
-  const bool wide = nsel && nsel[0] == '1' && N % 128 == 0;
-  switch (K) {
+  const bool wide = nsel && nsel[0] == '1' && c.N % 128 == 0;
+  switch (c.K) {
     case 64: return wide ? launch_b3<64, false, 128>(p, st) : launch_b3<64>(p, st);
     case 128: return wide ? launch_b3<128, false, 128>(p, st) : launch_b3<128>(p, st);
     case 144: return launch_b3<160, false, 64, 144>(p, st);      // DistgSSR's fuse.0 (DistgSSR.py:99): 144 valid of 160 operand columns
@@ -312,46 +310,37 @@ int lfsr_rowgemm_b3_launch(const float* x, int x_stride, int x_choff, int K, con
   }
 }
 
-// dx = (dy W) . lrelu'(mk): the data gradient of a 1x1 conv with 64 outputs behind a saved activation mk of N channels (DistgSSR fuse.0: N = 144; train.py:256-264 runs
-// autograd through DistgSSR.py:99); wT_packed [N][64].  LFSR_E_ARG = shape not covered (the caller keeps the fp32-MFMA kernel)
-int lfsr_rowgemm_b3_dgrad_launch(const float* dy, int dy_stride, int dy_choff, const float* wT_packed, const float* mk, int mk_stride, int mk_choff, float mk_slope,
-                                 float* dx, int dx_stride, int dx_choff, long long M, int N, hipStream_t st) {
-  if (!dy || !wT_packed || !mk || !dx || M <= 0 || N <= 0 || N % 16) return LFSR_E_ARG;
-  if ((dy_stride | dy_choff | dx_stride | dx_choff | mk_stride | mk_choff) & 3) return LFSR_E_ARG;
-  if (((uintptr_t)dy | (uintptr_t)dx | (uintptr_t)mk | (uintptr_t)wT_packed) & 15) return LFSR_E_ARG;
-  if ((M + 128) * (long long)dy_stride * 4 >= (1LL << 31) || (M + 128) * (long long)dx_stride * 4 >= (1LL << 31) || (M + 128) * (long long)mk_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;
+// y = (x W) . lrelu'(mk): the data gradient of a 1x1 conv with 64 outputs behind a saved activation mk of N channels (DistgSSR fuse.0: N = 144; train.py:256-264 runs
+// autograd through DistgSSR.py:99); w_packed [N][64]
+int lfsr_rowgemm_b3_dgrad_launch(const LfsrLin& c, hipStream_t st) {
+  if (!c.x || !c.w_packed || !c.mk || !c.y || c.M <= 0 || c.N <= 0 || c.N % 16) return LFSR_E_ARG;
+  if ((c.x_stride | c.x_choff | c.y_stride | c.y_choff | c.mk_stride | c.mk_choff) & 3) return LFSR_E_ARG;
+  if (((uintptr_t)c.x | (uintptr_t)c.y | (uintptr_t)c.mk | (uintptr_t)c.w_packed) & 15) return LFSR_E_ARG;
+  if ((c.M + 128) * (long long)c.x_stride * 4 >= (1LL << 31) || (c.M + 128) * (long long)c.y_stride * 4 >= (1LL << 31) || (c.M + 128) * (long long)c.mk_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;
   RowGemmB3Args p{};
-  p.X = dy; p.x_stride = dy_stride; p.x_choff = dy_choff; p.Wp = wT_packed; p.R1 = mk; p.r1_stride = mk_stride; p.r1_choff = mk_choff; p.r1_mask = 1; p.mk_slope = mk_slope;
-  p.Y = dx; p.y_stride = dx_stride; p.y_choff = dx_choff; p.M = M; p.N = N; p.slope = 1.0f;
+  p.X = c.x; p.x_stride = c.x_stride; p.x_choff = c.x_choff; p.Wp = c.w_packed; p.R1 = c.mk; p.r1_stride = c.mk_stride; p.r1_choff = c.mk_choff; p.r1_mask = 1;
+  p.mk_slope = c.mk_slope; p.Y = c.y; p.y_stride = c.y_stride; p.y_choff = c.y_choff; p.M = c.M; p.N = c.N; p.slope = 1.0f;
   return launch_b3<64>(p, st);
 }
 
-// LayerNorm + attention in-projection in one launch on the three-term bf16 form (argument meaning as lfsr_rowgemm_ln_launch in rowgemm.hip)
-int lfsr_rowgemm_b3_ln_launch(const float* x, int x_stride, int x_choff, int K, const float* w_packed, const float* ln_g, const float* ln_b, float ln_eps, int ln_cols,
-                              const float* pe, int pe_stride, int pe_rows, int pe_div, float* y, int y_stride, int y_choff,
-                              float* y2, int y2_stride, int y2_choff, int split_n, long long M, int N, hipStream_t st) {
-  if (!x || !w_packed || !ln_g || !ln_b || !y || M <= 0 || N <= 0 || N % 64 || ln_cols % 64 || (y2 && (split_n % 64 || split_n <= 0 || split_n >= N))) return LFSR_E_ARG;
-  if ((x_stride | x_choff | y_stride | y_choff) & 3 || (y2 && ((y2_stride | y2_choff) & 3)) || (pe && ((pe_stride & 3) || pe_rows <= 0 || pe_div <= 0))) return LFSR_E_ARG;
-  if (x_stride < x_choff + K || y_stride < y_choff + (y2 ? split_n : N) || (y2 && y2_stride < y2_choff + N - split_n)) return LFSR_E_ARG;
-  if (((uintptr_t)y | (uintptr_t)y2 | (uintptr_t)x | (uintptr_t)pe | (uintptr_t)ln_g | (uintptr_t)ln_b | (uintptr_t)w_packed) & 15) return LFSR_E_ARG;
-  if ((M + 128) * (long long)x_stride * 4 >= (1LL << 31) || (M + 128) * (long long)y_stride * 4 >= (1LL << 31) || (y2 && (M + 128) * (long long)y2_stride * 4 >= (1LL << 31)))
-    return LFSR_E_ARG;
-  {   // K = 128, N = 384 (the q | k | v projections of EPIT and of LFT's spatial transformer): the weights-in-registers form (lnlin_b3.hip); LFSR_LNLIN=0: the panel form below
-    const char* lsel = lfsr_sel("LFSR_LNLIN");
-    if (!(lsel && lsel[0] == '0')) {
-      const int rc = lfsr_lnlin_b3_launch(x, x_stride, x_choff, K, w_packed, ln_g, ln_b, ln_eps, ln_cols, pe, pe_stride, pe_rows, pe_div, y, y_stride, y_choff,
-                                          y2, y2_stride, y2_choff, split_n, M, N, st);
-      if (rc != LFSR_E_ARG) return rc;
-    }
-  }
+// LayerNorm + attention in-projection in one launch on the three-term bf16 form (the LN form of LfsrLin)
+bool lfsr_rowgemm_b3_ln_ok(const LfsrLin& c) {
+  if (!c.x || !c.w_packed || !c.ln_g || !c.ln_b || !c.y || c.M <= 0 || c.N <= 0 || c.N % 64 || c.ln_cols % 64 || (c.y2 && (c.split_n % 64 || c.split_n <= 0 || c.split_n >= c.N))) return false;
+  if ((c.x_stride | c.x_choff | c.y_stride | c.y_choff) & 3 || (c.y2 && ((c.y2_stride | c.y2_choff) & 3)) || (c.pe && ((c.pe_stride & 3) || c.pe_rows <= 0 || c.pe_div <= 0))) return false;
+  if (c.x_stride < c.x_choff + c.K || c.y_stride < c.y_choff + (c.y2 ? c.split_n : c.N) || (c.y2 && c.y2_stride < c.y2_choff + c.N - c.split_n)) return false;
+  if (((uintptr_t)c.y | (uintptr_t)c.y2 | (uintptr_t)c.x | (uintptr_t)c.pe | (uintptr_t)c.ln_g | (uintptr_t)c.ln_b | (uintptr_t)c.w_packed) & 15) return false;
+  return (c.M + 128) * (long long)c.x_stride * 4 < (1LL << 31) && (c.M + 128) * (long long)c.y_stride * 4 < (1LL << 31) && !(c.y2 && (c.M + 128) * (long long)c.y2_stride * 4 >= (1LL << 31));
+}
+int lfsr_rowgemm_b3_ln_launch(const LfsrLin& c, hipStream_t st) {
+  if (!lfsr_rowgemm_b3_ln_ok(c)) return LFSR_E_ARG;
   RowGemmB3Args p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wp = w_packed; p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff; p.M = M; p.N = N; p.slope = 1.0f;
-  p.ln_g = ln_g; p.ln_b = ln_b; p.ln_eps = ln_eps; p.ln_cols = ln_cols; p.pe = pe; p.pe_stride = pe_stride; p.pe_rows = pe_rows; p.pe_div = pe_div;
-  p.Y2 = y2; p.y2_stride = y2_stride; p.y2_choff = y2_choff; p.split_n = split_n;
+  p.X = c.x; p.x_stride = c.x_stride; p.x_choff = c.x_choff; p.Wp = c.w_packed; p.Y = c.y; p.y_stride = c.y_stride; p.y_choff = c.y_choff; p.M = c.M; p.N = c.N; p.slope = 1.0f;
+  p.ln_g = c.ln_g; p.ln_b = c.ln_b; p.ln_eps = c.ln_eps; p.ln_cols = c.ln_cols; p.pe = c.pe; p.pe_stride = c.pe_stride; p.pe_rows = c.pe_rows; p.pe_div = c.pe_div;
+  p.Y2 = c.y2; p.y2_stride = c.y2_stride; p.y2_choff = c.y2_choff; p.split_n = c.split_n;
   // 128-column panels by default here (the norm and the split are repeated per panel: EPIT 818 -> 831, LFT 1636 -> 1680 patches/s with them; LFSR_B3_NB=64: 64-column panels)
   const char* nsel = lfsr_sel("LFSR_B3_NB");
-  const bool wide = !(nsel && nsel[0] == '6') && ln_cols % 128 == 0 && (!y2 || split_n % 128 == 0);
-  switch (K) {
+  const bool wide = !(nsel && nsel[0] == '6') && c.ln_cols % 128 == 0 && (!c.y2 || c.split_n % 128 == 0);
+  switch (c.K) {
     case 64: return wide ? launch_b3<64, true, 128>(p, st) : launch_b3<64, true>(p, st);
     case 128: return wide ? launch_b3<128, true, 128>(p, st) : launch_b3<128, true>(p, st);
     default: return LFSR_E_ARG;

@@ -554,10 +554,11 @@ int lfsr_linear_fwd(const float* x, int x_stride, int x_choff, int cin, const fl
   p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff; p.R1 = res; p.r1_stride = res_stride; p.r1_choff = res_choff;
   p.M = (int)M; p.N = N; p.Npad = npad32(N); p.A = 1; p.AA = 1; p.H = 1; p.W = 1; p.ntaps = 1; p.CH = N; p.slope = slope;
   hipStream_t st = lfsr_stream(stream);
-  if (M >= 2048 && !lfsr_sel("LFSR_NO_ROWGEMM")) {
-    int rc = lfsr_rowgemm_launch(x, x_stride, x_choff, cin, w_packed, bias, res, res_stride, res_choff, y, y_stride, y_choff, M, N, slope, st);
-    if (rc != LFSR_E_ARG) return rc;
-  }
+  LfsrLin c{};
+  c.x = x; c.x_stride = x_stride; c.x_choff = x_choff; c.K = cin; c.w_packed = w_packed; c.bias = bias; c.res = res; c.res_stride = res_stride; c.res_choff = res_choff;
+  c.y = y; c.y_stride = y_stride; c.y_choff = y_choff; c.M = M; c.N = N; c.slope = slope;
+  const int rc = lfsr_linear_run(c, st);      // the row-streaming kernels for the shapes they cover
+  if (rc != LFSR_E_ARG) return rc;
   const bool two = (p.Npad % 64) == 0;
   switch (cin) {
     case 64: return two ? launch_gemm<IN_SAME, OUT_SAME, 64, 2>(p, st) : launch_gemm<IN_SAME, OUT_SAME, 64, 1>(p, st);
@@ -618,12 +619,10 @@ int lfsr_hr_tail_fwd(const float* hr, const float* w, const float* x_lr, float* 
 // patches/s), so it is the default there.  LFSR_LN_FUSE=0: every norm its own launch; 1: the attention norms as launches; 2: both fused.
 LfsrTransSel lfsr_trans_sel() {
   const char* lf = lfsr_sel("LFSR_LN_FUSE");
-  const char* rgs = lfsr_sel("LFSR_ROWGEMM");
   const char* psel = lfsr_sel("LFSR_FFN_PRESPLIT");
-  const bool rowgemm_f32 = (rgs && (rgs[0] == 'f' || rgs[0] == '1')) || lfsr_arith_f32();
   LfsrTransSel s;
   s.ln_fuse = !(lf && lf[0] == '0');
-  s.ln_fuse_qkv = lf ? lf[0] == '2' : !rowgemm_f32;
+  s.ln_fuse_qkv = lf ? lf[0] == '2' : !lfsr_gemm_sel().f32;
   s.ffn_fused = !lfsr_sel("LFSR_NO_FFN_FUSED");     // LFSR_NO_FFN_FUSED: the two-launch form (A/B runs)
   s.presplit = !(psel && psel[0] == '0');             // LFSR_FFN_PRESPLIT=0: the kernel splits the weight chunks itself (A/B runs)
   s.up_tail = !lfsr_sel("LFSR_NO_UPTAIL");
@@ -644,10 +643,13 @@ int lfsr_trans_head(const LfsrParamTable& P, const float* x, float* f0, float* c
 int lfsr_trans_qkv(const LfsrTransSel& sel, const LfsrParamTable& P, const std::string& pre, const float* x, int E, const float* pe, long long pe_rows,
                    long long pe_div, float* qk, float* v, float* tn, long long M, void* stream) {
   const float *W = P.w(pre + "attention.in_proj_weight"), *g = P.w(pre + "norm.weight"), *b = P.w(pre + "norm.bias");
-  const int rc = sel.ln_fuse_qkv ? lfsr_rowgemm_ln_launch(x, E, 0, E, W, g, b, 1e-5f, 2 * E, pe, pe ? E : 0, pe_rows, pe_div, qk, 2 * E, 0, v, E, 0, 2 * E,
-                                                          M, 3 * E, lfsr_stream(stream))
-                                 : LFSR_E_ARG;
-  if (rc != LFSR_E_ARG) return rc;
+  if (sel.ln_fuse_qkv) {
+    LfsrLin c{};
+    c.x = x; c.x_stride = E; c.K = E; c.w_packed = W; c.ln_g = g; c.ln_b = b; c.ln_eps = 1e-5f; c.ln_cols = 2 * E; c.pe = pe; c.pe_stride = pe ? E : 0;
+    c.pe_rows = (int)pe_rows; c.pe_div = (int)pe_div; c.y = qk; c.y_stride = 2 * E; c.y2 = v; c.y2_stride = E; c.split_n = 2 * E; c.M = M; c.N = 3 * E; c.slope = 1.0f;
+    const int rc = lfsr_linear_ln_run(c, lfsr_stream(stream));
+    if (rc != LFSR_E_ARG) return rc;
+  }
   LFSR_RC(lfsr_layernorm_fwd(x, E, 0, pe, pe ? E : 0, pe ? pe_rows : 0, pe_div, g, b, tn, E, 0, M, E, 1e-5f, stream));
   LFSR_RC(lfsr_linear_fwd(tn, E, 0, E, W, nullptr, nullptr, 0, 0, qk, 2 * E, 0, M, 2 * E, 1.0f, stream));      // q | k from the norm
   return lfsr_linear_fwd(x, E, 0, E, W + 2 * E * E, nullptr, nullptr, 0, 0, v, E, 0, M, E, 1.0f, stream);       // v from the raw rows
@@ -657,10 +659,13 @@ int lfsr_trans_ffn(const LfsrTransSel& sel, const LfsrParamTable& P, const std::
                    float* hid, long long M, void* stream) {
   const float *g = P.w(pre + "feed_forward.0.weight"), *b = P.w(pre + "feed_forward.0.bias");
   const float *W1 = P.w(pre + "feed_forward.1.weight"), *W4 = P.w(pre + "feed_forward.4.weight");
-  const int rc = (sel.ln_fuse && sel.ffn_fused) ? lfsr_ffn_ln_launch(x, E, 0, g, b, 1e-5f, W1, W4, x, E, 0, y, E, 0, M, E, 2 * E, E, 0.0f, lfsr_stream(stream),
-                                                                     sel.presplit ? P.packed + split_off : nullptr)
-                                                : LFSR_E_ARG;
-  if (rc != LFSR_E_ARG) return rc;
+  if (sel.ln_fuse && sel.ffn_fused) {
+    LfsrFfn f{};
+    f.x = x; f.x_stride = E; f.ln_g = g; f.ln_b = b; f.ln_eps = 1e-5f; f.w1_packed = W1; f.w2_packed = W4; f.wsplit = sel.presplit ? P.packed + split_off : nullptr;
+    f.res = x; f.res_stride = E; f.y = y; f.y_stride = E; f.M = M; f.K1 = E; f.H = 2 * E; f.N2 = E; f.slope = 0.0f;
+    const int rc = lfsr_ffn_run(f, lfsr_stream(stream));
+    if (rc != LFSR_E_ARG) return rc;
+  }
   LFSR_RC(lfsr_layernorm_fwd(x, E, 0, nullptr, 0, 0, 1, g, b, lnx, E, 0, M, E, 1e-5f, stream));
   if (sel.ffn_fused) return lfsr_ffn_fwd(lnx, E, 0, W1, W4, x, E, 0, y, E, 0, M, E, 2 * E, E, 0.0f, stream);
   LFSR_RC(lfsr_linear_fwd(lnx, E, 0, E, W1, nullptr, nullptr, 0, 0, hid, 2 * E, 0, M, 2 * E, 0.0f, stream));   // ReLU; the hidden rows go through HBM
