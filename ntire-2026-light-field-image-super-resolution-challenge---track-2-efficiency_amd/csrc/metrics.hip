@@ -11,34 +11,41 @@
 
 namespace {
 
-__device__ __forceinline__ int reflect_idx(int i, int n) {   // scipy.ndimage mode='reflect': d c b a | a b c d | d c b a
-  int p = 2 * n;
-  int r = i % p;
-  if (r < 0) r += p;
-  return r < n ? r : p - 1 - r;
+// One block per (b, u, v) view; views are H x W windows of (B,1,A*H,A*W) SAI mosaics.  The SSIM map is walked in tiles of
+// VM_TR x VM_TW output pixels, so the LDS need (5 planes of (VM_TR + 10) x VM_TW doubles = 60 KiB, static) does not depend on
+// the view size.  Only the map cropped by 5 pixels is averaged, and the 11-tap window of a cropped pixel lies inside the view:
+// no tap of a pixel that counts is reflected, and the horizontal pass needs no column halo (it filters exactly the tile's columns,
+// for the tile's rows +-5).  Every thread adds its pixels in tile order and the block sums the threads in a fixed tree: two calls
+// give the same bits.
+constexpr int VM_NT = 512;   // threads per block
+constexpr int VM_TW = 32;    // output columns per tile
+constexpr int VM_TR = 38;    // output rows per tile: (VM_TR + 10) * VM_TW = 3 * VM_NT items in the horizontal pass
+constexpr int VM_PLANE = (VM_TR + 10) * VM_TW;
+
+__device__ __forceinline__ double vm_block_sum(double v, double* red) {   // red: VM_NT doubles nobody else is using
+  const int tid = threadIdx.x;
+  __syncthreads();
+  red[tid] = v;
+  __syncthreads();
+  for (int s = VM_NT / 2; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
+  return red[0];
 }
 
-// one block per (b, u, v) view; views are H x W windows of (B,1,A*H,A*W) SAI mosaics
-__global__ __launch_bounds__(256) void k_view_metrics(const float* __restrict__ lab, const float* __restrict__ out, double* __restrict__ psnr, double* __restrict__ ssim,
-                                                     int A, int H, int W, int want_ssim, int TR) {
-  extern __shared__ double sm[];
-  __shared__ double red[256];
+__global__ __launch_bounds__(VM_NT) void k_view_metrics(const float* __restrict__ lab, const float* __restrict__ out, double* __restrict__ psnr,
+                                                       double* __restrict__ ssim, int A, int H, int W, int want_ssim) {
+  __shared__ double hx[5 * VM_PLANE];
   const int view = blockIdx.x % (A * A), b = blockIdx.x / (A * A), u = view / A, v = view % A;
   const long long Wm = (long long)A * W, base = ((long long)b * A * H + (long long)u * H) * Wm + (long long)v * W;
   const int tid = threadIdx.x;
   // ---- PSNR ----
   double se = 0.0;
-  for (int i = tid; i < H * W; i += 256) {
-    int y = i / W, x = i - y * W;
+  for (int y = tid / W, x = tid % W; y < H; x += VM_NT, y += x / W, x %= W) {   // pixels tid + n * VM_NT as (y, x): H * W may pass 2^31
     double d = (double)lab[base + y * Wm + x] - (double)out[base + y * Wm + x];
     se += d * d;
   }
-  red[tid] = se;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
-  if (tid == 0) { double mse = red[0] / ((double)H * W); psnr[blockIdx.x] = mse > 0.0 ? 10.0 * log10(1.0 / mse) : INFINITY; }
+  se = vm_block_sum(se, hx);
+  if (tid == 0) { double mse = se / ((double)H * W); psnr[blockIdx.x] = mse > 0.0 ? 10.0 * log10(1.0 / mse) : INFINITY; }
   if (!want_ssim) return;
-  __syncthreads();
   // ---- SSIM: separable 11-tap Gaussian of x, y, xx, yy, xy (horizontal pass into LDS, vertical pass on the fly) ----
   double g[11];
   {
@@ -46,42 +53,43 @@ __global__ __launch_bounds__(256) void k_view_metrics(const float* __restrict__ 
     for (int k = 0; k < 11; ++k) { double d = k - 5; g[k] = exp(-0.5 * d * d / (1.5 * 1.5)); sum += g[k]; }
     for (int k = 0; k < 11; ++k) g[k] /= sum;
   }
-  // row tiles of TR output rows: LDS holds the horizontally filtered planes of rows [y0-5, y0+TR+5) as [5][TR+10][W]
-  double* hx = sm;
   const double C1 = 0.01 * 0.01, C2 = 0.03 * 0.03, cov_norm = 121.0 / 120.0;
   const int ch = H - 10, cw = W - 10;
   double acc = 0.0;
-  const int RW = (TR + 10) * W;
-  for (int y0 = 5; y0 < H - 5; y0 += TR) {
-    const int rows_out = min(TR, H - 5 - y0);
-    __syncthreads();
-    for (int i = tid; i < (rows_out + 10) * W; i += 256) {
-      int ry = i / W, x = i - ry * W;
-      int y = reflect_idx(y0 - 5 + ry, H);
-      double ax = 0, ay = 0, axx = 0, ayy = 0, axy = 0;
-      for (int k = 0; k < 11; ++k) {
-        int xs = reflect_idx(x + k - 5, W);
-        double p = (double)lab[base + y * Wm + xs], q = (double)out[base + y * Wm + xs];
-        ax += g[k] * p; ay += g[k] * q; axx += g[k] * p * p; ayy += g[k] * q * q; axy += g[k] * p * q;
+  for (int y0 = 5; y0 < H - 5; y0 += VM_TR) {
+    const int rows_out = min(VM_TR, H - 5 - y0);
+    for (int x0 = 5; x0 < W - 5; x0 += VM_TW) {
+      const int cols_out = min(VM_TW, W - 5 - x0);
+      __syncthreads();
+      // rows [y0 - 5, y0 + rows_out + 5) and columns [x0 - 5, x0 + cols_out + 5) of the view: all inside it
+      for (int i = tid; i < (rows_out + 10) * cols_out; i += VM_NT) {
+        const int ry = i / cols_out, xl = i - ry * cols_out;
+        const float* pl = lab + base + (long long)(y0 - 5 + ry) * Wm + (x0 - 5 + xl);
+        const float* po = out + base + (long long)(y0 - 5 + ry) * Wm + (x0 - 5 + xl);
+        double ax = 0, ay = 0, axx = 0, ayy = 0, axy = 0;
+        for (int k = 0; k < 11; ++k) {
+          double p = (double)pl[k], q = (double)po[k];
+          ax += g[k] * p; ay += g[k] * q; axx += g[k] * p * p; ayy += g[k] * q * q; axy += g[k] * p * q;
+        }
+        const int o = ry * VM_TW + xl;
+        hx[o] = ax; hx[VM_PLANE + o] = ay; hx[2 * VM_PLANE + o] = axx; hx[3 * VM_PLANE + o] = ayy; hx[4 * VM_PLANE + o] = axy;
       }
-      hx[i] = ax; hx[RW + i] = ay; hx[2 * RW + i] = axx; hx[3 * RW + i] = ayy; hx[4 * RW + i] = axy;
-    }
-    __syncthreads();
-    for (int i = tid; i < rows_out * cw; i += 256) {
-      int ry = i / cw, x = 5 + i % cw;
-      double ux = 0, uy = 0, uxx = 0, uyy = 0, uxy = 0;
-      for (int k = 0; k < 11; ++k) {
-        int o = (ry + k) * W + x;
-        ux += g[k] * hx[o]; uy += g[k] * hx[RW + o]; uxx += g[k] * hx[2 * RW + o]; uyy += g[k] * hx[3 * RW + o]; uxy += g[k] * hx[4 * RW + o];
+      __syncthreads();
+      for (int i = tid; i < rows_out * cols_out; i += VM_NT) {
+        const int ry = i / cols_out, xl = i - ry * cols_out;
+        double ux = 0, uy = 0, uxx = 0, uyy = 0, uxy = 0;
+        for (int k = 0; k < 11; ++k) {
+          const int o = (ry + k) * VM_TW + xl;
+          ux += g[k] * hx[o]; uy += g[k] * hx[VM_PLANE + o]; uxx += g[k] * hx[2 * VM_PLANE + o]; uyy += g[k] * hx[3 * VM_PLANE + o];
+          uxy += g[k] * hx[4 * VM_PLANE + o];
+        }
+        double vx = cov_norm * (uxx - ux * ux), vy = cov_norm * (uyy - uy * uy), vxy = cov_norm * (uxy - ux * uy);
+        acc += ((2 * ux * uy + C1) * (2 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2));
       }
-      double vx = cov_norm * (uxx - ux * ux), vy = cov_norm * (uyy - uy * uy), vxy = cov_norm * (uxy - ux * uy);
-      acc += ((2 * ux * uy + C1) * (2 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2));
     }
   }
-  red[tid] = acc;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) { if (tid < s) red[tid] += red[tid + s]; __syncthreads(); }
-  if (tid == 0) ssim[blockIdx.x] = (ch > 0 && cw > 0) ? red[0] / ((double)ch * cw) : 0.0;
+  acc = vm_block_sum(acc, hx);
+  if (tid == 0) ssim[blockIdx.x] = acc / ((double)ch * cw);
 }
 
 __global__ __launch_bounds__(256) void k_mask_views(const float* __restrict__ x, float* __restrict__ y, const unsigned char* __restrict__ mask, float fill,
@@ -137,15 +145,9 @@ extern "C" {
 
 int lfsr_view_metrics(const float* label, const float* out, double* psnr, double* ssim, int B, int A, int H, int W, void* stream) {
   if (!label || !out || !psnr || B <= 0 || A <= 0 || H <= 0 || W <= 0) return LFSR_E_ARG;
-  int TR = 16;
-  while (ssim && TR > 1 && (size_t)5 * (TR + 10) * W * sizeof(double) > 150 * 1024) TR >>= 1;
-  size_t smem = ssim ? (size_t)5 * (TR + 10) * W * sizeof(double) : 0;
-  if (smem > 150 * 1024 || (ssim && (H < 11 || W < 11))) return LFSR_E_ARG;   // skimage needs win_size 11 <= view size
-  if (ssim && smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_view_metrics), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return LFSR_HIP_ERR(e);
-  }
-  hipLaunchKernelGGL(k_view_metrics, dim3((unsigned)(B * A * A)), dim3(256), smem, lfsr_stream(stream), label, out, psnr, ssim, A, H, W, ssim ? 1 : 0, TR);
+  if (ssim && (H < 11 || W < 11)) return LFSR_E_ARG;   // skimage needs win_size 11 <= view size
+  if ((long long)B * A * A > 0x7fffffffLL) return LFSR_E_ARG;
+  hipLaunchKernelGGL(k_view_metrics, dim3((unsigned)(B * A * A)), dim3(VM_NT), 0, lfsr_stream(stream), label, out, psnr, ssim, A, H, W, ssim ? 1 : 0);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }

@@ -7,13 +7,16 @@ from lfsr_amd import capi
 
 
 def view_metrics(label, out, angRes, want_ssim=True):
-    """label, out: (B,1,A*H,A*W) SAI mosaics on the device -> (psnr, ssim) tensors of shape (B, A, A), float64."""
+    """label, out: (B,1,A*H,A*W) SAI mosaics -> (psnr, ssim) tensors of shape (B, A, A), float64, on out's device.
+    out is on the device; label may be on the host, as the loader leaves Hr_SAI_y at train.py:296,322, and is copied to out's device."""
     lib = capi.load()
     B, c1, Hh, Ww = label.shape
     if c1 != 1 or out.shape != label.shape:
         raise capi.LfsrError(f"cal_metrics expects two (B,1,A*H,A*W) tensors, got {tuple(label.shape)} {tuple(out.shape)}")
+    if not out.is_cuda:
+        raise capi.LfsrError("cal_metrics needs the output on the device (there is no CPU fallback for the HIP path)")
     H, W = Hh // angRes, Ww // angRes
-    label = label.detach().float().contiguous()
+    label = label.detach().to(out.device).float().contiguous()
     out = out.detach().float().contiguous()
     psnr = torch.empty(B * angRes * angRes, dtype=torch.float64, device=label.device)
     ssim = torch.empty_like(psnr) if want_ssim else None

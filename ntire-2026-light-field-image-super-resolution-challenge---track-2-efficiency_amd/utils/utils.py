@@ -44,13 +44,14 @@ def rgb2ycbcr(x):
 
 def ycbcr2rgb_views(Sr_SAI_y, Sr_SAI_cbcr, angRes):
     """device form of  (ycbcr2rgb(cat(y, cbcr)).clip(0, 1) * 255).astype('uint8')  + the split into views:
-    Sr_SAI_y (1, 1, A h, A w) / (A h, A w), Sr_SAI_cbcr (1, 2, A h, A w) / (2, A h, A w) fp32 device tensors -> (A, A, h, w, 3) uint8"""
+    Sr_SAI_y (1, 1, A h, A w) / (A h, A w) on the device, Sr_SAI_cbcr (1, 2, A h, A w) / (2, A h, A w) on the device or on the host, where the
+    loader leaves it (train.py:297,332): it is copied to Sr_SAI_y's device.  fp32 -> (A, A, h, w, 3) uint8 on the device"""
     import ctypes as C
     import torch
+    if not Sr_SAI_y.is_cuda:
+        raise capi.LfsrError("ycbcr2rgb_views needs Sr_SAI_y on the device (there is no CPU fallback for the HIP path)")
     y = Sr_SAI_y.reshape(Sr_SAI_y.shape[-2], Sr_SAI_y.shape[-1]).contiguous().float()
-    cc = Sr_SAI_cbcr.reshape(2, y.shape[0], y.shape[1]).contiguous().float()
-    if not y.is_cuda:
-        raise capi.LfsrError("ycbcr2rgb_views needs device tensors (there is no CPU fallback for the HIP path)")
+    cc = Sr_SAI_cbcr.to(y.device).reshape(2, y.shape[0], y.shape[1]).contiguous().float()
     A = int(angRes)
     h, w = y.shape[0] // A, y.shape[1] // A
     out = torch.empty(A, A, h, w, 3, dtype=torch.uint8, device=y.device)

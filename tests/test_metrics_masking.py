@@ -44,6 +44,130 @@ def test_device_metrics_vs_oracle():
         view_metrics(torch.zeros(1, 1, 10, 10, device="cuda"), torch.zeros(1, 1, 10, 10, device="cuda"), 2)   # 5x5 views < 11x11 window
 
 
+def _vm_tile():
+    """(VM_TR, VM_TW): the output rows and columns of one SSIM tile of k_view_metrics, read from the kernel's source so that the rows
+    below which straddle a tile edge move with it"""
+    import os
+    import re
+    from lfsr_amd import PKG_DIR
+    src = open(os.path.join(PKG_DIR, "csrc", "metrics.hip")).read()
+    return tuple(int(re.search(r"constexpr int %s = (\d+);" % n, src).group(1)) for n in ("VM_TR", "VM_TW"))
+
+
+VM_TR, VM_TW = _vm_tile()
+# (B, A, H, W) of the views.  The SSIM map of an H x W view is (H - 10) x (W - 10); the kernel walks it in VM_TR x VM_TW tiles.
+METRIC_SHAPES = {
+    "TR8_ragged_rows": (1, 2, 27, 160),       # the row tiles the W-dependent LDS layout took up to width 349: 8 rows, the last tile ragged
+    "TR4": (1, 1, 23, 214),
+    "TR2": (1, 1, 13, 300),
+    "TR1_w349": (1, 1, 12, 349),              # the last width that layout accepted
+    "w350_two_rows": (1, 1, 12, 350),         # the first it refused; two output rows
+    "w625_one_row_B2": (2, 2, 11, 625),       # the widest baseline view; one output row; B > 1
+    "one_column": (1, 1, 434, 11),            # tall and narrow: one output column
+    "real_view": (1, 1, 432, 624),            # one view of real size
+    # one tile: a row and a column short of it, exactly it, one over
+    "tile_minus1": (1, 1, 10 + VM_TR - 1, 10 + VM_TW - 1),
+    "tile_exact": (1, 1, 10 + VM_TR, 10 + VM_TW),
+    "tile_plus1": (1, 1, 10 + VM_TR + 1, 10 + VM_TW + 1),
+    # two tiles each way, and the two edges against each other (rows over / columns short and the reverse)
+    "two_tiles_minus1": (1, 2, 10 + 2 * VM_TR - 1, 10 + 2 * VM_TW - 1),
+    "two_tiles_exact": (1, 1, 10 + 2 * VM_TR, 10 + 2 * VM_TW),
+    "two_tiles_plus1": (1, 1, 10 + 2 * VM_TR + 1, 10 + 2 * VM_TW + 1),
+    "rows_plus1_cols_minus1": (1, 1, 10 + VM_TR + 1, 10 + VM_TW - 1),
+    "rows_minus1_cols_plus1": (1, 1, 10 + VM_TR - 1, 10 + VM_TW + 1),
+}
+_METRIC_CASES = {}
+
+
+def _metric_case(name):
+    """(label, out, per-view PSNR, per-view SSIM) of METRIC_SHAPES[name]: fp32 mosaics and the oracle's fp64 values, computed once"""
+    if name not in _METRIC_CASES:
+        B, A, H, W = METRIC_SHAPES[name]
+        rng = np.random.default_rng(sorted(METRIC_SHAPES).index(name) + 20)
+        lab = rng.random((B, 1, A * H, A * W)).astype(np.float32)
+        out = np.clip(lab + 0.05 * rng.standard_normal(lab.shape).astype(np.float32), 0, 1)
+        _METRIC_CASES[name] = (lab, out) + O.view_psnr_ssim(lab, out, A)
+    return _METRIC_CASES[name]
+
+
+def _mean_pos(v):
+    """cal_metrics' mean (utils/utils.py:126-131): the sum over all views divided by the number of views whose value is > 0"""
+    n = int((v > 0).sum())
+    return float(v.sum() / n) if n > 0 else 0.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(METRIC_SHAPES))
+def test_device_metrics_any_view_size(name):
+    """lfsr_view_metrics at every row tile of the former layout, past its width limit, and on both sides of every tile edge of the present one:
+    per-view values against the oracle under the gates of test_device_metrics_vs_oracle, cal_metrics against the reference's means, nothing
+    written outside the B*A*A doubles, two calls bit-equal, a host label (train.py:296,322) equal to a device label, and the PSNR-only form"""
+    from lfsr_amd import capi
+    from lfsr_amd.utils.metrics import cal_metrics, view_metrics
+    B, A, H, W = METRIC_SHAPES[name]
+    lab, out, rps, rss = _metric_case(name)
+    lab_h, lab_d, out_d = torch.from_numpy(lab), torch.from_numpy(lab).cuda(), torch.from_numpy(out).cuda()
+    ps, ss = view_metrics(lab_d, out_d, A)
+    dps, dss = np.abs(ps.cpu().numpy() - rps).max(), np.abs(ss.cpu().numpy() - rss).max()
+    print(f"{name} {METRIC_SHAPES[name]}: max |dPSNR| {dps:.2e}, max |dSSIM| {dss:.2e}")
+    assert ps.shape == (B, A, A) and ss.shape == (B, A, A) and ps.dtype == torch.float64
+    assert dps < 1e-9
+    assert dss < 1e-10
+    pm, sm = cal_metrics(Namespace(angRes_in=A, task="SR"), lab_d, out_d)
+    assert abs(pm - _mean_pos(rps)) < 1e-9 and abs(sm - _mean_pos(rss)) < 1e-10
+    # sentinel-filled buffers with a guard band either side, through the C ABI
+    n, G, fill = B * A * A, 64, -12345.5
+    pbuf, sbuf = (torch.full((G + n + G,), fill, dtype=torch.float64, device="cuda") for _ in range(2))
+    capi.check(capi.load().lfsr_view_metrics(capi.dev_ptr(lab_d), capi.dev_ptr(out_d), capi.dev_ptr(pbuf[G:G + n]), capi.dev_ptr(sbuf[G:G + n]),
+                                             B, A, H, W, capi.stream_ptr()), "view_metrics")
+    for buf, want in ((pbuf, ps), (sbuf, ss)):
+        assert torch.equal(buf[G:G + n], want.reshape(-1))                 # a second call: the same bits
+        assert bool((buf[:G] == fill).all()) and bool((buf[G + n:] == fill).all())
+    ps_h, ss_h = view_metrics(lab_h, out_d, A)                             # host label, moved to out's device
+    assert ps_h.is_cuda and torch.equal(ps_h, ps) and torch.equal(ss_h, ss)
+    assert cal_metrics(Namespace(angRes_in=A, task="SR"), lab_h, out_d) == (pm, sm)
+    ps_only, none = view_metrics(lab_d, out_d, A, want_ssim=False)         # ssim == nullptr
+    assert none is None and torch.equal(ps_only, ps)
+
+
+@pytest.mark.gpu
+def test_device_identity_host_inputs_and_refusals():
+    from lfsr_amd import capi
+    from lfsr_amd.utils.metrics import cal_metrics, view_metrics
+    lab, out, _, _ = _metric_case("w350_two_rows")
+    x = torch.from_numpy(out).cuda()
+    ps, ss = view_metrics(x, x.clone(), 1)                                 # identical label and output at a wide shape
+    assert bool(torch.isinf(ps).all()) and bool((ps > 0).all()) and float((ss - 1.0).abs().max()) < 1e-10      # the SSIM gate: 1 up to round-off
+    # no CPU fallback: a host output raises whatever the label is, and nothing is computed on the host
+    for label in (torch.from_numpy(lab), torch.from_numpy(lab).cuda()):
+        with pytest.raises(capi.LfsrError):
+            view_metrics(label, torch.from_numpy(out), 1)
+        with pytest.raises(capi.LfsrError):
+            cal_metrics(Namespace(angRes_in=1, task="SR"), label, torch.from_numpy(out))
+    from lfsr_amd.utils.utils import ycbcr2rgb_views
+    y, cc = torch.from_numpy(out[0, 0]), torch.from_numpy(np.stack([lab[0, 0], out[0, 0]]))
+    want = ycbcr2rgb_views(y.cuda(), cc.cuda(), 1)
+    assert want.is_cuda and torch.equal(ycbcr2rgb_views(y.cuda(), cc, 1), want)       # host Sr_SAI_cbcr (train.py:297,332): moved to y's device
+    for c in (cc, cc.cuda()):
+        with pytest.raises(capi.LfsrError):
+            ycbcr2rgb_views(y, c, 1)                                                  # host Sr_SAI_y: no CPU fallback
+    # views below the 11 x 11 window: SSIM is refused before anything is written, on either side; the PSNR-only form takes them as before
+    rng = np.random.default_rng(40)
+    for (A, H, W) in [(2, 10, 350), (2, 350, 10), (2, 5, 5)]:
+        a = rng.random((1, 1, A * H, A * W)).astype(np.float32)
+        b = np.clip(a + 0.05 * rng.standard_normal(a.shape).astype(np.float32), 0, 1)
+        ad, bd = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+        n, fill = A * A, -12345.5
+        pbuf, sbuf = (torch.full((n,), fill, dtype=torch.float64, device="cuda") for _ in range(2))
+        rc = capi.load().lfsr_view_metrics(capi.dev_ptr(ad), capi.dev_ptr(bd), capi.dev_ptr(pbuf), capi.dev_ptr(sbuf), 1, A, H, W, capi.stream_ptr())
+        torch.cuda.synchronize()
+        assert rc == -1 and bool((pbuf == fill).all()) and bool((sbuf == fill).all())
+        ps_only, _ = view_metrics(ad, bd, A, want_ssim=False)
+        d = (a.astype(np.float64) - b.astype(np.float64)) ** 2
+        ref = 10 * np.log10(1.0 / d.reshape(A, H, A, W).mean(axis=(1, 3)))
+        assert np.abs(ps_only.cpu().numpy()[0] - ref).max() < 1e-9
+
+
 def _aux():
     import json
     import os
