@@ -2,7 +2,7 @@
  * lfsr_hip.h -- C ABI of liblfsr_hip.so: the MI355X (gfx950) light-field SR hot path.
  *
  * Drop-in boundary for the reference's arithmetic layer (stock PyTorch ops called from
- * model/SR/{DistgSSR,EPIT,LFT,LF_InterNet}.py and utils/utils.py of the BasicLFSR fork).  Every entry
+ * model/SR/{DistgSSR,EPIT,LFT,LF_InterNet,LFSSR}.py and utils/utils.py of the BasicLFSR fork).  Every entry
  * point cites the reference interface it replaces (file:line relative to the reference root).
  *
  * Conventions
@@ -453,6 +453,52 @@ int lfsr_internet_train_saved(const lfsr_internet* ctx, int B, int h, int w, int
 /* dout (B,1,A*h*s,A*w*s) = dLoss/dOut; grads: n_grads == lfsr_internet_num_params(ctx) floats, overwritten */
 int lfsr_internet_backward(lfsr_internet* ctx, const float* x, const float* dout, int B, int h, int w,
                            void* workspace, size_t workspace_bytes, float* grads, size_t n_grads, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * LFSSR (model/SR/LFSSR.py, the spatial-angular separable network): INFERENCE only -- there is no backward and there are no num_params / param_offset / *_train
+ * symbols.  Scale 2 (net2x) and 4 (net4x), angRes 2..9, any view size.  All its convs have biases; the activation is ReLU.
+ * The four kernels below have one arithmetic each and read none of the four arithmetic switches further down; the per-view 64 -> 64 3x3 convs of the model (the
+ * spatial half of every AltFilter, the four sub-pixel convs of lfsr_conv3x3_ps2_fwd) run through the 3x3 dispatcher and so follow lfsr_set_arithmetic, a mode that
+ * is NOT tested for LFSSR.
+ * ---------------------------------------------------------------------------------------------- */
+/* The angular half of an AltFilter (LFSSR.py:201,208-215): at every pixel, a 3x3 conv 64 -> 64 with zero padding over the A x A grid of views, on VCL rows
+ * p = ((b A + u) A + v) npix + q (npix = h w):
+ *   y[b,u,v,q,o] = relu(bias[o] + sum over du, dv in {-1,0,1} with 0 <= u+du < A and 0 <= v+dv < A, and over c, of
+ *                       W[o,c,du+1,dv+1] * pre(x[b,u+du,v+dv,q,c])),      pre(t) = in_bias ? max(t + in_bias[c], 0) : t
+ * (in_bias, may be NULL: the bias and ReLU of the conv in front, applied while the operand is staged; a view outside the grid contributes zero AFTER that prologue
+ * and is never loaded).  w_packed: lfsr_pack_conv_weight(O = 64, C = 64, taps = 9, perm = 0), of which the direct [9][64][64] part is read.  fp32 MFMA, exact
+ * products; no atomics: two runs give the same bits and a sample's result does not depend on B.  LFSR_E_ARG before any launch: A outside 2..9, strides or offsets
+ * that are no multiples of 4 or a stride below its offset + 64, x / y / w_packed / in_bias off the 16-byte grid, an operand span (B A^2 npix stride floats) of
+ * 2 GiB or more. */
+int lfsr_angconv3x3_fwd(const float* x, int x_stride, int x_choff, const float* w_packed, const float* bias, const float* in_bias,
+                        float* y, int y_stride, int y_choff, int B, int A, int npix, void* stream);
+/* conv0 (LFSSR.py:59,92): x (B,1,A*h,A*w) SAI mosaic NCHW, w (64,1,3,3) and bias (64) raw -> y VCL 64 channels = relu(per-view 3x3 conv, zero pad 1, + bias).
+ * y_stride, y_choff multiples of 4. */
+int lfsr_lfssr_conv0_fwd(const float* x, const float* w, const float* bias, float* y, int y_stride, int y_choff, int B, int A, int h, int wd, void* stream);
+/* fup (LFSSR.py:62-66): per-view 3x3 conv 64 -> 256 + bias, PixelShuffle(2), ReLU, into VCL rows of the n_img views of (2h, 2w): y[(img, 2y+i, 2x+j), c] =
+ * relu(conv(x)[img, 4c + 2i + j, y, x] + bias[4c + 2i + j]).  w_packed4: four consecutive lfsr_pack_conv_weight(64, 64, 9) packs, pack 2i + j made from rows
+ * 4c + 2i + j (c = 0..63) of the (256,64,3,3) weight; bias (256) raw; tmp: n_img*h*w*256 floats of scratch (the four conv results side by side).  x, y, tmp
+ * 16-byte aligned, strides and offsets multiples of 4; every tensor below 2 GiB. */
+int lfsr_conv3x3_ps2_fwd(const float* x, int x_stride, int x_choff, const float* w_packed4, const float* bias, float* tmp, float* y, int y_stride, int y_choff,
+                         int n_img, int h, int w, void* stream);
+/* res + iup (LFSSR.py:67-71,95-98): out = conv3x3_{64->1}(f) + b_res + PixelShuffle2(conv3x3_{1->4}(lo) + b_iup), per view, zero pad 1.  f: VCL rows of the
+ * B*A*A views of (2h, 2w); lo: per-view planes (B*A*A, h, w); w_res (1,64,3,3), b_res (1), w_iup (4,1,3,3), b_iup (4) raw.  mosaic = 0: out as per-view planes
+ * (B*A*A, 2h, 2w); 1: out as the SAI mosaic (B,1,A*2h,A*2w). */
+int lfsr_lfssr_tail_fwd(const float* f, int f_stride, int f_choff, const float* w_res, const float* b_res, const float* lo, const float* w_iup, const float* b_iup,
+                        float* out, int B, int A, int h, int w, int mosaic, void* stream);
+/* Whole-model driver: LFSSR forward (get_model.forward, LFSSR.py:30-46).  The life cycle and error codes of lfsr_internet_*; state_dict keys net.conv0.*,
+ * net.altblock{1,2}.{i}.{spaconv,angconv}.*, net.fup{1,2}.0.*, net.res{1,2}.*, net.iup{1,2}.0.* (48 tensors at scale 2 and 94 at scale 4 with n_layer = 10, the
+ * reference's depth; any n_layer >= 1 is accepted).  create: LFSR_E_ARG for a scale other than 2 and 4 or A outside 2..9.  forward: LFSR_E_ARG, nothing written,
+ * when a tensor of the forward (the widest: 256 floats per LR pixel at scale 2, 1024 at scale 4) would reach 2 GiB. */
+typedef struct lfsr_lfssr lfsr_lfssr;
+int lfsr_lfssr_create(lfsr_lfssr** ctx, int A, int scale, int n_layer);
+void lfsr_lfssr_destroy(lfsr_lfssr* ctx);
+size_t lfsr_lfssr_packed_bytes(const lfsr_lfssr* ctx);
+int lfsr_lfssr_set_packed(lfsr_lfssr* ctx, void* packed, size_t bytes);
+int lfsr_lfssr_load_param(lfsr_lfssr* ctx, const char* key, const float* data, size_t numel, void* stream);
+int lfsr_lfssr_finalize(lfsr_lfssr* ctx, void* stream);
+size_t lfsr_lfssr_workspace_bytes(const lfsr_lfssr* ctx, int B, int h, int w);
+int lfsr_lfssr_forward(lfsr_lfssr* ctx, const float* x, float* out, int B, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- backward of the disentangling branches as operators (disentg_branches_bwd; reference layers DistgSSR.py:84-97,108, differentiated by
  * autograd in train.py:256-264).  Raw PyTorch-layout weights in (the entry points pack what their kernels read into the workspace), raw-layout weight

@@ -46,6 +46,10 @@ SIGNATURES = {
     "lfsr_distgssr_forward_taps": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_sz, C.POINTER(c_p), c_p]),
     "lfsr_layernorm_fwd": (c_i, [c_p, c_i, c_i, c_p, c_i, C.c_longlong, C.c_longlong, c_p, c_p, c_p, c_i, c_i, C.c_longlong, c_i, c_f, c_p]),
     "lfsr_conv3x3_n_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "lfsr_angconv3x3_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "lfsr_lfssr_conv0_fwd": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "lfsr_conv3x3_ps2_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
+    "lfsr_lfssr_tail_fwd": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_lft_position_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_view_metrics": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_mask_views": (c_i, [c_p, c_p, c_p, c_f, c_i, c_i, c_i, c_i, c_i, c_p]),
@@ -125,7 +129,7 @@ def _model_signatures(name, n_create_ints, trainable):
 
 
 # (model, ints lfsr_<model>_create takes after A and scale, trainable)
-_MODELS = (("distgssr", 3, True), ("internet", 2, True), ("lft", 2, True), ("epit", 2, True))
+_MODELS = (("distgssr", 3, True), ("internet", 2, True), ("lft", 2, True), ("epit", 2, True), ("lfssr", 1, False))
 for _m in _MODELS:
     SIGNATURES.update(_model_signatures(*_m))
 
@@ -575,6 +579,15 @@ class ModelRuntime:
         return ws[off.value:off.value + n.value]
 
 
+class LFSSRRuntime(ModelRuntime):
+    """lfsr_lfssr: inference only (the C ABI has no training symbols for it).  Its widest tensor is the 256-wide result of the last up-sampling conv: 256 floats
+    per LR pixel at scale 2, and 4 x 256 = 16 x 64 at scale 4, where fup2 runs on the (2h, 2w) views and writes 64 channels at (4h, 4w)."""
+
+    def __init__(self, A, scale, n_layer=10):
+        super().__init__("lfssr", A, scale, n_layer)
+        self.widest_row_floats = 1024 if scale == 4 else 256
+
+
 class DistgSSRRuntime(ModelRuntime):
     """lfsr_distgssr: the batched weight load, the tapped forward and the per-class profile on top of the shared life cycle."""
 
@@ -715,6 +728,58 @@ def upsample_head(f, w0, b0, w2, x_lr, A, s):
     out = torch.empty((B, 1, Hh * s, Ww * s), dtype=torch.float32, device=f.device)
     check(lib.lfsr_upsample_head_fwd(dev_ptr(f), f.shape[1], 0, dev_ptr(wf), dev_ptr(bf), dev_ptr(x_lr), dev_ptr(out), B, A, h, w, s, stream_ptr()),
           "upsample_head_fwd")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# LFSSR's operators (inference only)
+# ---------------------------------------------------------------------------------------------------
+
+def angconv3x3(x, w_packed, bias, B, A, npix, in_bias=None, out=None, x_choff=0, out_choff=0):
+    """lfsr_angconv3x3_fwd: relu(3x3 conv over the A x A grid of views + bias) at every pixel of VCL rows; in_bias: the bias of a conv + ReLU in front, applied as
+    the operand is staged.  w_packed: pack_conv_weight of the (64,64,3,3) weight."""
+    lib = load()
+    if out is None:
+        out = torch.empty((B * A * A * npix, 64), dtype=torch.float32, device=x.device)
+    check(lib.lfsr_angconv3x3_fwd(dev_ptr(x), x.shape[1], x_choff, dev_ptr(w_packed), dev_ptr(bias), _opt(in_bias), dev_ptr(out), out.shape[1], out_choff,
+                                  B, A, npix, stream_ptr()), "angconv3x3_fwd")
+    return out
+
+
+def lfssr_conv0(x, w, bias, A, out=None, out_choff=0):
+    """lfsr_lfssr_conv0_fwd: SAI mosaic (B,1,A*h,A*w) -> VCL 64 channels, relu(per-view 3x3 conv + bias); w (64,1,3,3), bias (64) raw"""
+    lib = load()
+    B, _, Hh, Ww = x.shape
+    h, wd = Hh // A, Ww // A
+    if out is None:
+        out = torch.empty((B * A * A * h * wd, 64), dtype=torch.float32, device=x.device)
+    check(lib.lfsr_lfssr_conv0_fwd(dev_ptr(x), dev_ptr(w), dev_ptr(bias), dev_ptr(out), out.shape[1], out_choff, B, A, h, wd, stream_ptr()), "lfssr_conv0_fwd")
+    return out
+
+
+def pack_ps2_weight(w):
+    """(256,64,3,3) -> the four consecutive 64 -> 64 packs lfsr_conv3x3_ps2_fwd reads: pack 2i + j from rows 4c + 2i + j"""
+    return torch.cat([pack_conv_weight(w[ij::4].contiguous()) for ij in range(4)])
+
+
+def conv3x3_ps2(x, w_packed4, bias, n_img, h, w, out=None, out_choff=0, x_choff=0):
+    """lfsr_conv3x3_ps2_fwd: per-view 3x3 conv 64 -> 256 + bias, PixelShuffle(2), ReLU -> VCL rows of the (2h, 2w) views"""
+    lib = load()
+    if out is None:
+        out = torch.empty((n_img * h * w * 4, 64), dtype=torch.float32, device=x.device)
+    tmp = torch.empty((n_img * h * w, 256), dtype=torch.float32, device=x.device)
+    check(lib.lfsr_conv3x3_ps2_fwd(dev_ptr(x), x.shape[1], x_choff, dev_ptr(w_packed4), dev_ptr(bias), dev_ptr(tmp), dev_ptr(out), out.shape[1], out_choff,
+                                   n_img, h, w, stream_ptr()), "conv3x3_ps2_fwd")
+    return out
+
+
+def lfssr_tail(f, w_res, b_res, lo, w_iup, b_iup, B, A, h, w, mosaic, f_choff=0):
+    """lfsr_lfssr_tail_fwd: conv3x3_{64->1}(f) + b_res + PixelShuffle2(conv3x3_{1->4}(lo) + b_iup); f VCL rows of the (2h, 2w) views, lo (B*A*A, h, w) planes
+    -> (B*A*A, 2h, 2w) planes, or with mosaic the SAI mosaic (B,1,A*2h,A*2w)"""
+    lib = load()
+    out = torch.empty((B, 1, A * 2 * h, A * 2 * w) if mosaic else (B * A * A, 2 * h, 2 * w), dtype=torch.float32, device=f.device)
+    check(lib.lfsr_lfssr_tail_fwd(dev_ptr(f), f.shape[1], f_choff, dev_ptr(w_res), dev_ptr(b_res), dev_ptr(lo), dev_ptr(w_iup), dev_ptr(b_iup), dev_ptr(out),
+                                  B, A, h, w, int(bool(mosaic)), stream_ptr()), "lfssr_tail_fwd")
     return out
 
 

@@ -1,4 +1,4 @@
-// The model-context core of the four C model drivers (DistgSSR, EPIT, LFT, LF_InterNet): the packed-parameter table keyed by the reference's
+// The model-context core of the five C model drivers (DistgSSR, EPIT, LFT, LF_InterNet, LFSSR): the packed-parameter table keyed by the reference's
 // state_dict names, and the base every context derives from, with the life-cycle steps the drivers share.
 #pragma once
 #include <map>

@@ -1,4 +1,4 @@
-"""What the four model plugins (model/SR/*.py) share: the module tree of a plugin is a parameter container only, and
+"""What the model plugins (model/SR/*.py) share: the module tree of a plugin is a parameter container only, and
 ``forward`` hands the tensors to the gfx950 HIP library through the C ABI (lfsr_amd.capi); none of the
 ``nn.Module.forward`` paths of the containers is ever executed and there is no CPU fallback.
 
@@ -58,6 +58,7 @@ class HipModel(nn.Module):
     A subclass builds its module tree after ``super().__init__()`` and implements ``_new_runtime``."""
 
     hip_name = None           # the model's name in error texts
+    trainable = True          # False: the C ABI has no training symbols for the model, a forward with grad enabled is refused
 
     def __init__(self):
         super().__init__()
@@ -99,5 +100,8 @@ class HipModel(nn.Module):
         if not x.is_cuda:
             raise capi.LfsrError(f"{self.hip_name}: input must live on the MI355X (no CPU fallback in the HIP path)")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if not self.trainable:
+                raise capi.LfsrError(f"{self.hip_name} is inference-only on the HIP path (no backward behind the C ABI): run the forward under "
+                                     "torch.no_grad(), or freeze the parameters")
             return _HipModelFunction.apply(self, x.float(), *self.parameters())      # train.py:257
         return self._runtime(x.device).forward(x.float())

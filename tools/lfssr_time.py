@@ -1,0 +1,70 @@
+#!/usr/bin/env python3
+"""Times lfsr_angconv3x3_fwd beside lfsr_conv3x3_fwd (the per-view 3x3 conv: the same dense FLOP count on the same tensors) at angRes 5, B = 8, views of 32x32 and
+64x64, interleaved in this process (`rounds` timings of `reps` launches each, a warm-up before every timing, random operands), then the whole LFSSR x4 forward at
+B = 8 on 32x32 views.  Device events around launches that end in a synchronise.
+usage: python tools/lfssr_time.py [reps] [rounds] [steps]"""
+import os, sys, time
+import torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from lfsr_amd import capi
+from lfsr_amd.synth import synth_input
+from tests.lfssr_helpers import lfssr_spec, lfssr_state_dict
+capi.load()
+reps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
+rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 7
+steps = int(sys.argv[3]) if len(sys.argv) > 3 else 10
+A, B = 5, 8
+EXECUTED = sum((3 - (u in (0, A - 1))) * (3 - (v in (0, A - 1))) for u in range(A) for v in range(A)) / (9.0 * A * A)    # 169 / 225
+
+
+def timed(fn):
+    for _ in range(5): fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize(); e0.record()
+    for _ in range(reps): fn()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / reps
+
+
+g = torch.Generator(device="cuda").manual_seed(3)
+for hw in (32, 64):
+    npix, n_img = hw * hw, B * A * A
+    M = n_img * npix
+    x, y = torch.randn(M, 64, device="cuda", generator=g), torch.empty(M, 64, device="cuda")
+    wp = capi.pack_conv_weight(torch.randn(64, 64, 3, 3, device="cuda", generator=g) * 0.05)
+    bias, in_bias = torch.randn(64, device="cuda", generator=g) * 0.1, torch.rand(64, device="cuda", generator=g)
+    ops = (("angconv3x3", lambda: capi.angconv3x3(x, wp, bias, B, A, npix, in_bias=in_bias, out=y)),
+           ("conv3x3", lambda: capi.conv3x3(x, wp, n_img, hw, hw, slope=1.0, out=y)))
+    t = {name: [] for name, _ in ops}
+    for _ in range(rounds):
+        for name, fn in ops: t[name].append(timed(fn))
+    dense = 2.0 * 576 * 64 * M
+    for name, _ in ops:
+        v = sorted(t[name])
+        med = v[len(v) // 2]
+        work = dense * (EXECUTED if name == "angconv3x3" else 1.0)
+        print(f"{name:10s} A={A} B={B} {hw}x{hw}: median {med:8.1f} us  min {v[0]:8.1f}  max {v[-1]:8.1f}  dense {dense / med * 1e-6:6.1f} TFLOP/s"
+              f"  executed multiply-adds {work / med * 1e-6:6.1f} TFLOP/s  ({rounds} x {reps} launches)", flush=True)
+    a, c = sorted(t["angconv3x3"]), sorted(t["conv3x3"])
+    print(f"angconv3x3 / conv3x3 at {hw}x{hw}: {a[len(a) // 2] / c[len(c) // 2]:.3f}", flush=True)
+    del x, y
+
+if steps == 0: sys.exit(0)     # the operators only
+sd = lfssr_state_dict(lfssr_spec(4))
+rt = capi.LFSSRRuntime(A, 4)
+rt.load_state([(k, torch.from_numpy(v).cuda()) for k, v in sd.items()], torch.device("cuda", 0))
+xin = torch.from_numpy(synth_input((B, 1, A * 32, A * 32), seed=1)).cuda()
+for _ in range(3): rt.forward(xin)
+torch.cuda.synchronize()
+rates = []
+for _ in range(3):
+    t0 = time.perf_counter()
+    for _ in range(steps): rt.forward(xin)
+    torch.cuda.synchronize()
+    rates.append(B * steps / (time.perf_counter() - t0))
+capi.op_profile(True)
+rt.forward(xin)
+prof = capi.op_profile_read()
+capi.op_profile(False)
+print(f"LFSSR x4 forward, A=5, 32x32, B={B}: {sorted(rates)[1]:.1f} patches/s (median of 3 x {steps} forwards; min {min(rates):.1f}, max {max(rates):.1f})", flush=True)
+for k, (ms, n) in sorted(prof.items(), key=lambda kv: -kv[1][0]): print(f"  op {k[0]:12s} ({k[1]}, {k[2]}): {ms:8.3f} ms over {n} launches (one forward, event-bracketed)")
