@@ -595,6 +595,21 @@ int lfsr_get_gemm_arithmetic(void);
 int lfsr_set_branch_arithmetic(int mode);   /* LFSR_E_ARG for any other value, nothing changed */
 int lfsr_get_branch_arithmetic(void);
 
+/* ---- arithmetic of LFSSR's angular conv: a fifth process-wide selection, independent of the four above, read at every launch ----
+ * LFSR_ANG_ARITH_DEFAULT: every kernel as it is, bit for bit.
+ * LFSR_ANG_ARITH_BF16: opt-in.  lfsr_angconv3x3_fwd rounds its operands to bf16 (nearest even) once: the activations after the optional in_bias + ReLU prologue
+ * (which stays one fp32 add and one max), and the weight from its fp32 pack while a wave loads it, so the pack, lfsr_lfssr_packed_bytes and the workspace do not
+ * change.  The products are exact; accumulation, bias, ReLU and stores are fp32; x and y stay fp32 in memory; off-grid taps are skipped as under the default.  The
+ * geometries, argument checks and return codes are the default's (angRes 2..9, any npix, strides and channel offsets).  What follows: lfsr_angconv3x3_fwd and,
+ * through it, the angular convs of lfsr_lfssr_forward (n_layer per level: twenty at scale 4).  What does not, with its bits unchanged: LFSR_ARITH_F32 (which wins), LFSSR's per-view
+ * convs (they follow lfsr_set_arithmetic), the fused up-sampling tail, DistgSSR's AngConv (a different operator), and EPIT, LFT and LF_InterNet.  No atomics: taps
+ * and channels run in one fixed order, two runs give the same bits, and a sample's result depends neither on B nor on the grid.  Parity with the reference's fp32
+ * results is claimed only in the default mode (error against fp64 under the mode: below torch.autocast(bfloat16)'s, tests/test_gpu_ang_bf16.py). */
+#define LFSR_ANG_ARITH_DEFAULT 0
+#define LFSR_ANG_ARITH_BF16 1
+int lfsr_set_ang_arithmetic(int mode);   /* LFSR_E_ARG for any other value, nothing changed */
+int lfsr_get_ang_arithmetic(void);
+
 /* ---- operator-level timing hooks (measurement aid; the reference times whole forwards only: check_efficiency_official.py:306-330) ----
  * lfsr_op_profile(1): from now on every instrumented operator entry point brackets its launches with a hipEvent pair on its launch stream (and any
  * earlier records are dropped); lfsr_op_profile(0): off (the default; a hook then costs one atomic load).  lfsr_op_profile_read waits for the recorded

@@ -98,6 +98,8 @@ SIGNATURES = {
     "lfsr_get_gemm_arithmetic": (c_i, []),
     "lfsr_set_branch_arithmetic": (c_i, [c_i]),
     "lfsr_get_branch_arithmetic": (c_i, []),
+    "lfsr_set_ang_arithmetic": (c_i, [c_i]),
+    "lfsr_get_ang_arithmetic": (c_i, []),
     "lfsr_op_profile": (c_i, [c_i]),
     "lfsr_op_profile_read": (C.c_longlong, [C.c_char_p, c_sz]),
     "lfsr_distgssr_profile": (c_i, [c_p, c_i]),
@@ -240,6 +242,20 @@ def set_branch_arithmetic(mode):
 def get_branch_arithmetic():
     """lfsr_get_branch_arithmetic: the mode the next DistgSSR branch / block-tail launch runs in"""
     return int(load().lfsr_get_branch_arithmetic())
+
+
+ANG_ARITH_DEFAULT, ANG_ARITH_BF16 = 0, 1
+
+
+def set_ang_arithmetic(mode):
+    """lfsr_set_ang_arithmetic: ANG_ARITH_DEFAULT (LFSSR's angular 3x3 conv as it is) or ANG_ARITH_BF16 (lfsr_angconv3x3_fwd rounds its operands to bf16, fp32
+    accumulation); process-wide, independent of the other four switches"""
+    check(load().lfsr_set_ang_arithmetic(int(mode)), "set_ang_arithmetic")
+
+
+def get_ang_arithmetic():
+    """lfsr_get_ang_arithmetic: the mode the next lfsr_angconv3x3_fwd launch runs in"""
+    return int(load().lfsr_get_ang_arithmetic())
 
 
 def op_profile(enable):
@@ -427,7 +443,7 @@ class GraphedForward:
         self.graphs = {}
 
     def __call__(self, x):
-        key = (tuple(x.shape), x.device, x.dtype, get_arithmetic(), get_gemm_arithmetic(), get_branch_arithmetic())      # all are read at launch: a graph holds the kernels of the modes it was captured in
+        key = (tuple(x.shape), x.device, x.dtype, get_arithmetic(), get_gemm_arithmetic(), get_branch_arithmetic(), get_ang_arithmetic())      # all are read at launch: a graph holds the kernels of the modes it was captured in
         g = self.graphs.get(key)
         if g is None:
             static_x = x.clone()

@@ -14,7 +14,8 @@
 // instruction ks of the 16 multiplies channels {16 kq + ks}: any split of K is a valid GEMM as long as both operands use the same one.
 // Taps run 0 .. 8 and channels in that fixed order for every output, whatever B, the grid or the band: two runs give the same bits, and a sample's result does not
 // depend on the batch.  At angRes 5 the executed taps are 169 of 225.
-// The kernel has one arithmetic and reads none of the four arithmetic switches (lfsr_set_arithmetic and its three siblings).
+// k_ang3x3 has one arithmetic.  The entry point reads lfsr_set_ang_arithmetic at every launch: under LFSR_ANG_ARITH_BF16 (and not LFSR_ARITH_F32, which wins) the
+// same operation runs on bf16-rounded operands in ang3x3_bf16.hip, after the same argument checks.  It reads none of the other switches.
 #include "lfsr_internal.h"
 
 namespace {
@@ -117,6 +118,8 @@ extern "C" int lfsr_angconv3x3_fwd(const float* x, int x_stride, int x_choff, co
   if (rows * x_stride >= (1LL << 31) / 4 || rows * y_stride >= (1LL << 31) / 4) return LFSR_E_ARG;   // an operand span of 2 GiB or more
   const int R = a3_band_rows(A), tiles = (npix + A3_P - 1) / A3_P, bands = (A + R - 1) / R;
   if ((long long)B * tiles > 0x7fffffffLL) return LFSR_E_ARG;
+  if (lfsr_ang_arith_bf16() && !lfsr_arith_f32())
+    return lfsr_ang3x3_bf16_launch(x, x_stride, x_choff, w_packed, bias, in_bias, y, y_stride, y_choff, B, A, npix, lfsr_stream(stream));
   const int staged = (R + 2 < A ? R + 2 : A) * A;
   const size_t smem = (size_t)staged * A3_P * A3_PITCH * sizeof(float);
   static std::atomic<bool> attr_set[64];

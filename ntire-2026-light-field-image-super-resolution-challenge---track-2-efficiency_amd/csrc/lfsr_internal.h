@@ -151,6 +151,9 @@ int lfsr_distg_epi1_launch(const float* x, int x_stride, int x_choff, const floa
 int lfsr_distg_tail2_launch(const float* spa, int spa_stride, int spa_choff, const float* t_a, const float* t_h, const float* t_v, const float* wa2_packed,
                             const float* w_epi2, const float* wf_packed, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope,
                             hipStream_t st);
+// ang3x3_bf16.hip: lfsr_angconv3x3_fwd's kernel on bf16 operands (lfsr_set_ang_arithmetic(LFSR_ANG_ARITH_BF16)); the caller has checked the operands
+int lfsr_ang3x3_bf16_launch(const float* x, int x_stride, int x_choff, const float* w_packed, const float* bias, const float* in_bias, float* y, int y_stride,
+                            int y_choff, int B, int A, int npix, hipStream_t st);
 // epi_fused.hip  (t_h / t_v: optional (B*A*h*w, 32) buffers receiving the post-LeakyReLU stage-1 activations for backward)
 bool lfsr_epi_fused_ok(int A, int h, int w);
 int lfsr_epi_fused_launch(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed, float* y, int y_stride,

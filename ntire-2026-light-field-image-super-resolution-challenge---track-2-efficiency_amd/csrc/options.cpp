@@ -3,6 +3,7 @@
 //  * lfsr_set_grad_arithmetic: bf16 operands for the 64 -> 64 3x3 conv's data and weight gradients, independent of the first;
 //  * lfsr_set_gemm_arithmetic: bf16 operands for the transformer linears, LayerNorm + q | k | v projections and feed-forward blocks (gemm_bf16.hip), independent of both;
 //  * lfsr_set_branch_arithmetic: bf16 operands for DistgSSR's EPI branch and block tail (distg_bf16.hip), independent of the three;
+//  * lfsr_set_ang_arithmetic: bf16 operands for LFSSR's angular 3x3 conv (ang3x3_bf16.hip), independent of the four;
 //  * lfsr_sel: the A/B selectors of the measurement / parity tooling (LFSR_* environment variables), live only in a process started with LFSR_LAB set.
 #include <stdlib.h>
 
@@ -13,6 +14,7 @@ std::atomic<int> g_arith{LFSR_ARITH_DEFAULT};
 std::atomic<int> g_grad_arith{LFSR_GRAD_ARITH_DEFAULT};
 std::atomic<int> g_gemm_arith{LFSR_GEMM_ARITH_DEFAULT};
 std::atomic<int> g_branch_arith{LFSR_BRANCH_ARITH_DEFAULT};
+std::atomic<int> g_ang_arith{LFSR_ANG_ARITH_DEFAULT};
 std::atomic<int> g_lab{-1};
 }  // namespace
 
@@ -30,6 +32,7 @@ bool lfsr_arith_bf16() { return g_arith.load(std::memory_order_relaxed) == LFSR_
 bool lfsr_grad_arith_bf16() { return g_grad_arith.load(std::memory_order_relaxed) == LFSR_GRAD_ARITH_BF16; }
 bool lfsr_gemm_arith_bf16() { return g_gemm_arith.load(std::memory_order_relaxed) == LFSR_GEMM_ARITH_BF16; }
 bool lfsr_branch_arith_bf16() { return g_branch_arith.load(std::memory_order_relaxed) == LFSR_BRANCH_ARITH_BF16; }
+bool lfsr_ang_arith_bf16() { return g_ang_arith.load(std::memory_order_relaxed) == LFSR_ANG_ARITH_BF16; }
 
 extern "C" {
 
@@ -64,5 +67,13 @@ int lfsr_set_branch_arithmetic(int mode) {
 }
 
 int lfsr_get_branch_arithmetic(void) { return g_branch_arith.load(); }
+
+int lfsr_set_ang_arithmetic(int mode) {
+  if (mode != LFSR_ANG_ARITH_DEFAULT && mode != LFSR_ANG_ARITH_BF16) return LFSR_E_ARG;
+  g_ang_arith.store(mode);
+  return LFSR_OK;
+}
+
+int lfsr_get_ang_arithmetic(void) { return g_ang_arith.load(); }
 
 }  // extern "C"
