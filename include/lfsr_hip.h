@@ -610,6 +610,33 @@ int lfsr_get_branch_arithmetic(void);
 int lfsr_set_ang_arithmetic(int mode);   /* LFSR_E_ARG for any other value, nothing changed */
 int lfsr_get_ang_arithmetic(void);
 
+/* ---- arithmetic of LF_InterNet's wide per-view 3x3 convs: a sixth process-wide selection, independent of the five above, read at every launch ----
+ * LFSR_WIDE_ARITH_DEFAULT: every kernel as it is, bit for bit.
+ * LFSR_WIDE_ARITH_BF16: opt-in.  lfsr_conv3x3_wide_fwd (below) rounds its activations and its weight to bf16 (nearest even) once, the weight from its fp32 pack
+ * while a block stages it, so the pack, lfsr_internet_packed_bytes and the workspace do not change.  The products are exact; accumulation, LeakyReLU, the
+ * residual add and stores are fp32; x, r1 and y stay fp32 in memory.  The argument checks and return codes are the default's.  What follows: lfsr_conv3x3_wide_fwd
+ * and, through its launcher, the sixteen SpaConvSq (128 -> 64) and the SpaBottle (320 -> 64) of lfsr_internet_forward: 82 % of that forward's arithmetic.  What
+ * does not, with its bits unchanged: LFSR_ARITH_F32 (which wins), lfsr_internet_forward_train and lfsr_internet_backward (the training forward launches the
+ * gather-GEMM itself and reads no switch: a training step is the same in either mode), LF_InterNet's other operators (its 128 -> 64 angular squeeze follows
+ * lfsr_set_gemm_arithmetic), lfsr_conv3x3_fwd, lfsr_conv3x3_n_fwd, lfsr_angconv3x3_fwd, and DistgSSR, EPIT, LFT and LFSSR.  No atomics: chunks, taps and channels
+ * run in one fixed order, two runs give the same bits, and an image's result does not depend on n_img.  Parity with the reference's fp32 results is claimed only
+ * in the default mode (error against fp64 under the mode: below torch.autocast(bfloat16)'s, tests/test_gpu_wide_bf16.py). */
+#define LFSR_WIDE_ARITH_DEFAULT 0
+#define LFSR_WIDE_ARITH_BF16 1
+int lfsr_set_wide_arithmetic(int mode);   /* LFSR_E_ARG for any other value, nothing changed */
+int lfsr_get_wide_arithmetic(void);
+/* The wide per-view 3x3 conv of LF_InterNet (SpaConvSq, LF_InterNet.py:64; BottleNeck.SpaBottle, :122): zero pad 1, cin in {128, 320} -> 64 channels, on the VCL
+ * rows of n_img view images of h x w:  y = LeakyReLU_slope(conv(x)) + r1   (slope 0: ReLU, 1: identity; r1 may be NULL).
+ * w_packed: lfsr_pack_conv_weight(w, packed, 64, cin, 9, 0, 0), [9][64][cin] fp32.  r1 may alias x (the model passes the first 64 channels of the same rows);
+ * y must not overlap x.  LFSR_E_ARG before any launch, nothing written, in both arithmetics: NULL x / w_packed / y, cin outside {128, 320}, non-positive n_img /
+ * h / w, x_stride < x_choff + cin, y_stride < y_choff + 64 (r1 likewise when given), a negative stride or offset or one that is no multiple of 4, a pointer off
+ * the 16-byte grid, an operand span (n_img h w stride floats) of 2 GiB or more.  Then the switch above selects the kernel: the gather-GEMM on the fp32 MFMA
+ * pipe (default, and under LFSR_ARITH_F32), or csrc/conv3x3_wide_bf16.hip. */
+int lfsr_conv3x3_wide_fwd(const float* x, int x_stride, int x_choff, int cin, const float* w_packed,
+                          float* y, int y_stride, int y_choff,
+                          const float* r1, int r1_stride, int r1_choff,
+                          int n_img, int h, int w, float slope, void* stream);
+
 /* ---- operator-level timing hooks (measurement aid; the reference times whole forwards only: check_efficiency_official.py:306-330) ----
  * lfsr_op_profile(1): from now on every instrumented operator entry point brackets its launches with a hipEvent pair on its launch stream (and any
  * earlier records are dropped); lfsr_op_profile(0): off (the default; a hook then costs one atomic load).  lfsr_op_profile_read waits for the recorded

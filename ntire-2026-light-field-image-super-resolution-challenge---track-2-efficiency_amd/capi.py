@@ -100,6 +100,9 @@ SIGNATURES = {
     "lfsr_get_branch_arithmetic": (c_i, []),
     "lfsr_set_ang_arithmetic": (c_i, [c_i]),
     "lfsr_get_ang_arithmetic": (c_i, []),
+    "lfsr_set_wide_arithmetic": (c_i, [c_i]),
+    "lfsr_get_wide_arithmetic": (c_i, []),
+    "lfsr_conv3x3_wide_fwd": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
     "lfsr_op_profile": (c_i, [c_i]),
     "lfsr_op_profile_read": (C.c_longlong, [C.c_char_p, c_sz]),
     "lfsr_distgssr_profile": (c_i, [c_p, c_i]),
@@ -256,6 +259,20 @@ def set_ang_arithmetic(mode):
 def get_ang_arithmetic():
     """lfsr_get_ang_arithmetic: the mode the next lfsr_angconv3x3_fwd launch runs in"""
     return int(load().lfsr_get_ang_arithmetic())
+
+
+WIDE_ARITH_DEFAULT, WIDE_ARITH_BF16 = 0, 1
+
+
+def set_wide_arithmetic(mode):
+    """lfsr_set_wide_arithmetic: WIDE_ARITH_DEFAULT (LF_InterNet's wide per-view 3x3 convs as they are) or WIDE_ARITH_BF16 (lfsr_conv3x3_wide_fwd, and with it the
+    SpaConvSq and SpaBottle of the inference forward, rounds its operands to bf16, fp32 accumulation); process-wide, independent of the other five switches"""
+    check(load().lfsr_set_wide_arithmetic(int(mode)), "set_wide_arithmetic")
+
+
+def get_wide_arithmetic():
+    """lfsr_get_wide_arithmetic: the mode the next lfsr_conv3x3_wide_fwd launch runs in"""
+    return int(load().lfsr_get_wide_arithmetic())
 
 
 def op_profile(enable):
@@ -443,7 +460,7 @@ class GraphedForward:
         self.graphs = {}
 
     def __call__(self, x):
-        key = (tuple(x.shape), x.device, x.dtype, get_arithmetic(), get_gemm_arithmetic(), get_branch_arithmetic(), get_ang_arithmetic())      # all are read at launch: a graph holds the kernels of the modes it was captured in
+        key = (tuple(x.shape), x.device, x.dtype, get_arithmetic(), get_gemm_arithmetic(), get_branch_arithmetic(), get_ang_arithmetic(), get_wide_arithmetic())      # all are read at launch: a graph holds the kernels of the modes it was captured in
         g = self.graphs.get(key)
         if g is None:
             static_x = x.clone()
@@ -668,6 +685,18 @@ def conv3x3(x, w_packed, n_img, h, w, slope=1.0, res1=None, res2=None, out=None,
                                _opt(res1), res1.shape[1] if res1 is not None else 0, 0,
                                _opt(res2), res2.shape[1] if res2 is not None else 0, 0,
                                n_img, h, w, slope, stream_ptr()), "conv3x3_fwd")
+    return out
+
+
+def conv3x3_wide(x, cin, w_packed, n_img, h, w, slope=0.0, res1=None, res1_choff=0, out=None, out_choff=0, x_choff=0):
+    """lfsr_conv3x3_wide_fwd: lrelu(per-view 3x3 conv, cin in {128, 320} -> 64, slope) (+ res1's 64 channels from res1_choff on; res1 may be x itself) on VCL
+    rows; w_packed: pack_conv_weight of the (64, cin, 3, 3) weight.  Follows set_wide_arithmetic."""
+    lib = load()
+    if out is None:
+        out = torch.empty((n_img * h * w, 64), dtype=torch.float32, device=x.device)
+    check(lib.lfsr_conv3x3_wide_fwd(dev_ptr(x), x.shape[1], x_choff, cin, dev_ptr(w_packed), dev_ptr(out), out.shape[1], out_choff,
+                                    _opt(res1), res1.shape[1] if res1 is not None else 0, res1_choff if res1 is not None else 0,
+                                    n_img, h, w, slope, stream_ptr()), "conv3x3_wide_fwd")
     return out
 
 

@@ -5,7 +5,8 @@
 //   Spa2Ang (AxA stride A, 64->64)  = IN_ANG gather-GEMM, ReLU, into the angular rows' upper half
 //   Ang2Spa (1x1 64->A*A*64 + PixelShuffle(A)) = pointwise GEMM with OUT_VIEWS scatter into the spatial rows' upper half
 //   AngConvSq (1x1 128->64)         = row-wise GEMM over the 128-wide angular rows
-//   SpaConvSq (dilated 3x3 128->64) = per-view 3x3 gather-GEMM over the 128-wide spatial rows
+//   SpaConvSq (dilated 3x3 128->64) = per-view 3x3 gather-GEMM over the 128-wide spatial rows; it and BottleNeck.SpaBottle (320->64) go through
+//     lfsr_conv3x3_wide_run, the launcher of lfsr_conv3x3_wide_fwd, and so follow lfsr_set_wide_arithmetic (bf16 operands: conv3x3_wide_bf16.hip)
 // ReconBlock's PreConv -> MacPI2SAI -> PixelShuffle(s) -> FinalConv chain is linear and is folded to one 3x3 conv 64->s^2
 // whose epilogue scatters straight into the HR SAI mosaic.
 #include "gemm_gather_kernel.h"
@@ -78,7 +79,36 @@ int lfsr_internet_copy64(const float* src, int s_stride, int s_choff, float* dst
   return LFSR_OK;
 }
 
+// The wide per-view 3x3 conv (SpaConvSq 128 -> 64, SpaBottle 320 -> 64) as lfsr_set_wide_arithmetic selects it, read at every launch.  Default, or LFSR_ARITH_F32
+// (which wins): the gather-GEMM on the fp32 MFMA pipe, the launch lfsr_internet_forward has always issued.  LFSR_WIDE_ARITH_BF16: conv3x3_wide_bf16.hip.
+// lfsr_internet_forward_train (internet_train.hip) does not come through here: it launches the gather-GEMM itself and reads no switch.
+int lfsr_conv3x3_wide_run(const float* x, int x_stride, int x_choff, int cin, const float* w_packed, float* y, int y_stride, int y_choff, const float* r1,
+                          int r1_stride, int r1_choff, int n_img, int h, int w, float slope, int A, hipStream_t st) {
+  if (lfsr_wide_arith_bf16() && !lfsr_arith_f32())
+    return lfsr_conv3x3_wide_bf16_launch(x, x_stride, x_choff, cin, w_packed, y, y_stride, y_choff, r1, r1_stride, r1_choff, n_img, h, w, slope, st);
+  GemmArgs p{};
+  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wp = w_packed; p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff;
+  p.R1 = r1; p.r1_stride = r1_stride; p.r1_choff = r1_choff;
+  p.M = n_img * h * w; p.N = 64; p.Npad = 64; p.A = A; p.AA = A * A; p.H = h; p.W = w; p.ntaps = 9; p.CH = 64; p.slope = slope;
+  if (cin == 128) return launch_gemm<IN_CONV3, OUT_SAME, 128, 2>(p, st);
+  if (cin == 320) return launch_gemm<IN_CONV3, OUT_SAME, 320, 2>(p, st);
+  return LFSR_E_ARG;
+}
+
 extern "C" {
+
+int lfsr_conv3x3_wide_fwd(const float* x, int x_stride, int x_choff, int cin, const float* w_packed, float* y, int y_stride, int y_choff, const float* r1,
+                          int r1_stride, int r1_choff, int n_img, int h, int w, float slope, void* stream) {
+  LfsrOpTimer op_t("conv3x3_wide", cin, h * w, lfsr_stream(stream));
+  if (!x || !w_packed || !y || (cin != 128 && cin != 320) || n_img <= 0 || h <= 0 || w <= 0) return LFSR_E_ARG;
+  if (x_choff < 0 || y_choff < 0 || x_stride < x_choff + cin || y_stride < y_choff + 64 || ((x_stride | x_choff | y_stride | y_choff) & 3)) return LFSR_E_ARG;
+  if (r1 && (r1_choff < 0 || r1_stride < r1_choff + 64 || ((r1_stride | r1_choff) & 3))) return LFSR_E_ARG;
+  if (((uintptr_t)x | (uintptr_t)w_packed | (uintptr_t)y | (uintptr_t)r1) & 15) return LFSR_E_ARG;
+  const long long rows = (long long)n_img * h * w, lim = (1LL << 31) / 4;   // an operand span of 2 GiB or more
+  if (rows * x_stride >= lim || rows * y_stride >= lim || (r1 && rows * r1_stride >= lim)) return LFSR_E_ARG;
+  return lfsr_conv3x3_wide_run(x, x_stride, x_choff, cin, w_packed, y, y_stride, y_choff, r1, r1 ? r1_stride : 0, r1 ? r1_choff : 0, n_img, h, w, slope, 1,
+                               lfsr_stream(stream));
+}
 
 int lfsr_internet_create(lfsr_internet** out, int A, int scale, int n_groups, int n_layers) {
   if (!out || A <= 0 || A > 9 || scale < 2 || scale > 4 || n_groups <= 0 || n_layers <= 0) return LFSR_E_ARG;
@@ -177,7 +207,7 @@ int lfsr_internet_forward(lfsr_internet* c, const float* x, float* out, int B, i
       LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, Ar[cur], 128, 0, P.w(p + "Ang2Spa.0.weight"), S[cur], 128, 64, nullptr, 0, 0, (int)nlr, AA * 64, 1, 64, 1.0f));
       // out_a = ReLU(AngConvSq(cat(xa, ang2))) + xa ; out_s = ReLU(SpaConvSq(cat(xs, spa2))) + xs
       LFSR_RC(lfsr_linear_fwd(Ar[cur], 128, 0, 128, P.w(p + "AngConvSq.weight"), nullptr, Ar[cur], 128, 0, Ar[nxt], 128, 0, nlr, 64, 0.0f, stream));
-      LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 128, 2>, S[cur], 128, 0, P.w(p + "SpaConvSq.weight"), S[nxt], 128, 0, S[cur], 128, 0, (int)npix, 64, 9, 64, 0.0f));
+      LFSR_RC(lfsr_conv3x3_wide_run(S[cur], 128, 0, 128, P.w(p + "SpaConvSq.weight"), S[nxt], 128, 0, S[cur], 128, 0, nimg, h, w, 0.0f, A, st));   // follows lfsr_set_wide_arithmetic
       cur = nxt;
     }
     hipLaunchKernelGGL(k_copy64, dim3(lfsr_cap_grid(nlr * 16)), dim3(256), 0, st, Ar[cur], 128, 0, CA, ca_stride, 64 * g, nlr);
@@ -188,7 +218,7 @@ int lfsr_internet_forward(lfsr_internet* c, const float* x, float* out, int B, i
   // BottleNeck (LF_InterNet.py:119-124)
   LFSR_RC(lfsr_linear_fwd(CA, ca_stride, 0, 64 * G, P.w("BottleNeck.AngBottle.weight"), nullptr, nullptr, 0, 0, Ar[0], 128, 0, nlr, 64, 0.0f, stream));
   LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, Ar[0], 128, 0, P.w("BottleNeck.Ang2Spa.0.weight"), CS, cs_stride, 64 * G, nullptr, 0, 0, (int)nlr, AA * 64, 1, 64, 1.0f));
-  LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 320, 2>, CS, cs_stride, 0, P.w("BottleNeck.SpaBottle.weight"), BO, 64, 0, XS0, 64, 0, (int)npix, 64, 9, 64, 0.0f));
+  LFSR_RC(lfsr_conv3x3_wide_run(CS, cs_stride, 0, 320, P.w("BottleNeck.SpaBottle.weight"), BO, 64, 0, XS0, 64, 0, nimg, h, w, 0.0f, A, st));   // ... and so does this
   // ReconBlock (LF_InterNet.py:136-141), folded: 3x3 conv 64 -> s^2, epilogue = MacPI2SAI + PixelShuffle(s)
   LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_PS_HR, 64, 1>, BO, 64, 0, P.packed + c->off_wf, out, 1, 0, nullptr, 0, 0, (int)npix, c->s * c->s, 9, 1, 1.0f));
   return LFSR_OK;

@@ -154,6 +154,13 @@ int lfsr_distg_tail2_launch(const float* spa, int spa_stride, int spa_choff, con
 // ang3x3_bf16.hip: lfsr_angconv3x3_fwd's kernel on bf16 operands (lfsr_set_ang_arithmetic(LFSR_ANG_ARITH_BF16)); the caller has checked the operands
 int lfsr_ang3x3_bf16_launch(const float* x, int x_stride, int x_choff, const float* w_packed, const float* bias, const float* in_bias, float* y, int y_stride,
                             int y_choff, int B, int A, int npix, hipStream_t st);
+// internet.hip: lfsr_conv3x3_wide_fwd behind its argument checks -- y = lrelu(conv3x3(x), slope) (+ r1), cin in {128, 320} -> 64, as lfsr_set_wide_arithmetic selects
+// it at this launch: the gather-GEMM launch_gemm<IN_CONV3, OUT_SAME, cin, 2> (AA: what lfsr_internet_forward passes as GemmArgs.A * A, 1 from the operator), or
+// conv3x3_wide_bf16.hip's kernel under LFSR_WIDE_ARITH_BF16 unless LFSR_ARITH_F32 is set
+int lfsr_conv3x3_wide_run(const float* x, int x_stride, int x_choff, int cin, const float* w_packed, float* y, int y_stride, int y_choff, const float* r1,
+                          int r1_stride, int r1_choff, int n_img, int h, int w, float slope, int A, hipStream_t st);
+int lfsr_conv3x3_wide_bf16_launch(const float* x, int x_stride, int x_choff, int cin, const float* w_packed, float* y, int y_stride, int y_choff,
+                                  const float* r1, int r1_stride, int r1_choff, int n_img, int h, int w, float slope, hipStream_t st);
 // epi_fused.hip  (t_h / t_v: optional (B*A*h*w, 32) buffers receiving the post-LeakyReLU stage-1 activations for backward)
 bool lfsr_epi_fused_ok(int A, int h, int w);
 int lfsr_epi_fused_launch(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed, float* y, int y_stride,
