@@ -314,7 +314,7 @@ int lfsr_layernorm_bwd(const float* x, const float* pe, long long pe_rows, long 
 /* Data gradient of nn.Linear y = x W^T, W (cout, cin), with the extras of the transformer sublayers:  dx = (dy W) * (act > 0 ? 1 : 0) + r1.
  * dy: M dense rows of cout in {64,128,256,576,1024}, 16-byte aligned; wT_packed from lfsr_pack_conv_weight_tr(W, cout, cin, 1); cin in {64,128,256}.
  * dx, r1 (NULL: none), act (NULL: no mask; the saved ReLU output): rows of cin floats at row strides >= cin that are multiples of 4; r1 may be dx itself.
- * Writes columns [0, cin) of the M rows of dx and nothing else.  M < 2^31 - 128.  LFSR_E_ARG before any launch. */
+ * Writes columns [0, cin) of the M rows of dx and nothing else.  M < 2^31 - 128.  LFSR_E_ARG before any launch.  Follows lfsr_set_lin_grad_arithmetic (below). */
 int lfsr_linear_dgrad(const float* dy, int cout, const float* wT_packed, float* dx, int dx_stride, const float* r1, int r1_stride, const float* act, int act_stride,
                       long long M, int cin, void* stream);
 /* Backward of lfsr_hr_tail_fwd's LeakyReLU(slope) + 3x3 conv 64 -> 1 (zero pad 1 over the whole mosaic), s in {2,3,4}:
@@ -547,7 +547,7 @@ int lfsr_get_arithmetic(void);
  *  - the weight gradient of that conv where it runs on the tile kernel (lfsr_conv3x3_wgrad and lfsr_distgssr_backward): dy and x are rounded to bf16, products
  *    exact, fp32 accumulation into the same per-block partial slabs, the same reduction.  lfsr_conv3x3_wgrad_workspace_floats does not depend on the mode.
  * What does not change: gradients, activations and slabs stay fp32 in memory; the forward (it does not read this switch); the EPI, angular, fuse.0, 1x1,
- * 128 -> 64 and up-sampling gradients; the transformers' GEMM gradients; unaligned data-gradient operands (fp32 gather-GEMM); strides the bf16 weight-gradient
+ * 128 -> 64 and up-sampling gradients; the transformers' GEMM gradients (they have a switch of their own: lfsr_set_lin_grad_arithmetic below); unaligned data-gradient operands (fp32 gather-GEMM); strides the bf16 weight-gradient
  * kernel does not cover (the default kernel); and the 3x3 weight gradients of the EPIT, LFT and LF_InterNet drivers, which run through the generic gather
  * weight-gradient kernel.  bf16 keeps fp32's exponent range: no loss scaling is needed.  Both kernels are free of atomics: two runs give the same bits, and an
  * image's data gradient does not depend on how many images the launch has.  Parity with the reference's fp32 gradients is claimed only in the default mode
@@ -636,6 +636,39 @@ int lfsr_conv3x3_wide_fwd(const float* x, int x_stride, int x_choff, int cin, co
                           float* y, int y_stride, int y_choff,
                           const float* r1, int r1_stride, int r1_choff,
                           int n_img, int h, int w, float slope, void* stream);
+
+/* ---- arithmetic of the linears' GRADIENTS (the transformers' GEMM gradients): a seventh process-wide selection, independent of the six above, read at every launch ----
+ * LFSR_LIN_GRAD_ARITH_DEFAULT: every gradient kernel as it is, bit for bit.
+ * LFSR_LIN_GRAD_ARITH_BF16: opt-in, what LFSR_GRAD_ARITH_BF16 leaves out.  Two operators change:
+ *  - the weight gradient of a linear, lfsr_linear_wgrad (below) and LfsrTransBwd::wgrad_lin inside the drivers: dy and x are rounded to bf16 (nearest even) on their
+ *    way into LDS, the products are exact (v_mfma_f32_32x32x16_bf16, the row index as the MFMA's K), accumulation is fp32 into per-block partial slabs, and the same
+ *    fixed-order reduction sums them -- one launch and one reduction per linear, where the default runs one of each per 64 output rows
+ *    (csrc/lin_wgrad_bf16.hip: how often dy and x are read);
+ *  - the data gradient of a linear, lfsr_linear_dgrad and LfsrTransBwd::dgemm: dy and the transposed weight (from the fp32 pack, while a block stages it: no new
+ *    pack, no new workspace) are rounded to bf16 once, the products are exact, accumulation is fp32, and the act > 0 mask and the r1 add are fp32 after the
+ *    accumulation (csrc/lin_dgrad_bf16.hip).  Every shape the entry point accepts, r1 == dx, columns [0, cin) only; the argument checks and return codes are the
+ *    default's; an operand pointer off the 16-byte grid runs the default kernel.
+ * What follows: lfsr_epit_backward and lfsr_lft_backward, in every linear of their sublayers (feed_forward.1 / .4, out_proj, in_proj), EPIT's linear_in /
+ * linear_out, LFT's linear.0 and upsampling.0.  What does not, with its bits unchanged: the forwards and forward_train (they read no gradient switch), the
+ * recomputation inside the backward, the attention and LayerNorm backward, every 3x3 conv gradient (the conv_init stack, LFT's position 3x3, the tail's 3x3: the
+ * generic weight-gradient kernel and lfsr_set_grad_arithmetic), lfsr_pointwise_dgrad / lfsr_pointwise_wgrad, and DistgSSR, LF_InterNet and LFSSR.  It does not
+ * interact with lfsr_set_arithmetic: no "F32 wins" rule, as for the grad switch.  lfsr_linear_wgrad_workspace_floats and lfsr_*_train_workspace_bytes do not depend
+ * on the mode.  Gradients, activations and slabs stay fp32 in memory; bf16 keeps fp32's exponent range: no loss scaling is needed.  Both kernels are free of
+ * atomics: two runs give the same bits, and a row's data gradient does not depend on M.  Parity with the reference's fp32 gradients is claimed only in the default
+ * mode (error against fp64 autograd under the mode: tests/test_gpu_lin_grad_bf16.py). */
+#define LFSR_LIN_GRAD_ARITH_DEFAULT 0
+#define LFSR_LIN_GRAD_ARITH_BF16 1
+int lfsr_set_lin_grad_arithmetic(int mode);   /* LFSR_E_ARG for any other value, nothing changed */
+int lfsr_get_lin_grad_arithmetic(void);
+/* Weight gradient of nn.Linear y = x W^T, W (cout, cin):  dw[n][k] (=, or += if accumulate) sum over m < M of dy[m][n] x[m][k], dw in the raw (cout, cin) layout.
+ * cout in {64,128,256,576,1024}, cin in {64,128,256}; dy / x: rows of cout / cin floats at row strides that are multiples of 4 and at least the row width;
+ * dy, x, dw, workspace 16-byte aligned; 0 < M < 2^31 - 128.  workspace: lfsr_linear_wgrad_workspace_floats(M, cout, cin) floats of partial slabs (0 for a
+ * refused shape; the same in both modes).  LFSR_E_ARG / LFSR_E_WS before any launch, nothing written.  Then the switch above selects the kernels.  Default: what the
+ * drivers run, a loop over the 64-row slices of W through the generic gather weight-gradient kernel and its reduction -- the bits of lfsr_pointwise_wgrad called per
+ * slice with dy_choff = n0.  LFSR_LIN_GRAD_ARITH_BF16: csrc/lin_wgrad_bf16.hip and one reduction.  No float atomics in either: two runs give the same bits. */
+size_t lfsr_linear_wgrad_workspace_floats(long long M, int cout, int cin);
+int lfsr_linear_wgrad(const float* dy, int dy_stride, const float* x, int x_stride, float* dw, float* workspace, size_t workspace_floats, long long M, int cout,
+                      int cin, int accumulate, void* stream);
 
 /* ---- operator-level timing hooks (measurement aid; the reference times whole forwards only: check_efficiency_official.py:306-330) ----
  * lfsr_op_profile(1): from now on every instrumented operator entry point brackets its launches with a hipEvent pair on its launch stream (and any

@@ -102,6 +102,10 @@ SIGNATURES = {
     "lfsr_get_ang_arithmetic": (c_i, []),
     "lfsr_set_wide_arithmetic": (c_i, [c_i]),
     "lfsr_get_wide_arithmetic": (c_i, []),
+    "lfsr_set_lin_grad_arithmetic": (c_i, [c_i]),
+    "lfsr_get_lin_grad_arithmetic": (c_i, []),
+    "lfsr_linear_wgrad_workspace_floats": (c_sz, [C.c_longlong, c_i, c_i]),
+    "lfsr_linear_wgrad": (c_i, [c_p, c_i, c_p, c_i, c_p, c_p, c_sz, C.c_longlong, c_i, c_i, c_i, c_p]),
     "lfsr_conv3x3_wide_fwd": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
     "lfsr_op_profile": (c_i, [c_i]),
     "lfsr_op_profile_read": (C.c_longlong, [C.c_char_p, c_sz]),
@@ -273,6 +277,21 @@ def set_wide_arithmetic(mode):
 def get_wide_arithmetic():
     """lfsr_get_wide_arithmetic: the mode the next lfsr_conv3x3_wide_fwd launch runs in"""
     return int(load().lfsr_get_wide_arithmetic())
+
+
+LIN_GRAD_ARITH_DEFAULT, LIN_GRAD_ARITH_BF16 = 0, 1
+
+
+def set_lin_grad_arithmetic(mode):
+    """lfsr_set_lin_grad_arithmetic: LIN_GRAD_ARITH_DEFAULT (the linears' weight and data gradients as they are) or LIN_GRAD_ARITH_BF16 (lfsr_linear_wgrad and
+    lfsr_linear_dgrad, and with them every linear of the EPIT and LFT backward, round their operands to bf16, fp32 accumulation); process-wide, independent of the
+    other six switches"""
+    check(load().lfsr_set_lin_grad_arithmetic(int(mode)), "set_lin_grad_arithmetic")
+
+
+def get_lin_grad_arithmetic():
+    """lfsr_get_lin_grad_arithmetic: the mode the next lfsr_linear_wgrad / lfsr_linear_dgrad launch runs in"""
+    return int(load().lfsr_get_lin_grad_arithmetic())
 
 
 def op_profile(enable):
@@ -879,6 +898,31 @@ def pointwise_wgrad(dy, x, cout, cin):
     check(lib.lfsr_pointwise_wgrad(dev_ptr(dy), dy.shape[1], 0, cout, dev_ptr(x), x.shape[1], 0, cin, dev_ptr(dw), dev_ptr(ws), ws.numel(), M, 0,
                                    stream_ptr()), "pointwise_wgrad")
     return dw
+
+
+def linear_wgrad(dy, x, cout, cin, dw=None):
+    """lfsr_linear_wgrad: dw (cout, cin) = dy^T x over the rows of dy (M, >= cout) and x (M, >= cin); dw given: accumulated into.  Follows set_lin_grad_arithmetic."""
+    lib = load()
+    M = dy.shape[0]
+    acc = dw is not None
+    if dw is None:
+        dw = torch.empty((cout, cin), dtype=torch.float32, device=dy.device)
+    ws = torch.empty(lib.lfsr_linear_wgrad_workspace_floats(M, cout, cin), dtype=torch.float32, device=dy.device)
+    check(lib.lfsr_linear_wgrad(dev_ptr(dy), dy.shape[1], dev_ptr(x), x.shape[1], dev_ptr(dw), dev_ptr(ws), ws.numel(), M, cout, cin, int(acc), stream_ptr()),
+          "linear_wgrad")
+    return dw
+
+
+def linear_dgrad(dy, wT_packed, cin, r1=None, act=None, dx=None):
+    """lfsr_linear_dgrad: dx (M, cin) = (dy W) * (act > 0) + r1 from dense rows dy (M, cout) and wT_packed = pack_conv_weight_T of the (cout, cin, 1, 1) weight;
+    r1 / act: optional (M, >= cin) rows; dx given: columns [0, cin) of its rows are written (r1 may be dx).  Follows set_lin_grad_arithmetic."""
+    lib = load()
+    M, cout = dy.shape
+    if dx is None:
+        dx = torch.empty((M, cin), dtype=torch.float32, device=dy.device)
+    check(lib.lfsr_linear_dgrad(dev_ptr(dy), cout, dev_ptr(wT_packed), dev_ptr(dx), dx.shape[1], _opt(r1), r1.shape[1] if r1 is not None else 0,
+                                _opt(act), act.shape[1] if act is not None else 0, M, cin, stream_ptr()), "linear_dgrad")
+    return dx
 
 
 class RcclComm:

@@ -279,6 +279,20 @@ int lfsr_wgrad_conv3_bf16_launch(const float* G, int g_stride, int g_choff, cons
                                  int n_img, int h, int w, int blocks, hipStream_t st);
 int lfsr_wgrad_conv3_launch(const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff, float* P,
                             int n_img, int h, int w, hipStream_t st);
+// lin_wgrad_bf16.hip: a linear's weight gradient on bf16-rounded operands (LFSR_LIN_GRAD_ARITH_BF16): `blocks` blocks along x, each writing
+// lfsr_lin_wgrad_bf16_slabs_per_block(cout, cin) slabs [cout][cin]; _blocks: one per row tile up to 256 blocks in all, and no more than cap_floats holds (0: not one)
+int lfsr_lin_wgrad_bf16_slabs_per_block(int cout, int cin);
+int lfsr_lin_wgrad_bf16_blocks(long long M, int cout, int cin, size_t cap_floats);
+int lfsr_lin_wgrad_bf16_launch(const float* G, int g_stride, const float* X, int x_stride, float* P, long long M, int cout, int cin, int blocks, hipStream_t st);
+// lin_dgrad_bf16.hip: lfsr_linear_dgrad's kernel on bf16-rounded operands behind the default's argument checks; LFSR_E_ARG = not covered, the default kernel runs
+int lfsr_lin_dgrad_bf16_launch(const float* dy, int cout, const float* wT_packed, float* dx, int dx_stride, const float* r1, int r1_stride, const float* act,
+                               int act_stride, long long M, int cin, hipStream_t st);
+// trans_bwd.hip: the weight gradient of a (cout, cin) linear as lfsr_set_lin_grad_arithmetic selects it at this launch, what lfsr_linear_wgrad and
+// LfsrTransBwd::wgrad_lin both run.  Default: every 64-row slice through lfsr_wgrad_launch(IN_SAME, IN_SAME) + lfsr_wgrad_reduce.  part: part_floats floats,
+// at least lfsr_linear_wgrad_part_floats (LFSR_E_WS otherwise, nothing launched); the bf16 form sizes its grid to what part holds
+size_t lfsr_linear_wgrad_part_floats(long long M, int cout, int cin);   // what either mode needs at least; 0: shape not covered
+int lfsr_linear_wgrad_run(const float* dy, int dy_stride, const float* x, int x_stride, float* dw, float* part, size_t part_floats, long long M, int cout, int cin,
+                          int accumulate, int A, int h, int w, hipStream_t st);
 // c_valid < C: only the first c_valid input channels are written, with row length c_valid (init_conv's 9 taps)
 int lfsr_wgrad_reduce(const float* P, int nsplit, const float* P2, int nsplit2, float* dW, int O, int C, int T, int perm, int ch,
                       int accumulate, int c_valid, int chunk_mode, hipStream_t st);
@@ -331,7 +345,7 @@ int lfsr_trans_tail(const LfsrTransSel& sel, const LfsrParamTable& P, const floa
 inline size_t lfsr_tr3_floats() { return lfsr_packed_weight_tr_floats(64, 64, 9); }   // the 64 -> 64 3x3 data gradient's pack
 // geometry the training paths cover: every activation below 2 GiB (the widest rows: the 256-float q | k, and the HR map of 64 s^2 floats per LR pixel)
 bool lfsr_trans_train_geometry_ok(int A, int s, int B, int h, int w);
-size_t lfsr_trans_wgrad_partial_max(int B, int A, int h, int w);   // the largest partial slab of the weight gradients over all B A^2 h w pixels
+size_t lfsr_trans_wgrad_partial_max(int B, int A, int h, int w);   // the largest partial slab of the weight gradients over all B A^2 h w pixels, and at least one (1024, 64) slab of lin_wgrad_bf16.hip
 // the scratch of the shared stages (rows = VCL pixels): the tail's hr / du (64 s^2), ptail and up0T; the head's r4 / d64 / t64 (64), xg9 (16) and
 // initT; a sublayer's lnt / dln / dsm / dso / dv (128), dh / dqk (256); part / pln: the weight gradients' and the LayerNorm backward's partials
 struct LfsrTransBwdWs {
@@ -348,11 +362,12 @@ struct LfsrTransBwd {
   LfsrTransBwd(const LfsrParamTable& P_, float* grads, const LfsrTransBwdWs& ws_, int B_, int A_, int h_, int w_, int S_, hipStream_t st_)
       : P(P_), gbase(grads), ws(ws_), B(B_), A(A_), h(h_), w(w_), S(S_), nimg(B_ * A_ * A_), npix(B_ * A_ * A_ * h_ * w_), st(st_) {}
   float* G(const std::string& k) const;
-  // 1x1 data gradient Y (N columns) = X (dense rows of cin in {64, 128, 256, 576, 1024}) . WT, then * (Mk > 0 ? 1 : 0) (ReLU'), then + R1 (may alias Y)
+  // 1x1 data gradient Y (N columns) = X (dense rows of cin in {64, 128, 256, 576, 1024}) . WT, then * (Mk > 0 ? 1 : 0) (ReLU'), then + R1 (may alias Y);
+  // follows lfsr_set_lin_grad_arithmetic
   int dgemm(const float* X, int cin, const float* WT, float* Y, int ys, const float* R1, int r1s, const float* Mk, int mks, int N) const;
   // weight gradient of output rows [n0, n0 + N) (N <= 64) of a raw (O, C, T) weight: partial slabs, then the fixed-order reduce
   int wgrad(int xm, const float* Gr, int gs, int go, const float* X, int xs, int M, int N, int K, int ntaps, float* dW, int accumulate, int c_valid = 0) const;
-  // every 64-row slice of a (O, K) linear weight's gradient: Gr (O columns, stride gs) against X (K columns), over all pixels
+  // a (O, K) linear weight's gradient: Gr (O columns, stride gs) against X (K columns), over all pixels (lfsr_linear_wgrad_run: follows lfsr_set_lin_grad_arithmetic)
   int wgrad_lin(const float* Gr, int gs, int O, const float* X, int xs, int K, float* dW) const;
   int ew(int C, const float* a, const float* b, const float* mk, float slope, float* d) const;   // lfsr_ew_launch on dense rows of C, over all pixels
   // LayerNorm backward with the gradients of its affine parameters written to G(gkey) / G(bkey); no position embedding: pe = nullptr, pe_rows = pe_div = 1

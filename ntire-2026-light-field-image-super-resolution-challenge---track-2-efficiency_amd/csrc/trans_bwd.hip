@@ -393,9 +393,14 @@ extern "C" int lfsr_window_attn_bwd(const float* qk, int qk_stride, int q_choff,
 }
 
 namespace {
-// Y (N columns) = X (M dense rows of cin) . WT, then * (Mk > 0 ? 1 : 0), then + R1: the 1x1 data gradient of the drivers and of lfsr_linear_dgrad
+// Y (N columns) = X (M dense rows of cin) . WT, then * (Mk > 0 ? 1 : 0), then + R1: the 1x1 data gradient of the drivers and of lfsr_linear_dgrad.  Under
+// lfsr_set_lin_grad_arithmetic(LFSR_LIN_GRAD_ARITH_BF16): lin_dgrad_bf16.hip where it covers the call (N in {64, 128, 256}, 16-B aligned operands)
 int dgemm_launch(const float* X, int cin, const float* WT, float* Y, int ys, const float* R1, int r1s, const float* Mk, int mks, int M, int N, int A, int h, int w,
                  int S, hipStream_t st) {
+  if (lfsr_lin_grad_arith_bf16()) {
+    const int rc = lfsr_lin_dgrad_bf16_launch(X, cin, WT, Y, ys, R1, r1s, Mk, mks, M, N, st);
+    if (rc != LFSR_E_ARG) return rc;
+  }
   GemmArgs p{};
   p.X = X; p.x_stride = cin; p.Wp = WT; p.Y = Y; p.y_stride = ys; p.R1 = R1; p.r1_stride = r1s; p.Mk = Mk; p.mk_stride = mks; p.mk_slope = 0.0f;
   p.M = M; p.N = N; p.Npad = npad32(N); p.A = A; p.H = h; p.W = w; p.ntaps = 1; p.CH = N; p.slope = 1.0f; p.S = S;
@@ -430,6 +435,53 @@ extern "C" int lfsr_linear_dgrad(const float* dy, int cout, const float* wT_pack
   return dgemm_launch(dy, cout, wT_packed, dx, dx_stride, r1, r1 ? r1_stride : 0, act, act ? act_stride : 0, (int)M, cin, 1, 1, 1, 1, lfsr_stream(stream));
 }
 
+// ---- a linear's weight gradient: one launcher for the operator and the drivers ------------------------------------------------------------
+static bool lin_wgrad_shape_ok(int cout, int cin) {
+  return (cout == 64 || cout == 128 || cout == 256 || cout == 576 || cout == 1024) && (cin == 64 || cin == 128 || cin == 256);
+}
+
+// the default's slabs of one 64-row slice (every slice reuses them)
+size_t lfsr_linear_wgrad_part_floats(long long M, int cout, int cin) {
+  if (!lin_wgrad_shape_ok(cout, cin) || M <= 0 || M > 0x7fffffffLL - 128) return 0;
+  const size_t slice = lfsr_wgrad_partial_floats((int)M, 1, 64, cin);
+  const size_t one = (size_t)lfsr_lin_wgrad_bf16_slabs_per_block(cout, cin) * cout * cin;      // the bf16 form's smallest grid
+  return std::max(slice, one);
+}
+
+int lfsr_linear_wgrad_run(const float* dy, int dy_stride, const float* x, int x_stride, float* dw, float* part, size_t part_floats, long long M, int cout, int cin,
+                          int accumulate, int A, int h, int w, hipStream_t st) {
+  const size_t need = lfsr_linear_wgrad_part_floats(M, cout, cin);
+  if (!need) return LFSR_E_ARG;
+  if (part_floats < need) return LFSR_E_WS;
+  if (lfsr_lin_grad_arith_bf16()) {
+    const int blocks = lfsr_lin_wgrad_bf16_blocks(M, cout, cin, part_floats);
+    LFSR_RC(lfsr_lin_wgrad_bf16_launch(dy, dy_stride, x, x_stride, part, M, cout, cin, blocks, st));
+    return lfsr_wgrad_reduce(part, blocks * lfsr_lin_wgrad_bf16_slabs_per_block(cout, cin), nullptr, 0, dw, cout, cin, 1, 0, 0, accumulate, 0, 0, st);
+  }
+  for (int n0 = 0; n0 < cout; n0 += 64) {
+    LFSR_RC(lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_SAME, dy, dy_stride, n0, x, x_stride, 0, part, (int)M, 64, cin, A, h, w, 1, st));
+    LFSR_RC(lfsr_wgrad_reduce(part, lfsr_wgrad_splits((int)M, 1, cin), nullptr, 0, dw + (size_t)n0 * cin, 64, cin, 1, 0, 0, accumulate, 0, 0, st));
+  }
+  return LFSR_OK;
+}
+
+// one size for both modes: the default's slabs, or the bf16 form's full grid where that is more
+extern "C" size_t lfsr_linear_wgrad_workspace_floats(long long M, int cout, int cin) {
+  const size_t need = lfsr_linear_wgrad_part_floats(M, cout, cin);
+  if (!need) return 0;
+  const size_t full = (size_t)lfsr_lin_wgrad_bf16_blocks(M, cout, cin, (size_t)-1) * lfsr_lin_wgrad_bf16_slabs_per_block(cout, cin) * cout * cin;
+  return std::max(need, full);
+}
+
+extern "C" int lfsr_linear_wgrad(const float* dy, int dy_stride, const float* x, int x_stride, float* dw, float* workspace, size_t workspace_floats, long long M,
+                                 int cout, int cin, int accumulate, void* stream) {
+  if (!dy || !x || !dw || !workspace || M <= 0 || M > 0x7fffffffLL - 128 || !lin_wgrad_shape_ok(cout, cin)) return LFSR_E_ARG;
+  if (dy_stride < cout || x_stride < cin || ((dy_stride | x_stride) & 3)) return LFSR_E_ARG;
+  if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dw | (uintptr_t)workspace) & 15) return LFSR_E_ARG;
+  if (workspace_floats < lfsr_linear_wgrad_workspace_floats(M, cout, cin)) return LFSR_E_WS;
+  return lfsr_linear_wgrad_run(dy, dy_stride, x, x_stride, dw, workspace, workspace_floats, M, cout, cin, accumulate ? 1 : 0, 1, 1, 1, lfsr_stream(stream));
+}
+
 extern "C" size_t lfsr_up_tail_bwd_workspace_floats(void) { return (size_t)LFSR_RED_BLOCKS * 9 * 64; }
 
 extern "C" int lfsr_up_tail_bwd(const float* dout, const float* w3, const float* hr, float* du, float* dw3, float* workspace, size_t workspace_floats, int B, int A,
@@ -457,7 +509,7 @@ size_t lfsr_trans_wgrad_partial_max(int B, int A, int h, int w) {
   const size_t npix = (size_t)B * A * A * h * w;
   size_t m = lfsr_wgrad_partial_floats((int)npix, 9, 64, 64);
   for (int K : {16, 64, 128, 256}) m = std::max(m, lfsr_wgrad_partial_floats((int)npix, 1, 64, K));
-  return m;
+  return std::max(m, (size_t)1024 * 64);      // lin_wgrad_bf16.hip's smallest grid at the widest linear (upsampling.0 at scale 4); more than the rest only up to 256 pixels
 }
 
 float* LfsrTransBwd::G(const std::string& k) const { return gbase + P.grad_off(k); }
@@ -473,8 +525,7 @@ int LfsrTransBwd::wgrad(int xm, const float* Gr, int gs, int go, const float* X,
 }
 
 int LfsrTransBwd::wgrad_lin(const float* Gr, int gs, int O, const float* X, int xs, int K, float* dW) const {
-  for (int n0 = 0; n0 < O; n0 += 64) LFSR_RC(wgrad(LFSR_IN_SAME, Gr, gs, n0, X, xs, npix, 64, K, 1, dW + (size_t)n0 * K, 0));
-  return LFSR_OK;
+  return lfsr_linear_wgrad_run(Gr, gs, X, xs, dW, ws.part, lfsr_trans_wgrad_partial_max(B, A, h, w), npix, O, K, 0, A, h, w, st);
 }
 
 int LfsrTransBwd::ew(int C, const float* a, const float* b, const float* mk, float slope, float* d) const {
