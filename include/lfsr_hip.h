@@ -547,7 +547,8 @@ int lfsr_get_arithmetic(void);
  *  - the weight gradient of that conv where it runs on the tile kernel (lfsr_conv3x3_wgrad and lfsr_distgssr_backward): dy and x are rounded to bf16, products
  *    exact, fp32 accumulation into the same per-block partial slabs, the same reduction.  lfsr_conv3x3_wgrad_workspace_floats does not depend on the mode.
  * What does not change: gradients, activations and slabs stay fp32 in memory; the forward (it does not read this switch); the EPI, angular, fuse.0, 1x1,
- * 128 -> 64 and up-sampling gradients; the transformers' GEMM gradients (they have a switch of their own: lfsr_set_lin_grad_arithmetic below); unaligned data-gradient operands (fp32 gather-GEMM); strides the bf16 weight-gradient
+ * 128 | 320 -> 64 weight gradients (LF_InterNet's wide convs: they have a switch of their own, lfsr_set_wide_train_arithmetic below; their data gradients are
+ * 64 -> 64 calls of the dispatcher and do follow this mode) and up-sampling gradients; the transformers' GEMM gradients (they have a switch of their own: lfsr_set_lin_grad_arithmetic below); unaligned data-gradient operands (fp32 gather-GEMM); strides the bf16 weight-gradient
  * kernel does not cover (the default kernel); and the 3x3 weight gradients of the EPIT, LFT and LF_InterNet drivers, which run through the generic gather
  * weight-gradient kernel.  bf16 keeps fp32's exponent range: no loss scaling is needed.  Both kernels are free of atomics: two runs give the same bits, and an
  * image's data gradient does not depend on how many images the launch has.  Parity with the reference's fp32 gradients is claimed only in the default mode
@@ -616,8 +617,8 @@ int lfsr_get_ang_arithmetic(void);
  * while a block stages it, so the pack, lfsr_internet_packed_bytes and the workspace do not change.  The products are exact; accumulation, LeakyReLU, the
  * residual add and stores are fp32; x, r1 and y stay fp32 in memory.  The argument checks and return codes are the default's.  What follows: lfsr_conv3x3_wide_fwd
  * and, through its launcher, the sixteen SpaConvSq (128 -> 64) and the SpaBottle (320 -> 64) of lfsr_internet_forward: 82 % of that forward's arithmetic.  What
- * does not, with its bits unchanged: LFSR_ARITH_F32 (which wins), lfsr_internet_forward_train and lfsr_internet_backward (the training forward launches the
- * gather-GEMM itself and reads no switch: a training step is the same in either mode), LF_InterNet's other operators (its 128 -> 64 angular squeeze follows
+ * does not, with its bits unchanged: LFSR_ARITH_F32 (which wins), lfsr_internet_forward_train and lfsr_internet_backward (the training forward does not read
+ * this switch: a training step is the same in either mode; training has its own, lfsr_set_wide_train_arithmetic below), LF_InterNet's other operators (its 128 -> 64 angular squeeze follows
  * lfsr_set_gemm_arithmetic), lfsr_conv3x3_fwd, lfsr_conv3x3_n_fwd, lfsr_angconv3x3_fwd, and DistgSSR, EPIT, LFT and LFSSR.  No atomics: chunks, taps and channels
  * run in one fixed order, two runs give the same bits, and an image's result does not depend on n_img.  Parity with the reference's fp32 results is claimed only
  * in the default mode (error against fp64 under the mode: below torch.autocast(bfloat16)'s, tests/test_gpu_wide_bf16.py). */
@@ -669,6 +670,40 @@ int lfsr_get_lin_grad_arithmetic(void);
 size_t lfsr_linear_wgrad_workspace_floats(long long M, int cout, int cin);
 int lfsr_linear_wgrad(const float* dy, int dy_stride, const float* x, int x_stride, float* dw, float* workspace, size_t workspace_floats, long long M, int cout,
                       int cin, int accumulate, void* stream);
+
+/* ---- arithmetic of LF_InterNet's wide per-view 3x3 convs IN TRAINING: an eighth process-wide selection, independent of the seven above, read at every launch ----
+ * LFSR_WIDE_TRAIN_ARITH_DEFAULT: every kernel as it is, bit for bit.
+ * LFSR_WIDE_TRAIN_ARITH_BF16_WGRAD: opt-in.  The weight gradient of the wide convs (SpaConvSq 128 -> 64, BottleNeck.SpaBottle 320 -> 64), lfsr_conv3x3_wide_wgrad
+ * (below), rounds dy and x to bf16 (nearest even) on their way into LDS; the products are exact (v_mfma_f32_32x32x16_bf16, the pixel index as the MFMA's K),
+ * accumulation is fp32 into per-block partial slabs, and the fixed-order reduction of the default sums them (csrc/wgrad_wide_bf16.hip: the dy tile is staged once
+ * for every 64-channel chunk of x a block owns).  forward_train as it is.
+ * LFSR_WIDE_TRAIN_ARITH_BF16: that, and lfsr_internet_forward_train computes ReLU(SpaConvSq) and ReLU(SpaBottle) with the kernel of LFSR_WIDE_ARITH_BF16
+ * (csrc/conv3x3_wide_bf16.hip); the residual add stays the separate fp32 launch, so the output equals lfsr_internet_forward's under LFSR_WIDE_ARITH_BF16 bit for bit.
+ * What follows: lfsr_conv3x3_wide_wgrad, the seventeen wide weight gradients of lfsr_internet_backward (modes 1 and 2) and the seventeen wide convs of
+ * lfsr_internet_forward_train (mode 2).  What does not, with its bits unchanged: the wide convs' data gradients (64 -> 64 calls that follow
+ * lfsr_set_grad_arithmetic alone), every other operator of the LF_InterNet training step, lfsr_internet_forward and lfsr_conv3x3_wide_fwd (they follow
+ * lfsr_set_wide_arithmetic, which in turn does not reach training), spans of 2 GiB or more (the default kernel), and DistgSSR, EPIT, LFT and LFSSR (LFT's 64 -> 64
+ * position conv runs the same generic weight-gradient kernel and does not read this switch).  LFSR_ARITH_F32 wins for the forward half of mode 2 and has no
+ * bearing on the weight gradients, as for the other gradient switches.  lfsr_conv3x3_wide_wgrad_workspace_floats and lfsr_internet_train_workspace_bytes do not
+ * depend on the mode.  Gradients, activations and slabs stay fp32 in memory; bf16 keeps fp32's exponent range: no loss scaling is needed.  No atomics: slab order
+ * and block count are fixed by the geometry alone, two runs give the same bits.  Parity with the reference's fp32 gradients is claimed only in the default mode
+ * (error against fp64 autograd under the modes: below torch.autocast(bfloat16)'s, tests/test_gpu_wide_train_bf16.py). */
+#define LFSR_WIDE_TRAIN_ARITH_DEFAULT 0
+#define LFSR_WIDE_TRAIN_ARITH_BF16_WGRAD 1
+#define LFSR_WIDE_TRAIN_ARITH_BF16 2
+int lfsr_set_wide_train_arithmetic(int mode);   /* LFSR_E_ARG for any other value, nothing changed */
+int lfsr_get_wide_train_arithmetic(void);
+/* Weight gradient of the wide per-view 3x3 conv (zero pad 1, cin in {128, 320} -> 64):  dw[n][k][tap] (=, or += if accumulate) the sum over the pixels p of the
+ * n_img views of dy[p][n] x[p + shift(tap)][k], zero outside the view; dw (64, cin, 3, 3) in the raw PyTorch layout, dy and x VCL rows.  workspace:
+ * lfsr_conv3x3_wide_wgrad_workspace_floats(cin, n_img, h, w) floats of partial slabs (0 for a refused shape; the same in every mode).  LFSR_E_ARG before any launch,
+ * nothing written, in every mode: NULL dy / x / dw / workspace, cin outside {128, 320}, non-positive n_img / h / w, x_stride < x_choff + cin,
+ * dy_stride < dy_choff + 64, a negative stride or offset or one that is no multiple of 4, dy, x, dw or workspace off the 16-byte grid, an operand span
+ * (n_img h w stride floats) of 2 GiB or more; LFSR_E_WS for a short workspace.  Then the switch above selects the kernel.  Default: what lfsr_internet_backward
+ * has always run, the generic gather weight-gradient kernel over (row splits, 9 taps, cin / 64 column tiles) and its reduction.  Modes 1 and 2:
+ * csrc/wgrad_wide_bf16.hip and the same reduction.  No float atomics in either: two runs give the same bits. */
+size_t lfsr_conv3x3_wide_wgrad_workspace_floats(int cin, int n_img, int h, int w);
+int lfsr_conv3x3_wide_wgrad(const float* dy, int dy_stride, int dy_choff, const float* x, int x_stride, int x_choff, int cin,
+                            float* dw, float* workspace, size_t workspace_floats, int n_img, int h, int w, int accumulate, void* stream);
 
 /* ---- operator-level timing hooks (measurement aid; the reference times whole forwards only: check_efficiency_official.py:306-330) ----
  * lfsr_op_profile(1): from now on every instrumented operator entry point brackets its launches with a hipEvent pair on its launch stream (and any

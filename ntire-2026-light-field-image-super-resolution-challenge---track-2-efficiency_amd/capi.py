@@ -106,7 +106,11 @@ SIGNATURES = {
     "lfsr_get_lin_grad_arithmetic": (c_i, []),
     "lfsr_linear_wgrad_workspace_floats": (c_sz, [C.c_longlong, c_i, c_i]),
     "lfsr_linear_wgrad": (c_i, [c_p, c_i, c_p, c_i, c_p, c_p, c_sz, C.c_longlong, c_i, c_i, c_i, c_p]),
-    "lfsr_conv3x3_wide_fwd": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
+    "lfsr_set_wide_train_arithmetic": (c_i, [c_i]),
+    "lfsr_get_wide_train_arithmetic": (c_i, []),
+    "lfsr_conv3x3_wide_wgrad_workspace_floats": (c_sz, [c_i, c_i, c_i, c_i]),
+    "lfsr_conv3x3_wide_wgrad": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_sz, c_i, c_i, c_i, c_i, c_p]),
+    "lfsr_conv3x3_wide_fwd":(c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
     "lfsr_op_profile": (c_i, [c_i]),
     "lfsr_op_profile_read": (C.c_longlong, [C.c_char_p, c_sz]),
     "lfsr_distgssr_profile": (c_i, [c_p, c_i]),
@@ -292,6 +296,21 @@ def set_lin_grad_arithmetic(mode):
 def get_lin_grad_arithmetic():
     """lfsr_get_lin_grad_arithmetic: the mode the next lfsr_linear_wgrad / lfsr_linear_dgrad launch runs in"""
     return int(load().lfsr_get_lin_grad_arithmetic())
+
+
+WIDE_TRAIN_ARITH_DEFAULT, WIDE_TRAIN_ARITH_BF16_WGRAD, WIDE_TRAIN_ARITH_BF16 = 0, 1, 2
+
+
+def set_wide_train_arithmetic(mode):
+    """lfsr_set_wide_train_arithmetic: WIDE_TRAIN_ARITH_DEFAULT (LF_InterNet's wide per-view 3x3 convs in training as they are), WIDE_TRAIN_ARITH_BF16_WGRAD
+    (lfsr_conv3x3_wide_wgrad, and with it the seventeen wide weight gradients of the backward, rounds its operands to bf16, fp32 accumulation) or
+    WIDE_TRAIN_ARITH_BF16 (that, and forward_train's wide convs on bf16 operands); process-wide, independent of the other seven switches"""
+    check(load().lfsr_set_wide_train_arithmetic(int(mode)), "set_wide_train_arithmetic")
+
+
+def get_wide_train_arithmetic():
+    """lfsr_get_wide_train_arithmetic: the mode the next lfsr_conv3x3_wide_wgrad / lfsr_internet_forward_train / lfsr_internet_backward launch runs in"""
+    return int(load().lfsr_get_wide_train_arithmetic())
 
 
 def op_profile(enable):
@@ -910,6 +929,19 @@ def linear_wgrad(dy, x, cout, cin, dw=None):
     ws = torch.empty(lib.lfsr_linear_wgrad_workspace_floats(M, cout, cin), dtype=torch.float32, device=dy.device)
     check(lib.lfsr_linear_wgrad(dev_ptr(dy), dy.shape[1], dev_ptr(x), x.shape[1], dev_ptr(dw), dev_ptr(ws), ws.numel(), M, cout, cin, int(acc), stream_ptr()),
           "linear_wgrad")
+    return dw
+
+
+def conv3x3_wide_wgrad(dy, x, cin, n_img, h, w, dw=None, dy_choff=0, x_choff=0):
+    """lfsr_conv3x3_wide_wgrad: dw (64, cin, 3, 3) = the weight gradient of the per-view 3x3 conv cin in {128, 320} -> 64 from VCL rows dy (n_img h w, >= dy_choff + 64)
+    and x (n_img h w, >= x_choff + cin); dw given: accumulated into.  Follows set_wide_train_arithmetic."""
+    lib = load()
+    acc = dw is not None
+    if dw is None:
+        dw = torch.empty((64, cin, 3, 3), dtype=torch.float32, device=dy.device)
+    ws = torch.empty(lib.lfsr_conv3x3_wide_wgrad_workspace_floats(cin, n_img, h, w), dtype=torch.float32, device=dy.device)
+    check(lib.lfsr_conv3x3_wide_wgrad(dev_ptr(dy), dy.shape[1], dy_choff, dev_ptr(x), x.shape[1], x_choff, cin, dev_ptr(dw), dev_ptr(ws), ws.numel(),
+                                      n_img, h, w, int(acc), stream_ptr()), "conv3x3_wide_wgrad")
     return dw
 
 

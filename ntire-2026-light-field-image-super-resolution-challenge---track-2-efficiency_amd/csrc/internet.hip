@@ -81,7 +81,8 @@ int lfsr_internet_copy64(const float* src, int s_stride, int s_choff, float* dst
 
 // The wide per-view 3x3 conv (SpaConvSq 128 -> 64, SpaBottle 320 -> 64) as lfsr_set_wide_arithmetic selects it, read at every launch.  Default, or LFSR_ARITH_F32
 // (which wins): the gather-GEMM on the fp32 MFMA pipe, the launch lfsr_internet_forward has always issued.  LFSR_WIDE_ARITH_BF16: conv3x3_wide_bf16.hip.
-// lfsr_internet_forward_train (internet_train.hip) does not come through here: it launches the gather-GEMM itself and reads no switch.
+// lfsr_internet_forward_train (internet_train.hip) does not come through here: it launches the gather-GEMM itself, or the bf16 kernel under
+// lfsr_set_wide_train_arithmetic(LFSR_WIDE_TRAIN_ARITH_BF16), and does not read this switch.
 int lfsr_conv3x3_wide_run(const float* x, int x_stride, int x_choff, int cin, const float* w_packed, float* y, int y_stride, int y_choff, const float* r1,
                           int r1_stride, int r1_choff, int n_img, int h, int w, float slope, int A, hipStream_t st) {
   if (lfsr_wide_arith_bf16() && !lfsr_arith_f32())

@@ -10,6 +10,11 @@
 // Backward: every data gradient is a gather-GEMM over transposed packs (gemm_gather_kernel.h) or the 64 -> 64 3x3 data-gradient kernel
 // (on the 64-channel input slices of SpaConvSq / SpaBottle); every weight gradient is the two-pass partial-slab reduction of wgrad.hip
 // (no float atomics: bitwise reproducible).  ReconBlock's folded conv is differentiated through the fold (k_fold_bwd).
+//
+// lfsr_set_wide_train_arithmetic (read at every launch) reaches the wide per-view 3x3 convs, the sixteen SpaConvSq (128 -> 64) and SpaBottle (320 -> 64), and nothing
+// else: in modes 1 and 2 their weight gradients run wgrad_wide_bf16.hip through lfsr_wide_wgrad_run, the launcher lfsr_conv3x3_wide_wgrad shares; in mode 2 the
+// training forward computes ReLU(SpaConvSq) and ReLU(SpaBottle) with conv3x3_wide_bf16.hip (unless LFSR_ARITH_F32 is set) and keeps the separate residual add,
+// because the backward reads the ReLU results as masks.  lfsr_set_wide_arithmetic is not read here.
 #include <string>
 #include <vector>
 
@@ -154,11 +159,11 @@ size_t partial_floats(int A, int B, int h, int w) {
   size_t m = 0;
   auto up = [&](size_t v) { if (v > m) m = v; };
   up(lfsr_wgrad_partial_floats(npix, 9, 16, 64));         // ReconBlock fold
-  up(lfsr_wgrad_partial_floats(npix, 9, 64, 64 * (NG + 1)));   // SpaBottle
+  up(lfsr_wide_wgrad_part_floats(64 * (NG + 1), B * AA, h, w));   // SpaBottle: the generic kernel's slabs or wgrad_wide_bf16.hip's, whichever are more, in every mode
   up(lfsr_wgrad_partial_floats(nlr, AA, 64, 64));          // Ang2Spa / Spa2Ang
   up(lfsr_wgrad_partial_floats(nlr, 1, 64, 64 * NG));      // AngBottle
   up(lfsr_wgrad_partial_floats(nlr, 1, 64, 128));          // AngConvSq
-  up(lfsr_wgrad_partial_floats(npix, 9, 64, 128));         // SpaConvSq
+  up(lfsr_wide_wgrad_part_floats(128, B * AA, h, w));      // SpaConvSq: likewise
   up(lfsr_wgrad_partial_floats(npix, 1, 64, 16));          // SpaFE
   up(lfsr_wgrad_partial_floats(nlr, 1, 64, angfe_kpad(A)));   // AngFE
   return m;
@@ -201,6 +206,26 @@ std::string chain_key(int g, int l, const char* leaf) {
 
 }  // namespace
 
+size_t lfsr_wide_wgrad_part_floats(int cin, int n_img, int h, int w) {
+  const int blocks = lfsr_wgrad_wide_bf16_blocks(cin, n_img, h, w);
+  if (blocks <= 0 || (long long)n_img * h * w >= (1LL << 31)) return 0;
+  const size_t generic = lfsr_wgrad_partial_floats(n_img * h * w, 9, 64, cin), tile = (size_t)blocks * 9 * 64 * cin;
+  return generic > tile ? generic : tile;
+}
+
+int lfsr_wide_wgrad_run(const float* dy, int dy_stride, int dy_choff, const float* x, int x_stride, int x_choff, int cin, float* dw, float* part,
+                        int n_img, int h, int w, int accumulate, int A, hipStream_t st) {
+  if (lfsr_wide_train_arith() != LFSR_WIDE_TRAIN_ARITH_DEFAULT) {
+    const int rc = lfsr_wgrad_wide_bf16_launch(dy, dy_stride, dy_choff, x, x_stride, x_choff, cin, part, n_img, h, w, st);
+    if (rc == LFSR_OK) return lfsr_wgrad_reduce(part, lfsr_wgrad_wide_bf16_blocks(cin, n_img, h, w), nullptr, 0, dw, 64, cin, 9, 0, 0, accumulate, 0, 0, st);
+    if (rc != LFSR_E_ARG) return rc;   // LFSR_E_ARG: not covered, nothing launched
+  }
+  const int M = n_img * h * w;
+  int r = lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_CONV3, dy, dy_stride, dy_choff, x, x_stride, x_choff, part, M, 64, cin, A, h, w, 9, st);
+  if (!r) r = lfsr_wgrad_reduce(part, lfsr_wgrad_splits(M, 9, cin), nullptr, 0, dw, 64, cin, 9, 0, 0, accumulate, 0, 0, st);
+  return r;
+}
+
 int lfsr_pack_T_from_fwd(const float* Wp, float* out, int T, int Npad_in, int C, int O, int k0, int Kc, int flip, hipStream_t st) {
   hipLaunchKernelGGL(k_pack_T_from_fwd, dim3(lfsr_cap_grid((long long)T * Kc * O)), dim3(256), 0, st, Wp, out, T, Npad_in, C, O, k0, Kc, flip);
   LFSR_CHECK_LAUNCH();
@@ -208,6 +233,22 @@ int lfsr_pack_T_from_fwd(const float* Wp, float* out, int T, int Npad_in, int C,
 }
 
 extern "C" {
+
+size_t lfsr_conv3x3_wide_wgrad_workspace_floats(int cin, int n_img, int h, int w) { return lfsr_wide_wgrad_part_floats(cin, n_img, h, w); }
+
+int lfsr_conv3x3_wide_wgrad(const float* dy, int dy_stride, int dy_choff, const float* x, int x_stride, int x_choff, int cin, float* dw, float* workspace,
+                            size_t workspace_floats, int n_img, int h, int w, int accumulate, void* stream) {
+  LfsrOpTimer op_t("conv3x3_wide_wgrad", cin, h * w, lfsr_stream(stream));
+  if (!dy || !x || !dw || !workspace || (cin != 128 && cin != 320) || n_img <= 0 || h <= 0 || w <= 0) return LFSR_E_ARG;
+  if (x_choff < 0 || dy_choff < 0 || x_stride < x_choff + cin || dy_stride < dy_choff + 64 || ((x_stride | x_choff | dy_stride | dy_choff) & 3)) return LFSR_E_ARG;
+  if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dw | (uintptr_t)workspace) & 15) return LFSR_E_ARG;
+  const long long rows = (long long)n_img * h * w, lim = (1LL << 31) / 4;   // an operand span of 2 GiB or more
+  if (rows * x_stride >= lim || rows * dy_stride >= lim) return LFSR_E_ARG;
+  const size_t need = lfsr_wide_wgrad_part_floats(cin, n_img, h, w);
+  if (!need) return LFSR_E_ARG;
+  if (workspace_floats < need) return LFSR_E_WS;
+  return lfsr_wide_wgrad_run(dy, dy_stride, dy_choff, x, x_stride, x_choff, cin, dw, workspace, n_img, h, w, accumulate ? 1 : 0, 1, lfsr_stream(stream));
+}
 
 size_t lfsr_internet_num_params(const lfsr_internet* c) { return c ? c->P.num_params() : 0; }
 
@@ -287,6 +328,14 @@ int lfsr_internet_forward_train(lfsr_internet* c, const float* x, float* out, in
   hipLaunchKernelGGL(k_pack_fold_T, dim3((9 * 64 * 16 + 255) / 256), dim3(256), 0, st, P.packed + c->off_wf, t.FoldT, c->s * c->s);
   LFSR_CHECK_LAUNCH();
 
+  // ReLU(wide conv) into its saved buffer: conv3x3_wide_bf16.hip under LFSR_WIDE_TRAIN_ARITH_BF16 (LFSR_ARITH_F32 wins), else the fp32 gather-GEMM as ever
+  // (a concat of 2 GiB or more keeps the gather-GEMM and its 64-bit addresses)
+  const bool wide_bf16 = lfsr_wide_train_arith() == LFSR_WIDE_TRAIN_ARITH_BF16 && !lfsr_arith_f32() && npix * cs_stride * 4 < (1LL << 31);
+  auto wide_relu = [&](const float* X, int xs, int cin, const float* Wp, float* Y) -> int {
+    if (wide_bf16) return lfsr_conv3x3_wide_bf16_launch(X, xs, 0, cin, Wp, Y, 64, 0, nullptr, 0, 0, B * AA, h, w, 0.0f, st);
+    if (cin == 128) return gemm(launch_gemm<IN_CONV3, OUT_SAME, 128, 2>, X, xs, 0, Wp, Y, 64, 0, nullptr, 0, 0, (int)npix, 64, 9, 64, 0.0f);
+    return gemm(launch_gemm<IN_CONV3, OUT_SAME, 320, 2>, X, xs, 0, Wp, Y, 64, 0, nullptr, 0, 0, (int)npix, 64, 9, 64, 0.0f);
+  };
   // ---- the forward's launches (internet.hip), every layer into its own buffers
   LFSR_RC(lfsr_internet_angfe(x, P.w("AngFE.0.weight"), t.Ar[0], 128, 0, B, A, h, w, st));
   LFSR_RC(lfsr_initconv_fwd(x, P.w("SpaFE.0.weight"), t.S[0], 128, 0, B, A, h, w, stream));
@@ -297,7 +346,7 @@ int lfsr_internet_forward_train(lfsr_internet* c, const float* x, float* out, in
       LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, t.Ar[i], 128, 0, P.w(chain_key(g, l, "Ang2Spa.0.weight")), t.S[i], 128, 64, nullptr, 0, 0, (int)nlr, AA * 64, 1, 64, 1.0f));
       LFSR_RC(lfsr_linear_fwd(t.Ar[i], 128, 0, 128, P.w(chain_key(g, l, "AngConvSq.weight")), nullptr, t.Ar[i], 128, 0, t.Ar[i + 1], 128, 0, nlr, 64, 0.0f, stream));
       LFSR_RC(lfsr_linear_fwd(t.Ar[i], 128, 0, 128, P.w(chain_key(g, l, "AngConvSq.weight")), nullptr, nullptr, 0, 0, t.RA[i], 64, 0, nlr, 64, 0.0f, stream));
-      LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 128, 2>, t.S[i], 128, 0, P.w(chain_key(g, l, "SpaConvSq.weight")), t.RS[i], 64, 0, nullptr, 0, 0, (int)npix, 64, 9, 64, 0.0f));
+      LFSR_RC(wide_relu(t.S[i], 128, 128, P.w(chain_key(g, l, "SpaConvSq.weight")), t.RS[i]));
       LFSR_RC(ew64(t.RS[i], 64, 0, t.S[i], 128, 0, nullptr, 0, 0, t.S[i + 1], 128, 0, npix, st));
     }
     LFSR_RC(lfsr_internet_copy64(t.Ar[(g + 1) * NL], 128, 0, t.CA, ca_stride, 64 * g, nlr, st));
@@ -305,7 +354,7 @@ int lfsr_internet_forward_train(lfsr_internet* c, const float* x, float* out, in
   }
   LFSR_RC(lfsr_linear_fwd(t.CA, ca_stride, 0, 64 * NG, P.w("BottleNeck.AngBottle.weight"), nullptr, nullptr, 0, 0, t.BA, 64, 0, nlr, 64, 0.0f, stream));
   LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_VIEWS, 64, 2>, t.BA, 64, 0, P.w("BottleNeck.Ang2Spa.0.weight"), t.CS, cs_stride, 64 * NG, nullptr, 0, 0, (int)nlr, AA * 64, 1, 64, 1.0f));
-  LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_SAME, 320, 2>, t.CS, cs_stride, 0, P.w("BottleNeck.SpaBottle.weight"), t.RB, 64, 0, nullptr, 0, 0, (int)npix, 64, 9, 64, 0.0f));
+  LFSR_RC(wide_relu(t.CS, cs_stride, cs_stride, P.w("BottleNeck.SpaBottle.weight"), t.RB));
   LFSR_RC(ew64(t.RB, 64, 0, t.S[0], 128, 0, nullptr, 0, 0, t.BO, 64, 0, npix, st));
   LFSR_RC(gemm(launch_gemm<IN_CONV3, OUT_PS_HR, 64, 1>, t.BO, 64, 0, P.packed + c->off_wf, out, 1, 0, nullptr, 0, 0, (int)npix, c->s * c->s, 9, 1, 1.0f));
   return LFSR_OK;
@@ -340,6 +389,8 @@ int lfsr_internet_backward(lfsr_internet* c, const float* x, const float* dout, 
     if (!r) r = lfsr_wgrad_reduce(t.P, lfsr_wgrad_splits(M, ntaps, K), nullptr, 0, dW, O, C, T, perm, ch, 0, c_valid, chunk, st);
     return r;
   };
+  // the wide convs' weight gradients follow lfsr_set_wide_train_arithmetic (lfsr_wide_wgrad_run: the default is the generic launch and reduce above)
+  auto wgrad_wide = [&](const float* X, int xs, int cin, float* dW) -> int { return lfsr_wide_wgrad_run(t.dZ, 64, 0, X, xs, 0, cin, dW, t.P, nimg, h, w, 0, A, st); };
   auto dgrad3 = [&](const float* dy, const float* wT, float* dx, int dxs, int dxo, const float* r1) -> int {
     return lfsr_conv3x3_bwd_data(dy, 64, 0, wT, dx, dxs, dxo, r1, 64, 0, nullptr, 0, 0, 1.0f, nimg, h, w, st);
   };
@@ -355,7 +406,7 @@ int lfsr_internet_backward(lfsr_internet* c, const float* x, const float* dout, 
 
   // ---- BottleNeck: BO = ReLU(SpaBottle(CS)) + xs, CS[:, 256:320] = PS(Ang2Spa(a)), a = ReLU(AngBottle(CA)) --------------------------------
   LFSR_RC(ew64(t.dBO, 64, 0, nullptr, 0, 0, t.RB, 64, 0, t.dZ, 64, 0, npix, st));
-  LFSR_RC(wgrad(LFSR_IN_SAME, LFSR_IN_CONV3, t.dZ, 64, 0, t.CS, cs_stride, 0, npix, 64, cs_stride, 9, G("BottleNeck.SpaBottle.weight"), 64, cs_stride, 9, 0, 0, 0, 0));
+  LFSR_RC(wgrad_wide(t.CS, cs_stride, cs_stride, G("BottleNeck.SpaBottle.weight")));
   for (int j = 0; j <= NG; ++j) LFSR_RC(dgrad3(t.dZ, t.SbT[j], t.dCS, cs_stride, 64 * j, nullptr));
   LFSR_RC(gemm(launch_gemm<IN_ANG, OUT_SAME, 64, 2>, t.dCS, cs_stride, 64 * NG, t.BA2sT, t.dZa, 64, 0, nullptr, 0, 0, t.BA, 64, 0, nlr, 64, AA, 64));
   LFSR_RC(wgrad(LFSR_IN_ANG, LFSR_IN_SAME, t.dCS, cs_stride, 64 * NG, t.BA, 64, 0, nlr, 64, 64, AA, G("BottleNeck.Ang2Spa.0.weight"), AA * 64, 64, AA, 1, 64, 0, 1));
@@ -384,7 +435,7 @@ int lfsr_internet_backward(lfsr_internet* c, const float* x, const float* dout, 
       LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dzA, 64, 0, t.AcT[i], dxa, 64, 0, dOa, 64, 0, nullptr, 0, 0, nlr, 64, 1, 64));
       LFSR_RC(gemm(launch_gemm<IN_SAME, OUT_SAME, 64, 2>, t.dzA, 64, 0, t.AcT[i] + 64 * 64, t.dG2, 64, 0, nullptr, 0, 0, t.Ar[i], 128, 64, nlr, 64, 1, 64));
       // SpaConvSq: dxs = conv3^T(dzS; W[:, :64]) + dOs ; dspa2 = conv3^T(dzS; W[:, 64:])
-      LFSR_RC(wgrad(LFSR_IN_SAME, LFSR_IN_CONV3, t.dZ, 64, 0, t.S[i], 128, 0, npix, 64, 128, 9, G(chain_key(g, l, "SpaConvSq.weight")), 64, 128, 9, 0, 0, 0, 0));
+      LFSR_RC(wgrad_wide(t.S[i], 128, 128, G(chain_key(g, l, "SpaConvSq.weight"))));
       LFSR_RC(dgrad3(t.dZ, t.ScLo[i], dxs, 64, 0, dOs));
       LFSR_RC(dgrad3(t.dZ, t.ScHi[i], t.dSP, 64, 0, nullptr));
       // Ang2Spa: spa2 = PS(W xa) -> dxa += sum over the views (IN_ANG gather of dspa2)

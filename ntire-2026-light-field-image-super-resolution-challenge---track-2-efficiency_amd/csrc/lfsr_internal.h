@@ -293,6 +293,18 @@ int lfsr_lin_dgrad_bf16_launch(const float* dy, int cout, const float* wT_packed
 size_t lfsr_linear_wgrad_part_floats(long long M, int cout, int cin);   // what either mode needs at least; 0: shape not covered
 int lfsr_linear_wgrad_run(const float* dy, int dy_stride, const float* x, int x_stride, float* dw, float* part, size_t part_floats, long long M, int cout, int cin,
                           int accumulate, int A, int h, int w, hipStream_t st);
+// wgrad_wide_bf16.hip: the weight gradient of LF_InterNet's wide per-view 3x3 convs (cin in {128, 320} -> 64) on bf16-rounded operands.  _blocks: the
+// pixel blocks of the launch, one per 4 x 32 tile up to 256 / ceil(cin / 128) (0: cin not covered); the launch writes that many slabs [9][64][cin], which
+// lfsr_wgrad_reduce sums with nsplit = _blocks.  LFSR_E_ARG = not covered (a span of 2 GiB or more), the generic kernel runs
+int lfsr_wgrad_wide_bf16_blocks(int cin, int n_img, int h, int w);
+int lfsr_wgrad_wide_bf16_launch(const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff, int cin, float* P,
+                                int n_img, int h, int w, hipStream_t st);
+// internet_train.hip: that weight gradient as lfsr_set_wide_train_arithmetic selects it at this launch, what lfsr_conv3x3_wide_wgrad and lfsr_internet_backward
+// both run.  Default, and whatever the bf16 kernel declines: lfsr_wgrad_launch(IN_SAME, IN_CONV3, N = 64, K = cin, 9 taps) + lfsr_wgrad_reduce.  part holds
+// at least lfsr_wide_wgrad_part_floats floats (the larger of the two forms' slabs: the same in every mode; 0: shape not covered)
+size_t lfsr_wide_wgrad_part_floats(int cin, int n_img, int h, int w);
+int lfsr_wide_wgrad_run(const float* dy, int dy_stride, int dy_choff, const float* x, int x_stride, int x_choff, int cin, float* dw, float* part,
+                        int n_img, int h, int w, int accumulate, int A, hipStream_t st);
 // c_valid < C: only the first c_valid input channels are written, with row length c_valid (init_conv's 9 taps)
 int lfsr_wgrad_reduce(const float* P, int nsplit, const float* P2, int nsplit2, float* dW, int O, int C, int T, int perm, int ch,
                       int accumulate, int c_valid, int chunk_mode, hipStream_t st);

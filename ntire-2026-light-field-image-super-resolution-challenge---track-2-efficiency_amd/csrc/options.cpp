@@ -7,6 +7,8 @@
 //  * lfsr_set_wide_arithmetic: bf16 operands for LF_InterNet's wide per-view 3x3 convs, lfsr_conv3x3_wide_fwd (conv3x3_wide_bf16.hip), independent of the five;
 //  * lfsr_set_lin_grad_arithmetic: bf16 operands for the weight and data gradients of the transformers' linears, lfsr_linear_wgrad / lfsr_linear_dgrad (lin_wgrad_bf16.hip,
 //    lin_dgrad_bf16.hip), independent of the six;
+//  * lfsr_set_wide_train_arithmetic: bf16 operands for LF_InterNet's wide per-view 3x3 convs in training -- their weight gradients, lfsr_conv3x3_wide_wgrad
+//    (wgrad_wide_bf16.hip), and optionally forward_train's wide convs (conv3x3_wide_bf16.hip), independent of the seven;
 //  * lfsr_sel: the A/B selectors of the measurement / parity tooling (LFSR_* environment variables), live only in a process started with LFSR_LAB set.
 #include <stdlib.h>
 
@@ -20,6 +22,7 @@ std::atomic<int> g_branch_arith{LFSR_BRANCH_ARITH_DEFAULT};
 std::atomic<int> g_ang_arith{LFSR_ANG_ARITH_DEFAULT};
 std::atomic<int> g_wide_arith{LFSR_WIDE_ARITH_DEFAULT};
 std::atomic<int> g_lin_grad_arith{LFSR_LIN_GRAD_ARITH_DEFAULT};
+std::atomic<int> g_wide_train_arith{LFSR_WIDE_TRAIN_ARITH_DEFAULT};
 std::atomic<int> g_lab{-1};
 }  // namespace
 
@@ -40,6 +43,7 @@ bool lfsr_branch_arith_bf16() { return g_branch_arith.load(std::memory_order_rel
 bool lfsr_ang_arith_bf16() { return g_ang_arith.load(std::memory_order_relaxed) == LFSR_ANG_ARITH_BF16; }
 bool lfsr_wide_arith_bf16() { return g_wide_arith.load(std::memory_order_relaxed) == LFSR_WIDE_ARITH_BF16; }
 bool lfsr_lin_grad_arith_bf16() { return g_lin_grad_arith.load(std::memory_order_relaxed) == LFSR_LIN_GRAD_ARITH_BF16; }
+int lfsr_wide_train_arith() { return g_wide_train_arith.load(std::memory_order_relaxed); }
 
 extern "C" {
 
@@ -98,5 +102,13 @@ int lfsr_set_lin_grad_arithmetic(int mode) {
 }
 
 int lfsr_get_lin_grad_arithmetic(void) { return g_lin_grad_arith.load(); }
+
+int lfsr_set_wide_train_arithmetic(int mode) {
+  if (mode != LFSR_WIDE_TRAIN_ARITH_DEFAULT && mode != LFSR_WIDE_TRAIN_ARITH_BF16_WGRAD && mode != LFSR_WIDE_TRAIN_ARITH_BF16) return LFSR_E_ARG;
+  g_wide_train_arith.store(mode);
+  return LFSR_OK;
+}
+
+int lfsr_get_wide_train_arithmetic(void) { return g_wide_train_arith.load(); }
 
 }  // extern "C"
