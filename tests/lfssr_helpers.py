@@ -17,6 +17,22 @@ HE_GAIN = float(np.sqrt(6.0))   # U(-b, b) with b = sqrt(6 / fan_in): the varian
 CASES = {"a5h8s4": (5, 8, 8, 4, 1), "a3h6w8s2": (3, 6, 8, 2, 2), "a2h5w7s4": (2, 5, 7, 4, 2)}
 FULL = (5, 32, 32, 4, 1)
 LAYER_NAMES = ("conv0", "alt1.0", "alt1", "fup1", "sr2x", "alt2", "fup2", "out")
+# (A, s, B, h, w) and what each row reaches (tests/test_gpu_lfssr_geometries.py).  The angular kernel takes 16 consecutive pixels of one sample and a band of view rows:
+# the whole grid up to angRes 5, 4 / 3 / 2 / 2 rows at 6 / 7 / 8 / 9; k_lfssr_conv0, k_lfssr_ps2 and k_lfssr_tail are launched on at most 8192 blocks of 256 threads
+LFSSR_MATRIX = ((7, 2, 1, 5, 6),       # bands of 3 + 3 + 1 view rows; 30 pixels: one tile and a ragged one
+                (9, 2, 1, 4, 4),       # largest angRes: bands of 2, the last band one row
+                (8, 4, 1, 3, 5),       # bands of 2 that divide the grid; scale 4 on a banded grid, level-2 views of 6 x 10
+                (6, 2, 2, 3, 3),       # bands of 4 + 2; a batch boundary on a banded grid; 9 pixels: less than one 16-pixel tile
+                (4, 4, 2, 6, 5),       # even A, the widest grid that is one band; scale 4, B = 2
+                (2, 2, 3, 9, 7),       # every view a corner; B = 3; odd ragged views
+                (5, 4, 2, 8, 8),       # the benchmark's angRes at scale 4 with a batch boundary
+                (3, 4, 1, 33, 28))     # views larger than 32x32; level 2 has 9 x 66 x 56 = 33,264 rows: k_lfssr_ps2 (x 64) and k_lfssr_tail (16 x 133,056) have 2,128,896
+#                                        items each, past the 8192 x 256 = 2,097,152 threads of a capped launch -- the smallest shape at which both grid-stride loops take a
+#                                        second, partial pass inside the model
+GRID_CAP_ITEMS = 8192 * 256            # lfsr_cap_grid: past this many work items a thread of the three kernels above takes a second pass
+# (A, s, B, h, w), layer -> the measured HIP / CPU-fp32 mean-error ratio of a layer that is inside the gate and above helpers.YARDSTICK for a reason of arithmetic by design
+# (profiles/lfssr_geometry_tests.md); the gate admits no exception
+LFSSR_YARDSTICK_EXEMPT = {}
 STORED_FLOATS = 8192            # an intermediate's rows are stored every `stride`-th, so that no stored array is larger than this
 
 
@@ -47,6 +63,11 @@ def lfssr_case(tag):
     """-> (A, h, w, s, B), state_dict (numpy fp32), input mosaic (numpy fp32)"""
     A, h, w, s, B = FULL if tag == "full" else CASES[tag]
     return (A, h, w, s, B), lfssr_state_dict(lfssr_spec(s)), synth_input((B, 1, A * h, A * w), seed=1)
+
+
+def lfssr_matrix_case(A, s, B, h, w):
+    """a row of LFSSR_MATRIX -> state_dict (numpy fp32), input mosaic (numpy fp32): the weights and the input seed of lfssr_case"""
+    return lfssr_state_dict(lfssr_spec(s)), synth_input((B, 1, A * h, A * w), seed=1)
 
 
 def lfssr_meta():

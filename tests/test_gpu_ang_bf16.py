@@ -204,10 +204,9 @@ def _rms(a, b):
     return float(np.sqrt(np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)))
 
 
-@pytest.mark.parametrize("tag", list(H.CASES))
-def test_whole_model(tag):
-    (A, h, w, s, B), sd, x, layers = lfssr_fp64_case(tag)
-    y64 = layers["out"].numpy()
+def whole_model_gates(tag, A, s, sd, x, y64):
+    """LFSSR at angRes A, scale s on the mosaic x under the three reduced-precision mode combinations against the fp64 output y64: the three criteria of
+    test_whole_model (tests/test_gpu_lfssr_geometries.py applies them across its geometry matrix); the default output is bit-equal again afterwards"""
     with torch.autocast("cpu", dtype=torch.bfloat16):
         y_amp = lfssr_stock(x, sd, A, s, dtype=torch.float32).double().numpy()
     label = torch.rand(y64.shape, generator=torch.Generator().manual_seed(2)).numpy()
@@ -233,6 +232,12 @@ def test_whole_model(tag):
             fails.append((name, "equal to the default"))
     assert not fails, fails
     assert np.array_equal(rt.forward(xg).cpu().numpy(), y_def)
+
+
+@pytest.mark.parametrize("tag", list(H.CASES))
+def test_whole_model(tag):
+    (A, h, w, s, B), sd, x, layers = lfssr_fp64_case(tag)
+    whole_model_gates(tag, A, s, sd, x, layers["out"].numpy())
 
 
 # ---------------------------------------------------------------------------------------------------------------------

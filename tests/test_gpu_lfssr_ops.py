@@ -3,7 +3,10 @@ wider rows behind NaN guard rows, outputs in front of sentinel rows; the refusal
 
 lfsr_angconv3x3_fwd: angRes 2 (every view a corner), 3 and 5 (an interior view) x views of 1 x 1 (one pixel of a 16-pixel tile), 3 x 5 (15: one ragged tile) and
 8 x 8 (four tiles) x B 1 and 2 (view A^2 of sample 0 is view 0 of sample 1) x no prologue / an ALL-POSITIVE in_bias (a view outside the grid that went through the
-prologue would add relu(0 + bias) > 0) x the dense and the 144-wide layout for x and y independently; angRes 6..9 (the banded launches) at one geometry each."""
+prologue would add relu(0 + bias) > 0) x the dense and the 144-wide layout for x and y independently; angRes 6..9 (the banded launches) at one geometry each.
+
+lfsr_lfssr_conv0_fwd, lfsr_conv3x3_ps2_fwd, lfsr_lfssr_tail_fwd: 3 x 3 views of 5 x 7 at B 2, views of one pixel, a 9 x 9 grid, and sizes just past the launch cap, at which a thread of
+their grid-stride loops takes a second, ragged pass (measured figures: profiles/lfssr_geometry_tests.md)."""
 import ctypes as C
 import functools
 
@@ -13,6 +16,7 @@ import torch.nn.functional as F
 
 from lfsr_amd import capi
 from tests.helpers import OP_SENTINEL, op_gate, op_input, op_output, op_output_read
+from tests.lfssr_helpers import GRID_CAP_ITEMS
 
 pytestmark = pytest.mark.gpu
 
@@ -135,30 +139,49 @@ def test_angconv3x3_refusals_write_nothing():
     op_output_read(yb, 64, 64)
 
 
-# ---- conv0, the up-sampling conv, the tail: one geometry each, odd h and w ------------------------------------------------------------------------
+# ---- conv0, the up-sampling conv, the tail: (A, B, h, w) --------------------------------------------------------------------------------------------
+# BASE: odd h and w, a batch boundary (the refusals are checked there); ONE_PIXEL: views of one pixel, every tap but the centre off the image (the tail's output views are
+# 2 x 2); A9: the mosaic addressing at the largest grid; WRAP / WRAP0: past the 8192 blocks of 256 threads a launch is capped at (lfsr_cap_grid), so that a thread takes a
+# second pass, with a count that is no multiple of 256 -- a ragged last block, and in the tail a last 16-lane butterfly group with dead lanes
 
-A0, H0, W0, B0 = 3, 5, 7, 2
+BASE, ONE_PIXEL, A9, WRAP, WRAP0 = (3, 2, 5, 7), (2, 1, 1, 1), (9, 1, 2, 3), (3, 1, 61, 61), (3, 1, 121, 121)
+MOSAIC_GUARD = 1024          # NaN floats in front of and behind conv0's mosaic and the tail's LR planes
+op_ids = lambda g: "A%dB%dh%dw%d" % g if isinstance(g, tuple) else None
+
+
+def wraps(items):
+    """the count is past the launch cap and leaves a ragged last block"""
+    return items > GRID_CAP_ITEMS and items % 256 != 0
 
 
 def views_to_rows(t):
     return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]).contiguous()
 
 
-def test_conv0_vs_fp64():
+@pytest.mark.parametrize("geom", [BASE, ONE_PIXEL, A9, WRAP0], ids=op_ids)
+def test_conv0_vs_fp64(geom):
+    A0, B0, H0, W0 = geom
+    if geom == WRAP0:
+        assert B0 * A0 * A0 * H0 * W0 == 131769 and wraps(131769 * 16)               # 2,108,304 items: 8235.56 blocks
     x = torch.rand(B0, 1, A0 * H0, A0 * W0, generator=torch.Generator().manual_seed(3))
     wt, bias = rnd((64, 1, 3, 3), 1, 1.0 / 3.0).float(), rnd((64,), 2, 0.1).float()
     views = x.reshape(B0, A0, H0, A0, W0).permute(0, 1, 3, 2, 4).reshape(-1, 1, H0, W0)
     ref, cpu = (views_to_rows(torch.relu(F.conv2d(views.to(d), wt.to(d), bias.to(d), padding=1))) for d in (torch.float64, torch.float32))
     M = ref.shape[0]
     lib, outs = capi.load(), []
+    xbuf = torch.full((x.numel() + 2 * MOSAIC_GUARD,), float("nan"))       # the mosaic behind and in front of NaN: a tap that leaves it shows
+    xbuf[MOSAIC_GUARD:MOSAIC_GUARD + x.numel()] = x.reshape(-1)
+    xbuf, wd, bd = xbuf.cuda(), wt.cuda(), bias.cuda()
+    xd = xbuf[MOSAIC_GUARD:MOSAIC_GUARD + x.numel()]
     for k in range(2):
         yb = op_output(M, 144, 30 + k)
-        assert lib.lfsr_lfssr_conv0_fwd(capi.dev_ptr(x.cuda()), capi.dev_ptr(wt.cuda()), capi.dev_ptr(bias.cuda()), yb.ptr, 144, 64, B0, A0, H0, W0, capi.stream_ptr()) == 0
+        assert lib.lfsr_lfssr_conv0_fwd(capi.dev_ptr(xd), capi.dev_ptr(wd), capi.dev_ptr(bd), yb.ptr, 144, 64, B0, A0, H0, W0, capi.stream_ptr()) == 0
         outs.append(op_output_read(yb, 64, 64))
     op_gate(outs[0], ref, cpu, "lfssr_conv0", "bias+relu", f"A{A0} {H0}x{W0} B{B0}", tag="LFSSROP")
     assert torch.equal(outs[0], outs[1])
+    if geom != BASE:
+        return
     yb = op_output(M, 144, 33)
-    xd, wd, bd = x.cuda(), wt.cuda(), bias.cuda()
     bad = [lib.lfsr_lfssr_conv0_fwd(capi.dev_ptr(xd), capi.dev_ptr(wd), capi.dev_ptr(bd), yb.ptr, ys, yo, B, A0, H0, W0, None)
            for ys, yo, B in ((146, 64, B0), (144, 66, B0), (100, 64, B0), (144, 64, 0))]
     bad.append(lib.lfsr_lfssr_conv0_fwd(None, capi.dev_ptr(wd), capi.dev_ptr(bd), yb.ptr, 144, 64, B0, A0, H0, W0, None))
@@ -166,8 +189,12 @@ def test_conv0_vs_fp64():
     op_output_read(yb, 0, 0)
 
 
-def test_conv3x3_ps2_vs_fp64():
+@pytest.mark.parametrize("geom", [BASE, ONE_PIXEL, WRAP], ids=op_ids)
+def test_conv3x3_ps2_vs_fp64(geom):
+    A0, B0, H0, W0 = geom
     n_img = B0 * A0 * A0
+    if geom == WRAP:
+        assert n_img * H0 * W0 == 33489 and wraps(33489 * 64)                        # 2,143,296 items: 8372.25 blocks
     xin = rnd((n_img, 64, H0, W0), 4).float()
     wt, bias = rnd((256, 64, 3, 3), 5, 1.0 / 24.0).float(), rnd((256,), 6, 0.1).float()
     ref, cpu = (views_to_rows(torch.relu(F.pixel_shuffle(F.conv2d(xin.to(d), wt.to(d), bias.to(d), padding=1), 2))) for d in (torch.float64, torch.float32))
@@ -181,6 +208,8 @@ def test_conv3x3_ps2_vs_fp64():
         outs.append(op_output_read(yb, 64, 64))
     op_gate(outs[0], ref, cpu, "conv3x3_ps2", "bias+ps2+relu", f"{n_img} views {H0}x{W0}", tag="LFSSROP")
     assert torch.equal(outs[0], outs[1])
+    if geom != BASE:
+        return
     xb, yb = op_input(rows, 144, 64, 44), op_output(4 * rows.shape[0], 144, 45)
     args = dict(xs=144, xo=64, ys=144, yo=64, n=n_img)
     bad = []
@@ -193,8 +222,12 @@ def test_conv3x3_ps2_vs_fp64():
 
 
 @pytest.mark.parametrize("mosaic", [0, 1])
-def test_tail_vs_fp64(mosaic):
+@pytest.mark.parametrize("geom", [BASE, ONE_PIXEL, A9, WRAP], ids=op_ids)
+def test_tail_vs_fp64(geom, mosaic):
+    A0, B0, H0, W0 = geom
     n_img = B0 * A0 * A0
+    if geom == WRAP:
+        assert n_img * 4 * H0 * W0 == 133956 and 133956 % 16 and wraps(133956 * 16)   # 2,143,296 items, 8372.25 blocks: the last butterfly group has dead lanes
     f = rnd((n_img, 64, 2 * H0, 2 * W0), 7).float()
     lo = torch.rand(n_img, 1, H0, W0, generator=torch.Generator().manual_seed(8))
     w_res, b_res = rnd((1, 64, 3, 3), 9, 1.0 / 24.0).float(), rnd((1,), 10, 0.1).float()
@@ -208,19 +241,25 @@ def test_tail_vs_fp64(mosaic):
 
     rows = views_to_rows(f)
     n_out = n_img * 4 * H0 * W0
-    dev = [t.cuda() for t in (w_res, b_res, lo.contiguous(), w_iup, b_iup)]
+    lobuf = torch.full((lo.numel() + 2 * MOSAIC_GUARD,), float("nan"))         # the LR planes behind and in front of NaN
+    lobuf[MOSAIC_GUARD:MOSAIC_GUARD + lo.numel()] = lo.reshape(-1)
+    lobuf = lobuf.cuda()
+    dev = [t.cuda() for t in (w_res, b_res)] + [lobuf[MOSAIC_GUARD:MOSAIC_GUARD + lo.numel()]] + [t.cuda() for t in (w_iup, b_iup)]
     lib, outs = capi.load(), []
     for k in range(2):
         fb = op_input(rows, 144, 64, 50 + k)
-        out = torch.full((n_out + 8,), OP_SENTINEL, device="cuda")
+        pool = torch.full((8 + n_out + 8,), OP_SENTINEL, device="cuda")      # sentinels in front of the first output pixel and behind the last
+        out = pool[8:]
         rc = lib.lfsr_lfssr_tail_fwd(fb.ptr, 144, 64, capi.dev_ptr(dev[0]), capi.dev_ptr(dev[1]), capi.dev_ptr(dev[2]), capi.dev_ptr(dev[3]), capi.dev_ptr(dev[4]),
                                      capi.dev_ptr(out), B0, A0, H0, W0, mosaic, capi.stream_ptr())
         assert rc == 0
         torch.cuda.synchronize()
-        assert bool((out[n_out:] == OP_SENTINEL).all())
+        assert bool((out[n_out:] == OP_SENTINEL).all()) and bool((pool[:8] == OP_SENTINEL).all())
         outs.append(out[:n_out].cpu().reshape(1, -1))
     op_gate(outs[0], ref(torch.float64), ref(torch.float32), "lfssr_tail", "mosaic" if mosaic else "planes", f"A{A0} {H0}x{W0} B{B0}", tag="LFSSROP")
     assert torch.equal(outs[0], outs[1])
+    if geom != BASE:
+        return
     fb = op_input(rows, 144, 64, 52)
     out = torch.full((n_out + 8,), OP_SENTINEL, device="cuda")
     P = capi.dev_ptr
