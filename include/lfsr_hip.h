@@ -513,7 +513,9 @@ int lfsr_angconv_bwd(const float* dy, int dy_stride, int dy_choff, const float* 
                      int B, int A, int h, int w, float slope, void* stream);
 /* EPIConv on the tensor and on its transpose (shared weights; both passes' weight gradients summed): dy holds dLoss/dy_h at choff_h and dLoss/dy_v at
  * choff_v (32 channels each); y likewise the two outputs (or NULL, as above); e_h / e_v: the stage-1 activations lfsr_epiconv_fwd(vertical = 0 / 1) left
- * in `tmp` ((B A h w), 32); w0 (32,64,1,A^2), w2 (32 A,32,1,1).  Odd angRes only (symmetric padding of the EPI line). */
+ * in `tmp` ((B A h w), 32); w0 (32,64,1,A^2), w2 (32 A,32,1,1).  Odd angRes only (symmetric padding of the EPI line).
+ * EPIConv.0's data gradient (into dx) and weight gradient (dw0) follow lfsr_set_branch_grad_arithmetic (below) where their EPI-line kernels apply: A = 5, a pass's
+ * line length <= 32 (the weight gradient: both h and w <= 32); stage 2 (dE, dw2) does not, and the workspace does not depend on the mode. */
 size_t lfsr_epiconv_hv_bwd_workspace_floats(int B, int A, int h, int w);
 int lfsr_epiconv_hv_bwd(const float* dy, int dy_stride, int choff_h, int choff_v, const float* y, int y_stride, int y_choff_h, int y_choff_v,
                         const float* x, const float* e_h, const float* e_v, const float* w0, const float* w2,
@@ -588,7 +590,7 @@ int lfsr_get_gemm_arithmetic(void);
  * arithmetic.  What follows: lfsr_distgssr_forward (and _taps) and the operator lfsr_distg_branch_tail_fwd.  What does not, with its bits unchanged:
  * LFSR_ARITH_F32 (which wins), angRes other than 5, inputs of fewer than 2048 pixels, block (0,0) when the concat tap is requested, the LFSR_LAB selectors,
  * lfsr_distgssr_forward_train and every backward kernel (the training forward keeps the three-kernel sequence whose intermediates the backward reads: training
- * under the mode is not its aim), and EPIT, LFT and LF_InterNet.  No atomics: two runs give the same bits, and a macro-pixel's result depends neither on B nor on
+ * under the mode is not its aim; the branch backward has its own switch, lfsr_set_branch_grad_arithmetic below), and EPIT, LFT and LF_InterNet.  No atomics: two runs give the same bits, and a macro-pixel's result depends neither on B nor on
  * the grid.  Parity with the reference's fp32 results is claimed only in the default mode (error against fp64 under the mode: below
  * torch.autocast(bfloat16)'s, tests/test_gpu_branch_bf16.py). */
 #define LFSR_BRANCH_ARITH_DEFAULT 0
@@ -704,6 +706,30 @@ int lfsr_get_wide_train_arithmetic(void);
 size_t lfsr_conv3x3_wide_wgrad_workspace_floats(int cin, int n_img, int h, int w);
 int lfsr_conv3x3_wide_wgrad(const float* dy, int dy_stride, int dy_choff, const float* x, int x_stride, int x_choff, int cin,
                             float* dw, float* workspace, size_t workspace_floats, int n_img, int h, int w, int accumulate, void* stream);
+
+/* ---- arithmetic of EPIConv.0's GRADIENTS (DistgSSR's disentangling branch in training): a ninth process-wide selection, independent of the eight above, read at every
+ * launch ----
+ * LFSR_BRANCH_GRAD_ARITH_DEFAULT: every kernel as it is, bit for bit.
+ * LFSR_BRANCH_GRAD_ARITH_BF16: opt-in, the training counterpart of lfsr_set_branch_arithmetic.  The two EPI-line gradient kernels of EPIConv.0 (1 x A^2, stride A,
+ * 64 -> 32, shared by the horizontal and the vertical pass) run on bf16 operands (csrc/epi0_grad_bf16.hip):
+ *  - the weight gradient: dE and the input slab of an EPI line are rounded to bf16 (nearest even) on their way into LDS, the products are exact
+ *    (v_mfma_f32_16x16x32_bf16, the pixel index as the MFMA's K), accumulation is fp32 into one partial slab per block, and the fixed-order reduction of the default
+ *    sums the same number of slabs;
+ *  - the data gradient: dE and the weights (from the fp32 direct pack, while a block stages them: no new pack, no new workspace) are rounded to bf16, the products are
+ *    exact, accumulation is fp32 and the read-modify-write of dx stays fp32.
+ * They are taken exactly where the fp32 EPI-line kernels are taken: A = 5, the pass's line length <= 32 (the merged weight gradient: h and w both <= 32), the operand
+ * span below 2 GiB.  Everywhere else the call runs what it runs in the default mode, bit for bit.  The LFSR_LAB selectors LFSR_WGRAD_EPI=gather and
+ * LFSR_DGRAD_EPI=gather still win.
+ * What follows: lfsr_epiconv_hv_bwd and lfsr_distgssr_backward (one-stream and two-stream order alike).  What does not, with its bits unchanged: every forward and
+ * forward_train, lfsr_angconv_bwd, stage 2 of the EPI branch (dE, dw2), fuse.0's gradients, the 3x3 convs (lfsr_set_grad_arithmetic), and EPIT, LFT, LF_InterNet and
+ * LFSSR.  It does not interact with lfsr_set_arithmetic: no "F32 wins" rule, as for the grad switch.  lfsr_epiconv_hv_bwd_workspace_floats and
+ * lfsr_distgssr_train_workspace_bytes do not depend on the mode.  Gradients, activations and slabs stay fp32 in memory; bf16 keeps fp32's exponent range: no loss
+ * scaling is needed.  No atomics: two runs give the same bits, and a sample's data gradient does not depend on B.  Parity with the reference's fp32 gradients is
+ * claimed only in the default mode (error against fp64 autograd under the mode: below torch.autocast(bfloat16)'s, tests/test_gpu_branch_grad_bf16.py). */
+#define LFSR_BRANCH_GRAD_ARITH_DEFAULT 0
+#define LFSR_BRANCH_GRAD_ARITH_BF16 1
+int lfsr_set_branch_grad_arithmetic(int mode);   /* LFSR_E_ARG for any other value, nothing changed */
+int lfsr_get_branch_grad_arithmetic(void);
 
 /* ---- operator-level timing hooks (measurement aid; the reference times whole forwards only: check_efficiency_official.py:306-330) ----
  * lfsr_op_profile(1): from now on every instrumented operator entry point brackets its launches with a hipEvent pair on its launch stream (and any

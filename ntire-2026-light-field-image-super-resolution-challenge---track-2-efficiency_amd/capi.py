@@ -108,6 +108,8 @@ SIGNATURES = {
     "lfsr_linear_wgrad": (c_i, [c_p, c_i, c_p, c_i, c_p, c_p, c_sz, C.c_longlong, c_i, c_i, c_i, c_p]),
     "lfsr_set_wide_train_arithmetic": (c_i, [c_i]),
     "lfsr_get_wide_train_arithmetic": (c_i, []),
+    "lfsr_set_branch_grad_arithmetic": (c_i, [c_i]),
+    "lfsr_get_branch_grad_arithmetic": (c_i, []),
     "lfsr_conv3x3_wide_wgrad_workspace_floats": (c_sz, [c_i, c_i, c_i, c_i]),
     "lfsr_conv3x3_wide_wgrad": (c_i, [c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_sz, c_i, c_i, c_i, c_i, c_p]),
     "lfsr_conv3x3_wide_fwd":(c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p]),
@@ -311,6 +313,21 @@ def set_wide_train_arithmetic(mode):
 def get_wide_train_arithmetic():
     """lfsr_get_wide_train_arithmetic: the mode the next lfsr_conv3x3_wide_wgrad / lfsr_internet_forward_train / lfsr_internet_backward launch runs in"""
     return int(load().lfsr_get_wide_train_arithmetic())
+
+
+BRANCH_GRAD_ARITH_DEFAULT, BRANCH_GRAD_ARITH_BF16 = 0, 1
+
+
+def set_branch_grad_arithmetic(mode):
+    """lfsr_set_branch_grad_arithmetic: BRANCH_GRAD_ARITH_DEFAULT (EPIConv.0's gradients as they are) or BRANCH_GRAD_ARITH_BF16 (the EPI-line weight and data
+    gradients of EPIConv.0 behind epiconv_hv_bwd and the DistgSSR backward round their operands to bf16, fp32 accumulation); process-wide, independent of the
+    other eight switches"""
+    check(load().lfsr_set_branch_grad_arithmetic(int(mode)), "set_branch_grad_arithmetic")
+
+
+def get_branch_grad_arithmetic():
+    """lfsr_get_branch_grad_arithmetic: the mode the next lfsr_epiconv_hv_bwd / lfsr_distgssr_backward launch runs in"""
+    return int(load().lfsr_get_branch_grad_arithmetic())
 
 
 def op_profile(enable):

@@ -271,6 +271,7 @@ int lfsr_epi0_dgrad_launch(const float* dE, const float* w_direct, float* dx, in
   const char* sel = lfsr_sel("LFSR_DGRAD_EPI");
   if (A != 5 || (vert ? h : w) > 32 || (sel && sel[0] == 'g')) return LFSR_E_ARG;
   if ((long long)B * A * A * h * w * dx_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;
+  if (lfsr_branch_grad_arith_bf16()) return lfsr_epi0_dgrad_bf16_launch(dE, w_direct, dx, dx_stride, dx_choff, B, h, w, vert, st);   // epi0_grad_bf16.hip
   static std::atomic<bool> attr_set[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;

@@ -31,6 +31,7 @@ bool lfsr_branch_arith_bf16();   // lfsr_set_branch_arithmetic(LFSR_BRANCH_ARITH
 bool lfsr_ang_arith_bf16();   // lfsr_set_ang_arithmetic(LFSR_ANG_ARITH_BF16): LFSSR's angular 3x3 conv, lfsr_angconv3x3_fwd, on bf16 operands (ang3x3_bf16.hip)
 bool lfsr_wide_arith_bf16();   // lfsr_set_wide_arithmetic(LFSR_WIDE_ARITH_BF16): LF_InterNet's 128 | 320 -> 64 per-view 3x3 convs, lfsr_conv3x3_wide_fwd, on bf16 operands (conv3x3_wide_bf16.hip)
 bool lfsr_lin_grad_arith_bf16();   // lfsr_set_lin_grad_arithmetic(LFSR_LIN_GRAD_ARITH_BF16): the linears' weight and data gradients, lfsr_linear_wgrad / lfsr_linear_dgrad, on bf16 operands (lin_wgrad_bf16.hip, lin_dgrad_bf16.hip)
+bool lfsr_branch_grad_arith_bf16();   // lfsr_set_branch_grad_arithmetic(LFSR_BRANCH_GRAD_ARITH_BF16): EPIConv.0's weight and data gradients (the EPI-line forms) on bf16 operands (epi0_grad_bf16.hip)
 int lfsr_wide_train_arith();   // lfsr_get_wide_train_arithmetic(): LF_InterNet's wide convs in training -- 1: their weight gradients on bf16 operands (wgrad_wide_bf16.hip); 2: forward_train's wide convs as well
 static inline unsigned lfsr_blocks(long long n, int per) {
   long long b = (n + per - 1) / per;

@@ -274,6 +274,11 @@ int lfsr_wgrad_epi0_blocks(int B, int A, int h, int w, int vert);
 int lfsr_ang0_dgrad_launch(const float* dA16, const float* w_direct, float* dx, int dx_stride, int dx_choff, int B, int A, int h, int w, hipStream_t st);
 int lfsr_epi0_dgrad_launch(const float* dE, const float* w_direct, float* dx, int dx_stride, int dx_choff, int B, int A, int h, int w, int vert, hipStream_t st);
 int lfsr_wgrad_epi0_launch(const float* dE, const float* dE_v, const float* X, int x_stride, int x_choff, float* P, int B, int A, int h, int w, int vert, hipStream_t st);
+// epi0_grad_bf16.hip: the two EPI-line kernels on bf16-rounded operands (LFSR_BRANCH_GRAD_ARITH_BF16), A = 5; the two launchers above call them after their own coverage
+// checks and selectors.  The weight gradient writes all `blocks` slabs [25][32][64].
+int lfsr_wgrad_epi0_bf16_launch(const float* dE, const float* dE_v, const float* X, int x_stride, int x_choff, float* P, int B, int h, int w, int vert, int blocks,
+                                hipStream_t st);
+int lfsr_epi0_dgrad_bf16_launch(const float* dE, const float* w_direct, float* dx, int dx_stride, int dx_choff, int B, int h, int w, int vert, hipStream_t st);
 // wgrad_bf16.hip: the same contract on bf16-rounded operands (LFSR_GRAD_ARITH_BF16); writes all `blocks` slabs; LFSR_E_ARG = not covered, the fp32 kernel runs
 int lfsr_wgrad_conv3_bf16_launch(const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff, float* P,
                                  int n_img, int h, int w, int blocks, hipStream_t st);

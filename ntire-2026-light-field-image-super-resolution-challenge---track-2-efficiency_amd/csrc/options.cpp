@@ -9,6 +9,8 @@
 //    lin_dgrad_bf16.hip), independent of the six;
 //  * lfsr_set_wide_train_arithmetic: bf16 operands for LF_InterNet's wide per-view 3x3 convs in training -- their weight gradients, lfsr_conv3x3_wide_wgrad
 //    (wgrad_wide_bf16.hip), and optionally forward_train's wide convs (conv3x3_wide_bf16.hip), independent of the seven;
+//  * lfsr_set_branch_grad_arithmetic: bf16 operands for the EPI-line weight and data gradients of DistgSSR's EPIConv.0 (epi0_grad_bf16.hip) behind lfsr_epiconv_hv_bwd and
+//    lfsr_distgssr_backward, independent of the eight;
 //  * lfsr_sel: the A/B selectors of the measurement / parity tooling (LFSR_* environment variables), live only in a process started with LFSR_LAB set.
 #include <stdlib.h>
 
@@ -23,6 +25,7 @@ std::atomic<int> g_ang_arith{LFSR_ANG_ARITH_DEFAULT};
 std::atomic<int> g_wide_arith{LFSR_WIDE_ARITH_DEFAULT};
 std::atomic<int> g_lin_grad_arith{LFSR_LIN_GRAD_ARITH_DEFAULT};
 std::atomic<int> g_wide_train_arith{LFSR_WIDE_TRAIN_ARITH_DEFAULT};
+std::atomic<int> g_branch_grad_arith{LFSR_BRANCH_GRAD_ARITH_DEFAULT};
 std::atomic<int> g_lab{-1};
 }  // namespace
 
@@ -43,6 +46,7 @@ bool lfsr_branch_arith_bf16() { return g_branch_arith.load(std::memory_order_rel
 bool lfsr_ang_arith_bf16() { return g_ang_arith.load(std::memory_order_relaxed) == LFSR_ANG_ARITH_BF16; }
 bool lfsr_wide_arith_bf16() { return g_wide_arith.load(std::memory_order_relaxed) == LFSR_WIDE_ARITH_BF16; }
 bool lfsr_lin_grad_arith_bf16() { return g_lin_grad_arith.load(std::memory_order_relaxed) == LFSR_LIN_GRAD_ARITH_BF16; }
+bool lfsr_branch_grad_arith_bf16() { return g_branch_grad_arith.load(std::memory_order_relaxed) == LFSR_BRANCH_GRAD_ARITH_BF16; }
 int lfsr_wide_train_arith() { return g_wide_train_arith.load(std::memory_order_relaxed); }
 
 extern "C" {
@@ -110,5 +114,13 @@ int lfsr_set_wide_train_arithmetic(int mode) {
 }
 
 int lfsr_get_wide_train_arithmetic(void) { return g_wide_train_arith.load(); }
+
+int lfsr_set_branch_grad_arithmetic(int mode) {
+  if (mode != LFSR_BRANCH_GRAD_ARITH_DEFAULT && mode != LFSR_BRANCH_GRAD_ARITH_BF16) return LFSR_E_ARG;
+  g_branch_grad_arith.store(mode);
+  return LFSR_OK;
+}
+
+int lfsr_get_branch_grad_arithmetic(void) { return g_branch_grad_arith.load(); }
 
 }  // extern "C"

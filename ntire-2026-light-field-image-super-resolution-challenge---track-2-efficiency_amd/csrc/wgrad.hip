@@ -764,6 +764,8 @@ int lfsr_wgrad_epi0_launch(const float* dE, const float* dE_v, const float* X, i
   const char* sel = lfsr_sel("LFSR_WGRAD_EPI");
   if (A != 5 || (vert != 0 && h > 32) || (vert != 1 && w > 32) || (sel && sel[0] == 'g')) return LFSR_E_ARG;
   if ((long long)B * A * A * h * w * x_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;
+  if (lfsr_branch_grad_arith_bf16())   // the same lines, slabs and block count on bf16 operands (epi0_grad_bf16.hip)
+    return lfsr_wgrad_epi0_bf16_launch(dE, dE_v, X, x_stride, x_choff, P, B, h, w, vert, lfsr_wgrad_epi0_blocks(B, A, h, w, vert), st);
   static std::atomic<bool> attr_set[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
