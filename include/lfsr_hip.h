@@ -458,8 +458,8 @@ int lfsr_internet_backward(lfsr_internet* ctx, const float* x, const float* dout
  * LFSSR (model/SR/LFSSR.py, the spatial-angular separable network): INFERENCE only -- there is no backward and there are no num_params / param_offset / *_train
  * symbols.  Scale 2 (net2x) and 4 (net4x), angRes 2..9, any view size.  All its convs have biases; the activation is ReLU.
  * The four kernels below have one arithmetic each and read none of the four arithmetic switches further down; the per-view 64 -> 64 3x3 convs of the model (the
- * spatial half of every AltFilter, the four sub-pixel convs of lfsr_conv3x3_ps2_fwd) run through the 3x3 dispatcher and so follow lfsr_set_arithmetic, a mode that
- * is NOT tested for LFSSR.
+ * spatial half of every AltFilter, the four sub-pixel convs of lfsr_conv3x3_ps2_fwd) run through the 3x3 dispatcher and so follow lfsr_set_arithmetic; LFSSR is
+ * tested under that mode, alone and with lfsr_set_ang_arithmetic, across its geometry matrix (tests/test_gpu_lfssr_geometries.py::test_bf16_modes).
  * ---------------------------------------------------------------------------------------------- */
 /* The angular half of an AltFilter (LFSSR.py:201,208-215): at every pixel, a 3x3 conv 64 -> 64 with zero padding over the A x A grid of views, on VCL rows
  * p = ((b A + u) A + v) npix + q (npix = h w):

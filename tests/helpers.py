@@ -41,6 +41,44 @@ def arithmetic(mode):
         capi.set_arithmetic(capi.ARITH_DEFAULT)
 
 
+# switch -> (capi setter, capi getter, the name of capi's default value): the nine process-wide arithmetic selections
+MODE_SWITCHES = {"arith": ("set_arithmetic", "get_arithmetic", "ARITH_DEFAULT"),
+                 "grad": ("set_grad_arithmetic", "get_grad_arithmetic", "GRAD_ARITH_DEFAULT"),
+                 "gemm": ("set_gemm_arithmetic", "get_gemm_arithmetic", "GEMM_ARITH_DEFAULT"),
+                 "branch": ("set_branch_arithmetic", "get_branch_arithmetic", "BRANCH_ARITH_DEFAULT"),
+                 "ang": ("set_ang_arithmetic", "get_ang_arithmetic", "ANG_ARITH_DEFAULT"),
+                 "wide": ("set_wide_arithmetic", "get_wide_arithmetic", "WIDE_ARITH_DEFAULT"),
+                 "lin_grad": ("set_lin_grad_arithmetic", "get_lin_grad_arithmetic", "LIN_GRAD_ARITH_DEFAULT"),
+                 "wide_train": ("set_wide_train_arithmetic", "get_wide_train_arithmetic", "WIDE_TRAIN_ARITH_DEFAULT"),
+                 "branch_grad": ("set_branch_grad_arithmetic", "get_branch_grad_arithmetic", "BRANCH_GRAD_ARITH_DEFAULT")}
+
+
+@contextlib.contextmanager
+def modes(**switches):
+    """the given selections (keys of MODE_SWITCHES -> a value of that switch) for the block, every other one at its default; all nine are the default again after
+    it, whatever the block did (the settings are process-wide)"""
+    from lfsr_amd import capi
+    unknown = set(switches) - set(MODE_SWITCHES)
+    assert not unknown, unknown
+
+    def reset():
+        for setter, _, default in MODE_SWITCHES.values():
+            getattr(capi, setter)(getattr(capi, default))
+    try:
+        reset()
+        for k, v in switches.items():
+            getattr(capi, MODE_SWITCHES[k][0])(v)
+        yield
+    finally:
+        reset()
+
+
+def modes_now():
+    """{switch: the value the next launch runs in}"""
+    from lfsr_amd import capi
+    return {k: getattr(capi, getter)() for k, (_, getter, _) in MODE_SWITCHES.items()}
+
+
 def psnr(a, b):
     mse = np.mean((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2)
     return float("inf") if mse == 0 else 10.0 * np.log10(1.0 / mse)

@@ -6,7 +6,9 @@ Operator gates: against the fp64 gradient of the SAME rounded operands (torch.Te
 Whole-model gates (DistgSSR): every parameter's rel-L2 error against fp64 autograd not above that of the reference's own reduced-precision path, the torch port
 under torch.autocast("cpu", bfloat16), margin 1.0x (CPU emulation of the mode: >= 3.2x inside on all 137 tensors); with the bf16 forward as well only the flat
 bucket is gated (emulation: 1.44x / 1.67x inside, single tensors within 1.05x).  The other three drivers share the data-gradient dispatcher: their gradients
-move, stay finite, and stay within 5e-2 rel-L2 of the default's bucket (rounding alone: 2.35e-3 sqrt(depth) <= 1.4e-2; a wrong mask or tap order gives O(1))."""
+move, stay finite, and stay within 5e-2 rel-L2 of the default's bucket (rounding alone: 2.35e-3 sqrt(depth) <= 1.4e-2; a wrong mask or tap order gives O(1)).
+That distance cannot see a fault in a single layer (a mask lost in one conv moves the bucket by ~6e-3: tests/test_modes_refs_cpu.py); the fp64 gate per parameter
+for those three drivers, across geometry rows, is tests/test_gpu_modes_geometries.py::test_training_step (leg G)."""
 import contextlib
 import functools
 import importlib
