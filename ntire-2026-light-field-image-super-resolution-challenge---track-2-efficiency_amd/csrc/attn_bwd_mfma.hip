@@ -229,35 +229,34 @@ __global__ __launch_bounds__(64 * NW) void k_epi_attn_bwd_mfma(EpiAttnBwdArgs p)
 
 }  // namespace
 
-// LFSR_E_ARG = geometry not covered (the caller falls back to the VALU pair): the coverage of lfsr_epi_attn_mfma_launch
-int lfsr_epi_attn_bwd_mfma_launch(const float* qk, int qk_stride, int q_choff, int k_choff, const float* v, int v_stride, const float* o, const float* d_o,
-                                  int o_stride, float* dqk, float* dv, int nheads, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
-                                  int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, hipStream_t st) {
-  const long long Lll = (long long)n1 * n2;
+// LFSR_E_ARG = geometry not covered (the dispatcher runs the VALU pair): the coverage of lfsr_epi_attn_mfma_launch
+int lfsr_epi_attn_bwd_mfma_launch(const LfsrAttnGrad& a, hipStream_t st) {
+  const LfsrAttnGeom& g = a.g;
+  const long long Lll = g.tokens();
   // every angular position visible; <= 10 tiles of 16 tokens.  A one-token sequence goes to the VALU pair: the softmax over a single key is constant, dQ = dK = 0
   // and dV = dO exactly, which the pair returns, while dP - D here (two differently ordered sums of the same products) leaves rounding residue in their place
-  if (nheads % 4 || Lll > 160 || Lll < 2 || l1 < n1 - 1 || r1 < n1) return LFSR_E_ARG;
+  if (a.hd != 16 || a.nheads % 4 || Lll > 160 || Lll < 2 || g.l1 < g.n1 - 1 || g.r1 < g.n1) return LFSR_E_ARG;
   EpiAttnBwdArgs p{};
-  p.QK = qk; p.qk_stride = qk_stride; p.q_choff = q_choff; p.k_choff = k_choff; p.V = v; p.v_stride = v_stride; p.O = o; p.dO = d_o; p.o_stride = o_stride;
-  p.dQK = dqk; p.dV = dv; p.nheads = nheads; p.ns1 = ns1; p.ns2 = ns2; p.bs0 = bs0; p.bs1 = bs1; p.bs2 = bs2;
-  p.n1 = n1; p.n2 = n2; p.st1 = st1; p.st2 = st2; p.l2 = l2 < n2 ? l2 : n2; p.r2 = r2 < n2 ? r2 : n2; p.clip2 = clip2 > 0 ? clip2 : n2;     // (a window wider than the sequence is the sequence)
+  p.QK = a.qk; p.qk_stride = a.qk_stride; p.q_choff = a.q_choff; p.k_choff = a.k_choff; p.V = a.v; p.v_stride = a.v_stride; p.O = a.o; p.dO = a.d_o; p.o_stride = a.o_stride;
+  p.dQK = a.dqk; p.dV = a.dv; p.nheads = a.nheads; p.ns1 = g.ns1; p.ns2 = g.ns2; p.bs0 = g.bs0; p.bs1 = g.bs1; p.bs2 = g.bs2;
+  p.n1 = g.n1; p.n2 = g.n2; p.st1 = g.st1; p.st2 = g.st2; p.l2 = g.l2 < g.n2 ? g.l2 : g.n2; p.r2 = g.r2 < g.n2 ? g.r2 : g.n2; p.clip2 = g.clip2;     // (a window wider than the sequence is the sequence)
   p.scale = 1.0f / sqrtf(16.0f);
   p.scale2 = p.scale * 1.44269504088896340736f;
   p.L = (int)Lll;
-  const long long nblk = (long long)ns0 * ns1 * ns2 * nheads;
+  const long long nblk = g.nseq() * a.nheads;
   if (nblk <= 0 || nblk > 0x7fffffffLL) return LFSR_E_ARG;
   constexpr int NT = 10;
   const int smem = (7 * NT * 16 * 16 + 5 * NT * 16) * 4;   // 74880
   static std::atomic<bool> attr_set[64];
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_HIP_ERR(hipErrorInvalidDevice);
   if (!attr_set[dev]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_attn_bwd_mfma<NT, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_attn_bwd_mfma<NT, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (e != hipSuccess) return LFSR_HIP_ERR(e);
     attr_set[dev] = true;
   }
-  if (n1 == 5) hipLaunchKernelGGL((k_epi_attn_bwd_mfma<NT, 5>), dim3((unsigned)nblk), dim3(64 * NW), smem, st, p);
+  if (g.n1 == 5) hipLaunchKernelGGL((k_epi_attn_bwd_mfma<NT, 5>), dim3((unsigned)nblk), dim3(64 * NW), smem, st, p);
   else hipLaunchKernelGGL((k_epi_attn_bwd_mfma<NT, 0>), dim3((unsigned)nblk), dim3(64 * NW), smem, st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;

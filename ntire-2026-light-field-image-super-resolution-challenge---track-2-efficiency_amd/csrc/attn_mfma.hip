@@ -173,33 +173,32 @@ __global__ __launch_bounds__(512) void k_epi_attn_mfma(EpiAttnArgs p) {
 
 }  // namespace
 
-// LFSR_E_ARG = geometry not covered (the caller falls back to the VALU kernels)
-int lfsr_epi_attn_mfma_launch(const float* q, int q_stride, int q_choff, const float* k, int k_stride, int k_choff, const float* v, int v_stride, int v_choff,
-                              float* o, int o_stride, int o_choff, int nheads, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
-                              int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, hipStream_t st) {
-  const int L = n1 * n2;
-  if (nheads % 4 || L > 160 || L < 1 || l1 < n1 - 1 || r1 < n1) return LFSR_E_ARG;    // every angular position visible; <= 10 tiles of 16 tokens
+// LFSR_E_ARG = geometry not covered (the dispatcher goes on to the next kernel)
+int lfsr_epi_attn_mfma_launch(const LfsrAttn& a, hipStream_t st) {
+  const LfsrAttnGeom& g = a.g;
+  const int L = g.n1 * g.n2;
+  if (a.hd != 16 || a.nheads % 4 || L > 160 || L < 1 || g.l1 < g.n1 - 1 || g.r1 < g.n1) return LFSR_E_ARG;    // every angular position visible; <= 10 tiles of 16 tokens
   EpiAttnArgs p{};
-  p.Q = q; p.q_stride = q_stride; p.q_choff = q_choff; p.K = k; p.k_stride = k_stride; p.k_choff = k_choff;
-  p.V = v; p.v_stride = v_stride; p.v_choff = v_choff; p.O = o; p.o_stride = o_stride; p.o_choff = o_choff;
-  p.nheads = nheads; p.ns1 = ns1; p.ns2 = ns2; p.bs0 = bs0; p.bs1 = bs1; p.bs2 = bs2;
-  p.n1 = n1; p.n2 = n2; p.st1 = st1; p.st2 = st2; p.l2 = l2; p.r2 = r2; p.clip2 = clip2 > 0 ? clip2 : n2;
+  p.Q = a.q; p.q_stride = a.q_stride; p.q_choff = a.q_choff; p.K = a.k; p.k_stride = a.k_stride; p.k_choff = a.k_choff;
+  p.V = a.v; p.v_stride = a.v_stride; p.v_choff = a.v_choff; p.O = a.o; p.o_stride = a.o_stride; p.o_choff = a.o_choff;
+  p.nheads = a.nheads; p.ns1 = g.ns1; p.ns2 = g.ns2; p.bs0 = g.bs0; p.bs1 = g.bs1; p.bs2 = g.bs2;
+  p.n1 = g.n1; p.n2 = g.n2; p.st1 = g.st1; p.st2 = g.st2; p.l2 = g.l2; p.r2 = g.r2; p.clip2 = g.clip2;
   p.scale = (1.0f / sqrtf(16.0f)) * 1.44269504088896340736f;
   p.L = L;
-  const long long nblk = (long long)ns0 * ns1 * ns2 * (nheads / 4);
+  const long long nblk = g.nseq() * (a.nheads / 4);
   if (nblk <= 0 || nblk > 0x7fffffffLL) return LFSR_E_ARG;
   constexpr int NT = 10;
   const int smem = 4 * NT * 16 * 16 * 2 * 4;   // 81920
   static std::atomic<bool> attr_set[64];
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_HIP_ERR(hipErrorInvalidDevice);
   if (!attr_set[dev]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_attn_mfma<NT, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_attn_mfma<NT, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (e != hipSuccess) return LFSR_HIP_ERR(e);
     attr_set[dev] = true;
   }
-  if (n1 == 5) hipLaunchKernelGGL((k_epi_attn_mfma<NT, 5>), dim3((unsigned)nblk), dim3(512), smem, st, p);
+  if (g.n1 == 5) hipLaunchKernelGGL((k_epi_attn_mfma<NT, 5>), dim3((unsigned)nblk), dim3(512), smem, st, p);
   else hipLaunchKernelGGL((k_epi_attn_mfma<NT, 0>), dim3((unsigned)nblk), dim3(512), smem, st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;

@@ -105,11 +105,8 @@ int lfsr_epit_forward_body(const lfsr_epit* c, const float* x, float* out, int B
     float *T = bf.t[j], *QK = bf.qk[j], *V = bf.v[j], *AO = bf.ao[j], *T2 = bf.t2[j], *TF = bf.tf[j];
     LFSR_RC(lfsr_linear_fwd(X, 64, 0, 64, P.w(e + "linear_in.weight"), nullptr, nullptr, 0, 0, T, 128, 0, npix, 128, 1.0f, stream));
     LFSR_RC(lfsr_trans_qkv(sel, P, e, T, 128, nullptr, 1, 1, QK, V, bf.tn, npix, stream));     // q | k from LayerNorm(t), v from t
-    // mask_field = [2A, 11] (EPIT.py:147): all angular positions, spatial window [j-5, j+6)
-    if (!vertical) LFSR_RC(lfsr_window_attn_fwd(QK, 256, 0, QK, 256, 128, V, 128, 0, AO, 128, 0, 8, 16, B, A, w, (long long)AA * HW, HW, 1,
-                                                A, h, (long long)A * HW, w, A, A, 5, 6, 0, stream));      // sequence (b, v, x); tokens (u, y)
-    else LFSR_RC(lfsr_window_attn_fwd(QK, 256, 0, QK, 256, 128, V, 128, 0, AO, 128, 0, 8, 16, B, A, h, (long long)AA * HW, (long long)A * HW, w,
-                                      A, w, HW, 1, A, A, 5, 6, 0, stream));                               // sequence (b, u, y); tokens (v, x)
+    LFSR_RC(lfsr_attn_run(LfsrAttn{QK, 256, 0, QK, 256, 128, V, 128, 0, AO, 128, 0, 8, 16, vertical ? lfsr_attn_geom_epit_v(B, A, h, w) : lfsr_attn_geom_epit_h(B, A, h, w)},
+                          lfsr_stream(stream)));
     LFSR_RC(lfsr_linear_fwd(AO, 128, 0, 128, P.w(e + "attention.out_proj.weight"), nullptr, T, 128, 0, T2, 128, 0, npix, 128, 1.0f, stream));
     LFSR_RC(lfsr_trans_ffn(sel, P, e, T2, 128, c->ffn_split[blk], TF, bf.lnx, bf.hid, npix, stream));
     return lfsr_linear_fwd(TF, 128, 0, 128, P.w(e + "linear_out.weight"), nullptr, nullptr, 0, 0, bf.y[j], 64, 0, npix, 64, 1.0f, stream);

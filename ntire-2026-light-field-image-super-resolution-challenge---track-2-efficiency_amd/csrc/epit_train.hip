@@ -129,7 +129,7 @@ int lfsr_epit_backward(lfsr_epit* c, const float* x, const float* dout, int B, i
   EpitTrainWs t;
   train_layout(c, B, h, w, ws, t);
   if (workspace_bytes < ws.bytes()) return LFSR_E_WS;
-  const int A = c->A, AA = A * A, HW = h * w, nb = c->nblk;
+  const int A = c->A, nb = c->nblk;
   const LfsrParamTable& P = c->P;
   const EpitFwdBufs& f = t.f;
   hipStream_t st = lfsr_stream(stream);
@@ -168,12 +168,10 @@ int lfsr_epit_backward(lfsr_epit* c, const float* x, const float* dout, int B, i
       // ---- BasicTrans (EPIT.py:110-128): y = linear_out(tf), tf = t2 + FFN(LN(t2)), t2 = out_proj(attn) + t, t = linear_in(x) ----
       LFSR_RC(k.dgemm(t.d64, 64, lin[0], t.dsf, 128, nullptr, 0, nullptr, 0, 128));
       LFSR_RC(k.wgrad_lin(t.d64, 64, 64, f.tf[j], 128, 128, k.G(e + "linear_out.weight")));
-      // mask_field = [2A, 11]: the geometry of the forward's launch
-      const LfsrAttnBwd attn = [&](const float* qk, const float* v, const float* o, const float* d_o, float* dqk, float* dv) {
-        if (!vert) return lfsr_window_attn_bwd(qk, 256, 0, 128, v, 128, 0, o, d_o, 128, 0, dqk, dv, t.stats, 8, 16, B, A, w, (long long)AA * HW, HW, 1,
-                                               A, h, (long long)A * HW, w, A, A, 5, 6, 0, stream);
-        return lfsr_window_attn_bwd(qk, 256, 0, 128, v, 128, 0, o, d_o, 128, 0, dqk, dv, t.stats, 8, 16, B, A, h, (long long)AA * HW, (long long)A * HW, w,
-                                    A, w, HW, 1, A, A, 5, 6, 0, stream);
+      // the geometry of the forward's launch; the kernel is the dispatcher's choice (the matrix pipe up to 160 tokens, else the VALU pair)
+      const LfsrAttnBwdCallback attn = [&](const float* qk, const float* v, const float* o, const float* d_o, float* dqk, float* dv) {
+        return lfsr_attn_grad_run(LfsrAttnGrad{qk, 256, 0, 128, v, 128, o, d_o, 128, dqk, dv, t.stats, 8, 16,
+                                               vert ? lfsr_attn_geom_epit_v(B, A, h, w) : lfsr_attn_geom_epit_h(B, A, h, w)}, st);
       };
       LFSR_RC(lfsr_trans_sublayer_bwd(k, e, 128, t.dsf, f.t2[j], f.ao[j], f.qk[j], f.v[j], f.t[j], nullptr, 1, 1, t.hid[j], lin + 1, attn, t.dst, t.dst,
                                       t.dst));                                                                             // dst = dL/d t

@@ -232,10 +232,42 @@ LfsrLinFn lfsr_linear_run, lfsr_linear_ln_run, lfsr_dgrad144_run; LfsrFfnFn lfsr
 size_t lfsr_ffn_b3_presplit_bytes(int K1, int H, int N2);
 int lfsr_ffn_b3_presplit(const float* w1_packed, const float* w2_packed, int K1, int H, int N2, void* out, hipStream_t st);
 
-// attn_mfma.hip: EPI attention on MFMA; LFSR_E_ARG = geometry not covered
-int lfsr_epi_attn_mfma_launch(const float* q, int q_stride, int q_choff, const float* k, int k_stride, int k_choff, const float* v, int v_stride, int v_choff,
-                              float* o, int o_stride, int o_choff, int nheads, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
-                              int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, hipStream_t st);
+// attn.cpp: the windowed attention.  The sequence / window geometry, the parametrisation documented at lfsr_window_attn_fwd (include/lfsr_hip.h): sequence (s0,s1,s2) starts
+// at pixel s0 bs0 + s1 bs1 + s2 bs2, token (t1,t2) sits at + t1 st1 + t2 st2 and attends keys [t1-l1, t1+r1) x [t2-l2, min(t2+r2, clip2, n2)).
+struct LfsrAttnGeom {
+  int ns0, ns1, ns2; long long bs0, bs1, bs2;
+  int n1, n2; long long st1, st2;
+  int l1, r1, l2, r2, clip2;         // every launcher takes a normalised() geometry: clip2 is never 0 (the C ABI's "no clip beyond n2")
+  long long nseq() const { return (long long)ns0 * ns1 * ns2; }
+  long long tokens() const { return (long long)n1 * n2; }
+  LfsrAttnGeom normalised() const { LfsrAttnGeom g = *this; g.clip2 = clip2 > 0 ? clip2 : n2; return g; }
+};
+// the four geometries the models run, a forward and its backward from the same constructor: LFT's AngTrans and SpaTrans, EPIT's horizontal and vertical pass
+LfsrAttnGeom lfsr_attn_geom_lft_ang(int B, int A, int h, int w), lfsr_attn_geom_lft_spa(int nimg, int h, int w), lfsr_attn_geom_epit_h(int B, int A, int h, int w),
+    lfsr_attn_geom_epit_v(int B, int A, int h, int w);
+// One windowed attention o = softmax(q k^T / sqrt(hd) + window mask) v over nheads heads of hd floats; strides and channel offsets in floats, multiples of 4
+struct LfsrAttn {
+  const float* q; int q_stride, q_choff; const float* k; int k_stride, k_choff;
+  const float* v; int v_stride, v_choff; float* o; int o_stride, o_choff;
+  int nheads, hd; LfsrAttnGeom g;
+};
+// ... and its backward: q | k in one buffer (dqk in its layout); O and dO share a row stride; v / o / d_o / dv point at their first channel (dv in v's layout).
+// stats: 4 floats per (pixel, head) of the span the sequences cover, the VALU pair's scratch
+struct LfsrAttnGrad {
+  const float* qk; int qk_stride, q_choff, k_choff; const float* v; int v_stride;
+  const float *o, *d_o; int o_stride; float *dqk, *dv, *stats;
+  int nheads, hd; LfsrAttnGeom g;
+};
+// A launcher launches its own kernel(s) only; LFSR_E_ARG = the call is not covered and nothing was launched or written: the dispatcher goes down its chain.
+using LfsrAttnFn = int(const LfsrAttn& a, hipStream_t st);
+using LfsrAttnGradFn = int(const LfsrAttnGrad& a, hipStream_t st);
+LfsrAttnFn lfsr_epi_attn_mfma_launch, lfsr_win_attn_mfma_launch;   // attn_mfma.hip, win_attn_mfma.hip: EPI attention (<= 160 tokens) and LFT's 5 x 5 window on the matrix pipe, heads of 16
+LfsrAttnFn lfsr_attn_lds16_launch, lfsr_attn_ang8_launch, lfsr_attn_valu_launch;   // transformer.hip: k_window_attn_lds<16, 2>; k_ang_attn_pair | k_window_attn_lds<8, 8>; k_window_attn (every geometry)
+LfsrAttnGradFn lfsr_epi_attn_bwd_mfma_launch, lfsr_attn_bwd_valu_launch;   // attn_bwd_mfma.hip (reads no stats); trans_bwd.hip: the gather pair, one thread per (query, head) and per (key, head), every geometry
+// which kernel runs.  lfsr_attn_sel: LFSR_ATTN=valu, LFSR_ATTN_L1, LFSR_ATTN_ANG=lds | loop | l1 (ang_set: any value), parsed at every call, never cached; the only reader of their characters
+struct LfsrAttnSel { bool valu, l1, ang_set, ang_loop, ang_l1; };
+LfsrAttnSel lfsr_attn_sel();
+LfsrAttnFn lfsr_attn_run; LfsrAttnGradFn lfsr_attn_grad_run;   // what lfsr_window_attn_fwd / _bwd run behind their argument checks; op timers "window_attn" / "window_attn_bwd"
 // trans_bwd.hip: what the backward drivers of LFT and EPIT share.  LFSR_RED_BLOCKS: the fixed grid of the kernels that write per-block partials (a fixed order for every geometry)
 #define LFSR_RED_BLOCKS 1024
 // d = (a (+ b)) * (mk > 0 ? 1 : slope) over C columns (C % 4 == 0); b, mk optional; a and d may alias
@@ -247,19 +279,6 @@ int lfsr_ln_bwd_launch(int C, const float* x, const float* pe, long long pe_rows
 int lfsr_tail_bwd_launch(const float* dout, const float* w3, const float* hr, float* du, float* part, float* dw3, int B, int A, int h, int w, int S, float slope,
                          hipStream_t st);
 int lfsr_pack_up0_T_launch(const float* Wp, float* out, int s2, hipStream_t st);   // dgrad pack of upsampling.0 from its forward (perm 1) pack
-// the windowed attention backward on the VALU, any geometry of lfsr_window_attn_fwd (q | k in one buffer; O and dO share a row stride; v / o / dO / dv
-// point at their first channel).  Two gathers, one thread per (query, head) and one per (key, head); stats: 4 floats per (pixel, head) of the span the sequences cover
-int lfsr_attn_bwd_valu_launch(int hd, const float* qk, int qk_stride, int q_choff, int k_choff, const float* v, int v_stride, const float* o, const float* d_o,
-                              int o_stride, float* dqk, float* dv, float* stats, int nheads, int ns0, int ns1, int ns2, long long bs0, long long bs1,
-                              long long bs2, int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, hipStream_t st);
-// attn_bwd_mfma.hip: the EPI attention backward on MFMA (heads of 16); LFSR_E_ARG = geometry not covered
-int lfsr_epi_attn_bwd_mfma_launch(const float* qk, int qk_stride, int q_choff, int k_choff, const float* v, int v_stride, const float* o, const float* d_o,
-                                  int o_stride, float* dqk, float* dv, int nheads, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
-                                  int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, hipStream_t st);
-// win_attn_mfma.hip: 5 x 5 spatial window attention (LFT) on the matrix pipe; LFSR_E_ARG = geometry not covered
-int lfsr_win_attn_mfma_launch(const float* q, int q_stride, int q_choff, const float* k, int k_stride, int k_choff, const float* v, int v_stride, int v_choff,
-                              float* o, int o_stride, int o_choff, int nheads, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
-                              int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, hipStream_t st);
 
 // wgrad.hip
 int lfsr_wgrad_splits(int M, int ntaps, int K);
@@ -400,13 +419,13 @@ int lfsr_trans_tail_bwd(const LfsrTransBwd& k, const float* dout, const float* x
 // lfsr_trans_head in reverse: from dbuf0 = dL/d buf0 and the saved f0 / c1 / c2; writes the four conv_init* gradients
 int lfsr_trans_head_bwd(const LfsrTransBwd& k, const float* x, const float* f0, const float* c1, const float* c2, const float* dbuf0);
 // the attention backward of a sublayer, the driver's choice of kernel and geometry: (q | k, v, o, d_o) -> (dqk, dv)
-using LfsrAttnBwd = std::function<int(const float* qk, const float* v, const float* o, const float* d_o, float* dqk, float* dv)>;
+using LfsrAttnBwdCallback = std::function<int(const float* qk, const float* v, const float* o, const float* d_o, float* dqk, float* dv)>;
 // lfsr_trans_ffn and lfsr_trans_qkv in reverse, one attention + feed-forward sublayer of width E (key prefix `pre`), from dy = dL/d y to the token:
 //   y = x2 + FFN(LayerNorm(x2)), x2 = out_proj(ao) + tok, ao = attention(q | k, v), q | k = LayerNorm(tok + pe) W[0:2E]^T, v = tok W[2E:3E]^T.
 // hid (2E) receives the hidden rows after the ReLU, rebuilt; lin: the five dgrad packs of lfsr_trans_sublayer_packs.  dtok = dL/d x2 + the v path's
 // share of dL/d tok; ln_dx = the norm's share (+ ln_r, which may alias it).
 int lfsr_trans_sublayer_bwd(const LfsrTransBwd& k, const std::string& pre, int E, const float* dy, const float* x2, const float* ao, const float* qk,
                             const float* v, const float* tok, const float* pe, long long pe_rows, long long pe_div, float* hid, float* const* lin,
-                            const LfsrAttnBwd& attn, float* dtok, const float* ln_r, float* ln_dx);
+                            const LfsrAttnBwdCallback& attn, float* dtok, const float* ln_r, float* ln_dx);
 // ... and its 1x1 dgrad packs [C_in][O]: feed_forward.4, feed_forward.1, out_proj and the q | k and v rows of in_proj_weight into lin[0..4]
 int lfsr_trans_sublayer_packs(const LfsrTransBwd& k, const std::string& pre, int E, float* const* lin);

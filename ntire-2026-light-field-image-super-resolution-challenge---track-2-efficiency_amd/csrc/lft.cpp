@@ -130,8 +130,7 @@ int lfsr_lft_forward_body(const lfsr_lft* c, const float* x, float* out, int B, 
     // ---- AngTrans (LFT.py:233-246): tokens = the A*A views at one (y, x); E = 64, 8 heads of 8, no mask -----------
     std::string an = "altblock." + std::to_string(b) + ".ang_trans.";
     LFSR_RC(lfsr_trans_qkv(sel, P, an, cur, 64, APE, AA, HW, AQK, AV, N64, npix, stream));    // q | k from LayerNorm(token + PE), v from the raw token
-    LFSR_RC(lfsr_window_attn_fwd(AQK, 128, 0, AQK, 128, 64, AV, 64, 0, AO, 64, 0, 8, 8, B, h, w, (long long)AA * HW, w, 1,
-                                 AA, 1, HW, 0, AA, AA, 0, 1, 0, stream));
+    LFSR_RC(lfsr_attn_run(LfsrAttn{AQK, 128, 0, AQK, 128, 64, AV, 64, 0, AO, 64, 0, 8, 8, lfsr_attn_geom_lft_ang(B, A, h, w)}, lfsr_stream(stream)));
     LFSR_RC(lfsr_linear_fwd(AO, 64, 0, 64, P.w(an + "attention.out_proj.weight"), nullptr, cur, 64, 0, AM, 64, 0, npix, 64, 1.0f, stream));     // + token
     LFSR_RC(lfsr_trans_ffn(sel, P, an, AM, 64, c->ffn_split_ang[b], AY, N64, HA, npix, stream));
     // ---- SpaTrans (LFT.py:188-203): tokens = the h*w positions of one view; E = 128, 8 heads of 16, 5x5 window --------
@@ -140,8 +139,7 @@ int lfsr_lft_forward_body(const lfsr_lft* c, const float* x, float* out, int B, 
     LFSR_RC(lfsr_conv3x3_fwd(AY, 64, 0, P.w(sp + "MLP.weight#hi"), ST, 128, 64, nullptr, 0, 0, nullptr, 0, 0, nimg, h, w, 1.0f, stream));  // as two 64-output convs
     LFSR_RC(lfsr_conv3x3_n_fwd(SPOS, 64, 0, P.w(sp + "MLP.weight"), SPE, 128, 0, 1, h, w, 128, 1.0f, stream));              // same embedding of the PE map
     LFSR_RC(lfsr_trans_qkv(sel, P, sp, ST, 128, SPE, HW, 1, SQK, SV, TN, npix, stream));
-    // window [i-2, i+3) x [j-2, min(h, j+3)): the column clamp uses h (LFT.py:168)
-    LFSR_RC(lfsr_window_attn_fwd(SQK, 256, 0, SQK, 256, 128, SV, 128, 0, SO, 128, 0, 8, 16, nimg, 1, 1, HW, 0, 0, h, w, w, 1, 2, 3, 2, 3, h, stream));
+    LFSR_RC(lfsr_attn_run(LfsrAttn{SQK, 256, 0, SQK, 256, 128, SV, 128, 0, SO, 128, 0, 8, 16, lfsr_attn_geom_lft_spa(nimg, h, w)}, lfsr_stream(stream)));
     LFSR_RC(lfsr_linear_fwd(SO, 128, 0, 128, P.w(sp + "attention.out_proj.weight"), nullptr, ST, 128, 0, SM, 128, 0, npix, 128, 1.0f, stream));
     LFSR_RC(lfsr_trans_ffn(sel, P, sp, SM, 128, c->ffn_split_spa[b], SF, LNF, HS, npix, stream));
     // Conv3d 1x1x1 128 -> 64 (LFT.py:183-186); the network-level skip (LFT.py:91) rides on the last layer's projection

@@ -75,13 +75,12 @@ void train_layout(const lfsr_lft* c, int B, int h, int w, LfsrArena& ws, LftTrai
   for (float*& l : t.lin) l = ws.take(256 * 128);       // the largest: [128][256]
 }
 
-// a sublayer's attention backward: the VALU pair on rows of width E (q | k in rows of 2 E, 8 heads of hd floats), with the sequence / window
-// geometry of the forward's launch
-LfsrAttnBwd attn_bwd(int E, int hd, float4* stats, hipStream_t st, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2, int n1, int n2,
-                     long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2) {
+// a sublayer's attention backward on rows of width E (q | k in rows of 2 E, 8 heads of hd floats), with the sequence / window geometry of the forward's
+// launch.  The VALU pair directly, not lfsr_attn_grad_run: the dispatcher would hand the spatial geometry to k_epi_attn_bwd_mfma whenever h <= 3
+// (every row visible, <= 160 tokens) and change those gradients' bits
+LfsrAttnBwdCallback attn_bwd(int E, int hd, float4* stats, hipStream_t st, const LfsrAttnGeom& g) {
   return [=](const float* qk, const float* v, const float* o, const float* d_o, float* dqk, float* dv) {
-    return lfsr_attn_bwd_valu_launch(hd, qk, 2 * E, 0, E, v, E, o, d_o, E, dqk, dv, reinterpret_cast<float*>(stats), 8, ns0, ns1, ns2, bs0, bs1, bs2,
-                                     n1, n2, st1, st2, l1, r1, l2, r2, clip2, st);
+    return lfsr_attn_bwd_valu_launch(LfsrAttnGrad{qk, 2 * E, 0, E, v, E, o, d_o, E, dqk, dv, reinterpret_cast<float*>(stats), 8, hd, g}, st);
   };
 }
 
@@ -178,10 +177,9 @@ int lfsr_lft_backward(lfsr_lft* c, const float* x, const float* dout, int B, int
     // ---- SpaTrans (LFT.py:188-203): x[b+1] = linear.0(sf), sf = sm + FFN(LN(sm)), sm = out_proj(attn) + st ----------------------
     LFSR_RC(k.dgemm(dX, 64, lin[0], t.dsf, 128, nullptr, 0, nullptr, 0, 128));
     LFSR_RC(k.wgrad_lin(dX, 64, 64, f.sf[b], 128, 128, k.G(sp + "linear.0.weight")));
-    // window [i-2, i+3) x [j-2, min(h, j+3)): the column clamp uses h (LFT.py:168), as the forward.  q | k = LN(st + spe) W[0:256]^T: the
-    // LayerNorm's input gradient goes to dln2, dst = the rest of dL/d st
+    // the forward's window (lfsr_attn_geom_lft_spa).  q | k = LN(st + spe) W[0:256]^T: the LayerNorm's input gradient goes to dln2, dst = the rest of dL/d st
     LFSR_RC(lfsr_trans_sublayer_bwd(k, sp, 128, t.dsf, f.sm[b], f.so[b], f.sqk[b], f.sv[b], f.st[b], f.spe[b], HW, 1, t.hid_s[b], lin + 1,
-                                    attn_bwd(128, 16, t.stats, st, nimg, 1, 1, HW, 0, 0, h, w, w, 1, 2, 3, 2, 3, h), t.dst, nullptr, t.dln2));
+                                    attn_bwd(128, 16, t.stats, st, lfsr_attn_geom_lft_spa(nimg, h, w)), t.dst, nullptr, t.dln2));
     LFSR_RC(k.ew(128, t.dst, t.dln2, nullptr, 1.0f, t.dst));
     // st = MLP(unfold(ay)), spe = MLP(unfold(spa_position)): MLP.weight also gets the LayerNorm-input gradient summed over the images
     hipLaunchKernelGGL(k_pe_reduce, dim3(lfsr_blocks((long long)HW * 128, 256)), dim3(256), 0, st, t.dln2, t.dspe, nimg, HW);
@@ -198,7 +196,7 @@ int lfsr_lft_backward(lfsr_lft* c, const float* x, const float* dout, int B, int
     // ---- AngTrans (LFT.py:233-246): ay = am + FFN(LN(am)), am = out_proj(attn) + x[b], q | k = LN(x[b] + ape) W[0:128]^T ------------------
     float* dXp = t.dx[(nl - b) & 1];
     LFSR_RC(lfsr_trans_sublayer_bwd(k, an, 64, t.t64, f.am[b], f.ao[b], f.aqk[b], f.av[b], f.x[b], f.ape, AA, HW, t.hid_a[b], lin + 6,
-                                    attn_bwd(64, 8, t.stats, st, B, h, w, (long long)AA * HW, w, 1, AA, 1, HW, 0, AA, AA, 0, 1, 0), dXp, dXp, dXp));
+                                    attn_bwd(64, 8, t.stats, st, lfsr_attn_geom_lft_ang(B, A, h, w)), dXp, dXp, dXp));
     dX = dXp;
   }
 

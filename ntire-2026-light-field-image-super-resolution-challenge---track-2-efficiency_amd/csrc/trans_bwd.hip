@@ -1,7 +1,7 @@
 // What the backward drivers of LFT (lft_train.hip) and EPIT (epit_train.hip) share beyond the gather-GEMMs and wgrad.hip: the elementwise
-// add / mask, the LayerNorm backward, the up-sampling tail's backward, and the windowed attention backward -- the operator entry
-// lfsr_window_attn_bwd and the VALU pair every geometry can run on (LFT's angular and spatial attention; EPIT's EPI attention outside the
-// coverage of attn_bwd_mfma.hip).  Every reduction runs in a fixed order: gradient buckets are bitwise reproducible.  After the kernels
+// add / mask, the LayerNorm backward, the up-sampling tail's backward, and the windowed attention backward's VALU pair, which every
+// geometry can run on (LFT's angular and spatial attention; EPIT's EPI attention outside the coverage of attn_bwd_mfma.hip; attn.cpp
+// picks).  Every reduction runs in a fixed order: gradient buckets are bitwise reproducible.  After the kernels
 // and their launchers comes the drivers' shared host code: the context the two drivers are written in (LfsrTransBwd) and the three stages that
 // are the same graph in both models, the mirror of transformer.hip's lfsr_trans_head / _qkv / _ffn / _tail.
 #include <math.h>
@@ -352,44 +352,24 @@ int lfsr_pack_up0_T_launch(const float* Wp, float* out, int s2, hipStream_t st) 
   return LFSR_OK;
 }
 
-int lfsr_attn_bwd_valu_launch(int hd, const float* qk, int qk_stride, int q_choff, int k_choff, const float* v, int v_stride, const float* o, const float* d_o,
-                              int o_stride, float* dqk, float* dv, float* stats, int nheads, int ns0, int ns1, int ns2, long long bs0, long long bs1,
-                              long long bs2, int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, hipStream_t st) {
+int lfsr_attn_bwd_valu_launch(const LfsrAttnGrad& a, hipStream_t st) {
+  const LfsrAttnGeom& g = a.g;
+  if (a.hd != 8 && a.hd != 16) return LFSR_E_ARG;
   AttnBwdArgs p{};
-  p.Q = qk; p.K = qk; p.qk_stride = qk_stride; p.q_choff = q_choff; p.k_choff = k_choff; p.V = v; p.v_stride = v_stride; p.O = o; p.dO = d_o; p.o_stride = o_stride;
-  p.dQK = dqk; p.dV = dv; p.stats = reinterpret_cast<float4*>(stats); p.nheads = nheads;
-  p.ns1 = ns1; p.ns2 = ns2; p.bs0 = bs0; p.bs1 = bs1; p.bs2 = bs2; p.n1 = n1; p.n2 = n2; p.st1 = st1; p.st2 = st2;
-  p.l1 = l1; p.r1 = r1; p.l2 = l2; p.r2 = r2; p.clip2 = clip2 > 0 ? clip2 : n2;
-  p.scale = 1.0f / sqrtf((float)hd);
-  p.total = (long long)ns0 * ns1 * ns2 * n1 * n2 * nheads;
+  p.Q = a.qk; p.K = a.qk; p.qk_stride = a.qk_stride; p.q_choff = a.q_choff; p.k_choff = a.k_choff; p.V = a.v; p.v_stride = a.v_stride; p.O = a.o; p.dO = a.d_o;
+  p.o_stride = a.o_stride; p.dQK = a.dqk; p.dV = a.dv; p.stats = reinterpret_cast<float4*>(a.stats); p.nheads = a.nheads;
+  p.ns1 = g.ns1; p.ns2 = g.ns2; p.bs0 = g.bs0; p.bs1 = g.bs1; p.bs2 = g.bs2; p.n1 = g.n1; p.n2 = g.n2; p.st1 = g.st1; p.st2 = g.st2;
+  p.l1 = g.l1; p.r1 = g.r1; p.l2 = g.l2; p.r2 = g.r2; p.clip2 = g.clip2;
+  p.scale = 1.0f / sqrtf((float)a.hd);
+  p.total = g.nseq() * g.tokens() * a.nheads;
   const unsigned grid = lfsr_blocks(p.total, 256);
-  if (hd == 8) hipLaunchKernelGGL(k_attn_bwd_q<8>, dim3(grid), dim3(256), 0, st, p);
+  if (a.hd == 8) hipLaunchKernelGGL(k_attn_bwd_q<8>, dim3(grid), dim3(256), 0, st, p);
   else hipLaunchKernelGGL(k_attn_bwd_q<16>, dim3(grid), dim3(256), 0, st, p);
   LFSR_CHECK_LAUNCH();
-  if (hd == 8) hipLaunchKernelGGL(k_attn_bwd_kv<8>, dim3(grid), dim3(256), 0, st, p);
+  if (a.hd == 8) hipLaunchKernelGGL(k_attn_bwd_kv<8>, dim3(grid), dim3(256), 0, st, p);
   else hipLaunchKernelGGL(k_attn_bwd_kv<16>, dim3(grid), dim3(256), 0, st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
-}
-
-extern "C" int lfsr_window_attn_bwd(const float* qk, int qk_stride, int q_choff, int k_choff, const float* v, int v_stride, int v_choff, const float* o,
-                                    const float* d_o, int o_stride, int o_choff, float* dqk, float* dv, float* stats, int nheads, int hd,
-                                    int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
-                                    int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, void* stream) {
-  LfsrOpTimer op_t("window_attn_bwd", hd, n1 * n2, lfsr_stream(stream));
-  if (!qk || !v || !o || !d_o || !dqk || !dv || !stats || nheads <= 0 || (hd != 8 && hd != 16) || ns0 <= 0 || ns1 <= 0 || ns2 <= 0 || n1 <= 0 || n2 <= 0) return LFSR_E_ARG;
-  if ((qk_stride | q_choff | k_choff | v_stride | v_choff | o_stride | o_choff) & 3) return LFSR_E_ARG;
-  if ((long long)ns0 * ns1 * ns2 * n1 * n2 * nheads > 0x7fffffffLL * 256) return LFSR_E_ARG;
-  v += v_choff; dv += v_choff; o += o_choff; d_o += o_choff;
-  // EPI geometry (as the forward's dispatch): the matrix-pipe kernel of attn_bwd_mfma.hip, which needs no statistics; LFSR_ATTN=valu keeps the VALU pair (A/B runs)
-  const char* asel = lfsr_sel("LFSR_ATTN");
-  if (hd == 16 && !(asel && asel[0] == 'v')) {
-    const int rc = lfsr_epi_attn_bwd_mfma_launch(qk, qk_stride, q_choff, k_choff, v, v_stride, o, d_o, o_stride, dqk, dv, nheads, ns0, ns1, ns2, bs0, bs1, bs2,
-                                                 n1, n2, st1, st2, l1, r1, l2, r2, clip2, lfsr_stream(stream));
-    if (rc != LFSR_E_ARG) return rc;
-  }
-  return lfsr_attn_bwd_valu_launch(hd, qk, qk_stride, q_choff, k_choff, v, v_stride, o, d_o, o_stride, dqk, dv, stats, nheads, ns0, ns1, ns2, bs0, bs1, bs2,
-                                   n1, n2, st1, st2, l1, r1, l2, r2, clip2, lfsr_stream(stream));
 }
 
 namespace {
@@ -588,7 +568,7 @@ int lfsr_trans_sublayer_packs(const LfsrTransBwd& k, const std::string& pre, int
 
 int lfsr_trans_sublayer_bwd(const LfsrTransBwd& k, const std::string& pre, int E, const float* dy, const float* x2, const float* ao, const float* qk,
                             const float* v, const float* tok, const float* pe, long long pe_rows, long long pe_div, float* hid, float* const* lin,
-                            const LfsrAttnBwd& attn, float* dtok, const float* ln_r, float* ln_dx) {
+                            const LfsrAttnBwdCallback& attn, float* dtok, const float* ln_r, float* ln_dx) {
   const LfsrParamTable& P = k.P;
   const LfsrTransBwdWs& s = k.ws;
   // the feed-forward: its LayerNorm (into lnt) and hidden rows are recomputed

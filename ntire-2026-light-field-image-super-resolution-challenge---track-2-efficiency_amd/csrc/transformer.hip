@@ -433,7 +433,92 @@ __global__ void k_lft_position(float* __restrict__ spa_pe, float* __restrict__ a
   }
 }
 
+AttnArgs attn_args(const LfsrAttn& a) {
+  const LfsrAttnGeom& g = a.g;
+  AttnArgs p{};
+  p.Q = a.q; p.q_stride = a.q_stride; p.q_choff = a.q_choff; p.K = a.k; p.k_stride = a.k_stride; p.k_choff = a.k_choff;
+  p.V = a.v; p.v_stride = a.v_stride; p.v_choff = a.v_choff; p.O = a.o; p.o_stride = a.o_stride; p.o_choff = a.o_choff;
+  p.nheads = a.nheads; p.ns0 = g.ns0; p.ns1 = g.ns1; p.ns2 = g.ns2; p.bs0 = g.bs0; p.bs1 = g.bs1; p.bs2 = g.bs2;
+  p.n1 = g.n1; p.n2 = g.n2; p.st1 = g.st1; p.st2 = g.st2; p.l1 = g.l1; p.r1 = g.r1; p.l2 = g.l2; p.r2 = g.r2; p.clip2 = g.clip2;
+  p.scale = 1.0f / sqrtf((float)a.hd);
+  p.scale2 = p.scale * 1.44269504088896340736f;
+  p.total = g.nseq() * g.tokens() * a.nheads;
+  return p;
+}
+
 }  // namespace
+
+// ---- the VALU launchers of the windowed attention (lfsr_attn_run, attn.cpp, tries them after the matrix-pipe kernels of attn_mfma.hip / win_attn_mfma.hip) ----
+// LDS-tiled path (hd 16, heads in pairs): stage the keys a tile of queries can see once; used when the staged tile fits
+int lfsr_attn_lds16_launch(const LfsrAttn& a, hipStream_t st) {
+  const LfsrAttnGeom& g = a.g;
+  if (a.hd != 16 || a.nheads % 2) return LFSR_E_ARG;
+  constexpr int HB = 2, TS = HB * 32 + 4;
+  int T1 = g.n1;                                            // whole sequence if it fits (EPIT: 5 x 32 tokens)
+  auto smem_for = [&](int t1) { int rows = t1 + g.l1 + g.r1 - 1; if (rows > g.n1) rows = g.n1; return (size_t)rows * g.n2 * TS * 4; };
+  while (T1 > 1 && smem_for(T1) > 96 * 1024) T1 = (T1 + 1) / 2;
+  if (smem_for(T1) > 150 * 1024) return LFSR_E_ARG;
+  const int ntile1 = (g.n1 + T1 - 1) / T1;
+  size_t smem = smem_for(T1);
+  static std::atomic<bool> attr_set[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && !attr_set[dev]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_window_attn_lds<16, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    if (e != hipSuccess) return LFSR_HIP_ERR(e);
+    attr_set[dev] = true;
+  }
+  int threads = T1 * g.n2 * HB;
+  threads = (threads + 63) / 64 * 64;
+  if (threads > 1024) threads = 1024;
+  dim3 grid((unsigned)(g.nseq() * ntile1), (unsigned)(a.nheads / HB));
+  hipLaunchKernelGGL((k_window_attn_lds<16, 2>), grid, dim3(threads), smem, st, attn_args(a), T1, ntile1);
+  LFSR_CHECK_LAUNCH();
+  return LFSR_OK;
+}
+
+// heads of 8, all eight in one block, whole (short) sequences: LFT's angular attention (25 views per pixel).  One block per sequence stages its 25 x (k | v) rows
+// once; the L1-served kernel re-reads them for every query (it ran at the L1's 64 B/clk: 0.43 ms per launch at 32 patches).  LFSR_ATTN_ANG=l1 keeps it (A/B runs)
+int lfsr_attn_ang8_launch(const LfsrAttn& a, hipStream_t st) {
+  const LfsrAttnGeom& g = a.g;
+  if (a.hd != 8 || a.nheads != 8 || g.n2 != 1 || g.l1 < g.n1 || g.r1 < g.n1 || g.n1 > 64) return LFSR_E_ARG;
+  const LfsrAttnSel sel = lfsr_attn_sel();
+  if (g.n1 == 25 && !sel.ang_set) {      // A = 5: two queries per thread, two-pass softmax, four pixels per 512-thread block (two pixels per 256-thread block: 220 against 213 us) (LFSR_ATTN_ANG=lds / loop / l1: the earlier forms)
+    constexpr int AP = 4, NTH = 512, TS8 = 8 * 20 + 4;
+    constexpr int smem = AP * 25 * TS8 * 4 + AP * 8;
+    static std::atomic<bool> attr_set[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_HIP_ERR(hipErrorInvalidDevice);
+    if (!attr_set[dev]) {
+      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ang_attn_pair<25, AP, NTH>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+      if (e != hipSuccess) return LFSR_HIP_ERR(e);
+      attr_set[dev] = true;
+    }
+    const long long nseq = g.nseq();
+    hipLaunchKernelGGL((k_ang_attn_pair<25, AP, NTH>), dim3((unsigned)((nseq + AP - 1) / AP)), dim3(NTH), smem, st, attn_args(a), nseq);
+    LFSR_CHECK_LAUNCH();
+    return LFSR_OK;
+  }
+  if (sel.ang_l1) return LFSR_E_ARG;
+  AttnArgs p = attn_args(a);
+  p.loop_stage = sel.ang_loop;
+  constexpr int TS8 = 8 * 20 + 4;
+  const size_t smem = (size_t)g.n1 * TS8 * 4;
+  int threads = (g.n1 * 8 + 63) / 64 * 64;
+  dim3 grid((unsigned)g.nseq(), 1);
+  hipLaunchKernelGGL((k_window_attn_lds<8, 8>), grid, dim3(threads), smem, st, p, g.n1, 1);
+  LFSR_CHECK_LAUNCH();
+  return LFSR_OK;
+}
+
+int lfsr_attn_valu_launch(const LfsrAttn& a, hipStream_t st) {
+  if (a.hd != 8 && a.hd != 16) return LFSR_E_ARG;
+  const AttnArgs p = attn_args(a);
+  unsigned grid = lfsr_blocks(p.total, 256);
+  if (a.hd == 8) hipLaunchKernelGGL((k_window_attn<8>), dim3(grid), dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((k_window_attn<16>), dim3(grid), dim3(256), 0, st, p);
+  LFSR_CHECK_LAUNCH();
+  return LFSR_OK;
+}
 
 extern "C" {
 
@@ -447,99 +532,6 @@ int lfsr_layernorm_fwd(const float* x, int x_stride, int x_choff, const float* p
   if (grid > 256u * 32) grid = 256u * 32;
   if (C == 64) hipLaunchKernelGGL((k_layernorm<64>), dim3(grid), dim3(256), 0, lfsr_stream(stream), x, x_stride, x_choff, pe, pe_stride, pe_rows, pe_div, gamma, beta, y, y_stride, y_choff, M, eps);
   else hipLaunchKernelGGL((k_layernorm<128>), dim3(grid), dim3(256), 0, lfsr_stream(stream), x, x_stride, x_choff, pe, pe_stride, pe_rows, pe_div, gamma, beta, y, y_stride, y_choff, M, eps);
-  LFSR_CHECK_LAUNCH();
-  return LFSR_OK;
-}
-
-int lfsr_window_attn_fwd(const float* q, int q_stride, int q_choff, const float* k, int k_stride, int k_choff, const float* v, int v_stride, int v_choff,
-                         float* o, int o_stride, int o_choff, int nheads, int hd,
-                         int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
-                         int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, void* stream) {
-  LfsrOpTimer op_t("window_attn", hd, n1 * n2, lfsr_stream(stream));
-  if (!q || !k || !v || !o || nheads <= 0 || (hd != 8 && hd != 16) || ns0 <= 0 || ns1 <= 0 || ns2 <= 0 || n1 <= 0 || n2 <= 0) return LFSR_E_ARG;
-  if ((q_stride | q_choff | k_stride | k_choff | v_stride | v_choff | o_stride | o_choff) & 3) return LFSR_E_ARG;
-  AttnArgs p{};
-  p.Q = q; p.q_stride = q_stride; p.q_choff = q_choff; p.K = k; p.k_stride = k_stride; p.k_choff = k_choff;
-  p.V = v; p.v_stride = v_stride; p.v_choff = v_choff; p.O = o; p.o_stride = o_stride; p.o_choff = o_choff;
-  p.nheads = nheads; p.ns0 = ns0; p.ns1 = ns1; p.ns2 = ns2; p.bs0 = bs0; p.bs1 = bs1; p.bs2 = bs2;
-  p.n1 = n1; p.n2 = n2; p.st1 = st1; p.st2 = st2; p.l1 = l1; p.r1 = r1; p.l2 = l2; p.r2 = r2; p.clip2 = clip2 > 0 ? clip2 : n2;
-  p.scale = 1.0f / sqrtf((float)hd);
-  p.scale2 = p.scale * 1.44269504088896340736f;
-  p.total = (long long)ns0 * ns1 * ns2 * n1 * n2 * nheads;
-  // EPI geometry (every angular position visible, <= 160 tokens per sequence, heads of 16): QK^T / softmax / PV on the matrix pipe
-  // (attn_mfma.hip); LFSR_ATTN=valu keeps the VALU kernels below (A/B runs)
-  {
-    const char* asel = lfsr_sel("LFSR_ATTN");
-    if (hd == 16 && !(asel && asel[0] == 'v') && !lfsr_sel("LFSR_ATTN_L1")) {
-      const int rc = lfsr_epi_attn_mfma_launch(q, q_stride, q_choff, k, k_stride, k_choff, v, v_stride, v_choff, o, o_stride, o_choff, nheads, ns0, ns1, ns2,
-                                               bs0, bs1, bs2, n1, n2, st1, st2, l1, r1, l2, r2, clip2, lfsr_stream(stream));
-      if (rc != LFSR_E_ARG) return rc;
-    }
-    // 5 x 5 spatial windows (LFT's SpaTrans): tiles of 4 x 4 queries against the 8 x 8 keys around them on the matrix pipe (win_attn_mfma.hip)
-    if (hd == 16 && !(asel && asel[0] == 'v') && !lfsr_sel("LFSR_ATTN_L1")) {
-      const int rc = lfsr_win_attn_mfma_launch(q, q_stride, q_choff, k, k_stride, k_choff, v, v_stride, v_choff, o, o_stride, o_choff, nheads, ns0, ns1, ns2,
-                                               bs0, bs1, bs2, n1, n2, st1, st2, l1, r1, l2, r2, clip2, lfsr_stream(stream));
-      if (rc != LFSR_E_ARG) return rc;
-    }
-  }
-  // LDS-tiled path (hd 16, heads in pairs): stage the keys a tile of queries can see once; used when the staged tile fits
-  if (hd == 16 && nheads % 2 == 0 && !lfsr_sel("LFSR_ATTN_L1")) {
-    constexpr int HB = 2, TS = HB * 32 + 4;
-    int T1 = n1;                                            // whole sequence if it fits (EPIT: 5 x 32 tokens)
-    auto smem_for = [&](int t1) { int rows = t1 + l1 + r1 - 1; if (rows > n1) rows = n1; return (size_t)rows * n2 * TS * 4; };
-    while (T1 > 1 && smem_for(T1) > 96 * 1024) T1 = (T1 + 1) / 2;
-    if (smem_for(T1) <= 150 * 1024) {
-      const int ntile1 = (n1 + T1 - 1) / T1;
-      size_t smem = smem_for(T1);
-      static std::atomic<bool> attr_set[64];
-      int dev = 0;
-      if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 && !attr_set[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_window_attn_lds<16, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return LFSR_E_ARG;
-        attr_set[dev] = true;
-      }
-      int threads = T1 * n2 * HB;
-      threads = (threads + 63) / 64 * 64;
-      if (threads > 1024) threads = 1024;
-      dim3 grid((unsigned)((long long)ns0 * ns1 * ns2 * ntile1), (unsigned)(nheads / HB));
-      hipLaunchKernelGGL((k_window_attn_lds<16, 2>), grid, dim3(threads), smem, lfsr_stream(stream), p, T1, ntile1);
-      LFSR_CHECK_LAUNCH();
-      return LFSR_OK;
-    }
-  }
-  // heads of 8, all eight in one block, whole (short) sequences: LFT's angular attention (25 views per pixel).  One block per sequence stages its 25 x (k | v) rows
-  // once; the L1-served kernel below re-reads them for every query (it ran at the L1's 64 B/clk: 0.43 ms per launch at 32 patches).  LFSR_ATTN_ANG=l1 keeps it (A/B runs)
-  if (hd == 8 && nheads == 8 && n2 == 1 && l1 >= n1 && r1 >= n1 && n1 <= 64 && !lfsr_sel("LFSR_ATTN_L1")) {
-    const char* asel = lfsr_sel("LFSR_ATTN_ANG");
-    if (n1 == 25 && !asel) {      // A = 5: two queries per thread, two-pass softmax, four pixels per 512-thread block (two pixels per 256-thread block: 220 against 213 us) (LFSR_ATTN_ANG=lds / loop / l1: the earlier forms)
-      constexpr int AP = 4, NTH = 512, TS8 = 8 * 20 + 4;
-      constexpr int smem = AP * 25 * TS8 * 4 + AP * 8;
-      static std::atomic<bool> attr_set[64];
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
-      if (!attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ang_attn_pair<25, AP, NTH>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-        if (e != hipSuccess) return LFSR_HIP_ERR(e);
-        attr_set[dev] = true;
-      }
-      const long long nseq = (long long)ns0 * ns1 * ns2;
-      hipLaunchKernelGGL((k_ang_attn_pair<25, AP, NTH>), dim3((unsigned)((nseq + AP - 1) / AP)), dim3(NTH), smem, lfsr_stream(stream), p, nseq);
-      LFSR_CHECK_LAUNCH();
-      return LFSR_OK;
-    }
-    if (!(asel && asel[0] == 'l' && asel[1] == '1')) {
-      p.loop_stage = asel && asel[0] == 'l' && asel[1] == 'o';
-      constexpr int TS8 = 8 * 20 + 4;
-      const size_t smem = (size_t)n1 * TS8 * 4;
-      int threads = (n1 * 8 + 63) / 64 * 64;
-      dim3 grid((unsigned)((long long)ns0 * ns1 * ns2), 1);
-      hipLaunchKernelGGL((k_window_attn_lds<8, 8>), grid, dim3(threads), smem, lfsr_stream(stream), p, n1, 1);
-      LFSR_CHECK_LAUNCH();
-      return LFSR_OK;
-    }
-  }
-  unsigned grid = lfsr_blocks(p.total, 256);
-  if (hd == 8) hipLaunchKernelGGL((k_window_attn<8>), dim3(grid), dim3(256), 0, lfsr_stream(stream), p);
-  else hipLaunchKernelGGL((k_window_attn<16>), dim3(grid), dim3(256), 0, lfsr_stream(stream), p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }

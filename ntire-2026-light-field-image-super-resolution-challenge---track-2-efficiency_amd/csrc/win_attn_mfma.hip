@@ -13,6 +13,8 @@
 // groups), V^T [d][row][col] with a d pitch of 484 floats (the 16 lanes of an A-operand read hit 16 distinct 16-B slots) -- 60 KB, two blocks per CU.
 #include <math.h>
 
+#include <algorithm>
+
 #include "lfsr_internal.h"
 
 typedef float f32x4q __attribute__((ext_vector_type(4)));
@@ -234,35 +236,33 @@ __global__ __launch_bounds__(256) void k_win_attn_mfma(WinAttnArgs p) {
 
 }  // namespace
 
-// LFSR_E_ARG = geometry not covered (the caller keeps the VALU kernels): heads of 16, the 5 x 5 window [t-2, t+3) in both directions, at most 36 staged key columns
-int lfsr_win_attn_mfma_launch(const float* q, int q_stride, int q_choff, const float* k, int k_stride, int k_choff, const float* v, int v_stride, int v_choff,
-                              float* o, int o_stride, int o_choff, int nheads, int ns0, int ns1, int ns2, long long bs0, long long bs1, long long bs2,
-                              int n1, int n2, long long st1, long long st2, int l1, int r1, int l2, int r2, int clip2, hipStream_t st) {
-  if (l1 != 2 || r1 != 3 || l2 != 2 || r2 != 3 || n2 > 32 || n2 < 1 || n1 < 1 || nheads < 1 || nheads > 65535) return LFSR_E_ARG;
-  if ((q_stride | q_choff | k_stride | k_choff | v_stride | v_choff | o_stride | o_choff) & 3) return LFSR_E_ARG;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) return LFSR_E_ARG;
+// LFSR_E_ARG = geometry not covered (the dispatcher goes on to the VALU kernels): heads of 16, the 5 x 5 window [t-2, t+3) in both directions, at most 36 staged key columns
+int lfsr_win_attn_mfma_launch(const LfsrAttn& a, hipStream_t st) {
+  const LfsrAttnGeom& g = a.g;
+  const int nheads = a.nheads, n1 = g.n1, n2 = g.n2;
+  if (a.hd != 16 || g.l1 != 2 || g.r1 != 3 || g.l2 != 2 || g.r2 != 3 || n2 > 32 || n2 < 1 || n1 < 1 || nheads < 1 || nheads > 65535) return LFSR_E_ARG;
+  if ((a.q_stride | a.q_choff | a.k_stride | a.k_choff | a.v_stride | a.v_choff | a.o_stride | a.o_choff) & 3) return LFSR_E_ARG;
+  if (((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.o) & 15) return LFSR_E_ARG;
   WinAttnArgs p{};
-  p.Q = q; p.q_stride = q_stride; p.q_choff = q_choff; p.K = k; p.k_stride = k_stride; p.k_choff = k_choff;
-  p.V = v; p.v_stride = v_stride; p.v_choff = v_choff; p.O = o; p.o_stride = o_stride; p.o_choff = o_choff;
-  p.ns1 = ns1; p.ns2 = ns2; p.bs0 = bs0; p.bs1 = bs1; p.bs2 = bs2; p.n1 = n1; p.n2 = n2; p.st1 = st1; p.st2 = st2;
-  const int clip = clip2 > 0 ? clip2 : n2;
-  p.kmax = n2 < clip ? n2 : clip;
+  p.Q = a.q; p.q_stride = a.q_stride; p.q_choff = a.q_choff; p.K = a.k; p.k_stride = a.k_stride; p.k_choff = a.k_choff;
+  p.V = a.v; p.v_stride = a.v_stride; p.v_choff = a.v_choff; p.O = a.o; p.o_stride = a.o_stride; p.o_choff = a.o_choff;
+  p.ns1 = g.ns1; p.ns2 = g.ns2; p.bs0 = g.bs0; p.bs1 = g.bs1; p.bs2 = g.bs2; p.n1 = n1; p.n2 = n2; p.st1 = g.st1; p.st2 = g.st2;
+  p.kmax = n2 < g.clip2 ? n2 : g.clip2;
   p.nstrip = (n1 + 7) / 8; p.ntc = (n2 + 3) / 4;
   p.scale = (1.0f / sqrtf(16.0f)) * 1.44269504088896340736f;
   {   // 32-bit byte offsets: the farthest pixel any sequence touches, times the widest row, must stay below 2^31 (the caller keeps the VALU kernel otherwise)
-    const long long far = (long long)(ns0 - 1) * bs0 + (long long)(ns1 - 1) * bs1 + (long long)(ns2 - 1) * bs2 + (long long)(n1 + 16) * st1 + (long long)(n2 + 8) * st2;
-    const long long wide = (long long)(q_stride > k_stride ? q_stride : k_stride) > (long long)(v_stride > o_stride ? v_stride : o_stride)
-                               ? (long long)(q_stride > k_stride ? q_stride : k_stride) : (long long)(v_stride > o_stride ? v_stride : o_stride);
-    if (bs0 < 0 || bs1 < 0 || bs2 < 0 || st1 <= 0 || st2 <= 0 || (far + 64) * wide * 4 >= (1LL << 31)) return LFSR_E_ARG;
+    const long long far = (long long)(g.ns0 - 1) * g.bs0 + (long long)(g.ns1 - 1) * g.bs1 + (long long)(g.ns2 - 1) * g.bs2 + (long long)(n1 + 16) * g.st1 + (long long)(n2 + 8) * g.st2;
+    const long long wide = std::max(std::max(a.q_stride, a.k_stride), std::max(a.v_stride, a.o_stride));
+    if (g.bs0 < 0 || g.bs1 < 0 || g.bs2 < 0 || g.st1 <= 0 || g.st2 <= 0 || (far + 64) * wide * 4 >= (1LL << 31)) return LFSR_E_ARG;
   }
-  const long long nblk = (long long)ns0 * ns1 * ns2 * p.nstrip;
+  const long long nblk = g.nseq() * p.nstrip;
   if (nblk <= 0 || nblk * nheads > 0x7fffffffLL) return LFSR_E_ARG;
   p.nheads = (unsigned)nheads;
   p.nunits = nblk * nheads;
   static std::atomic<bool> attr_set[64];
   static std::atomic<int> cus[64];
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_HIP_ERR(hipErrorInvalidDevice);
   if (!attr_set[dev]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_win_attn_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, WA_SMEM);
     if (e != hipSuccess) return LFSR_HIP_ERR(e);

@@ -84,6 +84,18 @@ def test_angular_attention_vs_mha(B, A, h, w):
     assert np.abs(o.cpu().numpy() - ref).max() < 1e-5
 
 
+@pytest.mark.parametrize("sel", [None, ("LFSR_ATTN_ANG", "lds"), ("LFSR_ATTN_ANG", "loop"), ("LFSR_ATTN_ANG", "l1"), ("LFSR_ATTN_L1", "1")])
+def test_angular_attention_kept_forms_vs_mha(sel, monkeypatch):
+    """The kept A/B forms of the angular attention at A = 5, the rows of the forward chain (attn.cpp) below k_ang_attn_pair: LFSR_ATTN_ANG=lds runs
+    k_window_attn_lds<8, 8> with its batched staging, =loop with its plain staging loop, =l1 and LFSR_ATTN_L1 the generic k_window_attn<8>.  The call, the fp64
+    reference and the gate of test_angular_attention_vs_mha at (1, 5, 3, 5): 15 sequences, so the last k_ang_attn_pair block of the default form is ragged"""
+    for name in ("LFSR_ATTN", "LFSR_ATTN_ANG", "LFSR_ATTN_L1"):
+        monkeypatch.delenv(name, raising=False)
+    if sel:
+        monkeypatch.setenv(*sel)
+    test_angular_attention_vs_mha(1, 5, 3, 5)
+
+
 @pytest.mark.parametrize("ln_fuse", ["default", "0", "1"])   # default: all norms inside the consuming kernels / every norm its own launch / only the feed-forward norms fused
 @pytest.mark.parametrize("tag", ["a5h8s4", "a3h6w8s2", "a3h6w8s3"])     # a3h6w8s3: scale 3, the two-kernel tail
 def test_lft_small_vs_golden_and_oracle(tag, ln_fuse, monkeypatch):
