@@ -528,8 +528,11 @@ class GraphedForward:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 static_y = self.rt.forward(static_x)
-            g = self.graphs[key] = (graph, static_x, static_y)
-        graph, static_x, static_y = g
+            # The captured launches hold the raw pointer of the workspace the warm-up left in rt.ws.  The runtime keeps one workspace and drops it when the
+            # geometry changes (ModelRuntime._workspace), so the entry owns that tensor: a forward at another shape, here or eager, must not hand the
+            # memory a live graph writes to back to the allocator.
+            g = self.graphs[key] = (graph, static_x, static_y, tuple(self.rt.ws.values()))
+        graph, static_x, static_y = g[:3]
         static_x.copy_(x)
         graph.replay()
         return static_y
