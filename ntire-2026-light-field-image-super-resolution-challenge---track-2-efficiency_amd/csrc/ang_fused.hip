@@ -159,13 +159,13 @@ size_t lfsr_ang_fused_smem(int A, int waves) {
 
 bool lfsr_ang_fused_ok(int A) { return A >= 1 && A <= 5 && lfsr_ang_fused_smem(A, 8) <= 160 * 1024; }
 
-// y = NULL: stage 1 only (t written, w2_packed unused)
-int lfsr_ang_fused_launch(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed, float* t, float* y,
-                          int y_stride, int y_choff, int B, int A, int h, int w, float slope, hipStream_t st) {
-  if (!lfsr_ang_fused_ok(A) || !t) return LFSR_E_ARG;
+// y = NULL: stage 1 only (t written, w2 unused)
+int lfsr_ang_fused_launch(const LfsrAng& a, hipStream_t st) {
+  const int B = a.B, A = a.A, h = a.h, w = a.w;
+  if (!lfsr_ang_fused_ok(A) || !a.t) return LFSR_E_ARG;
   static std::atomic<bool> attr_set[64];
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_HIP_ERR(hipErrorInvalidDevice);
   if (!attr_set[dev]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ang_fused<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_ang_fused<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -173,13 +173,13 @@ int lfsr_ang_fused_launch(const float* x, int x_stride, int x_choff, const float
     attr_set[dev] = true;
   }
   AngArgs p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.W1 = w1_packed; p.W2 = w2_packed; p.T = t;
-  p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff; p.B = B; p.A = A; p.H = h; p.W = w; p.slope = slope;
+  p.X = a.x; p.x_stride = a.x_stride; p.x_choff = a.x_choff; p.W1 = a.w0; p.W2 = a.w2; p.T = a.t;
+  p.Y = a.y; p.y_stride = a.y_stride; p.y_choff = a.y_choff; p.B = B; p.A = A; p.H = h; p.W = w; p.slope = a.slope;
   const long long ngroups = ((long long)B * h * w + 15) / 16;
   const int waves = 8;
   long long grid = (ngroups + waves - 1) / waves;
   if (grid > 256) grid = 256;
-  if (y) hipLaunchKernelGGL(k_ang_fused<true>, dim3((unsigned)grid), dim3(waves * 64), lfsr_ang_fused_smem(A, waves), st, p);
+  if (a.y) hipLaunchKernelGGL(k_ang_fused<true>, dim3((unsigned)grid), dim3(waves * 64), lfsr_ang_fused_smem(A, waves), st, p);
   else hipLaunchKernelGGL(k_ang_fused<false>, dim3((unsigned)grid), dim3(waves * 64), lfsr_ang_fused_smem(A, waves), st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;

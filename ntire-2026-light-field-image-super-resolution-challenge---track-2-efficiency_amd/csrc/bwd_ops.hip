@@ -381,7 +381,7 @@ int lfsr_bwd_gemm(const LfsrGemm& g, hipStream_t st) {
   p.M = g.M; p.N = g.N; p.Npad = npad32(g.N); p.A = g.A; p.AA = g.A * g.A; p.H = g.h; p.W = g.w; p.ntaps = g.ntaps; p.CH = g.CH; p.slope = 1.0f;
   if ((g.x_stride | g.x_choff) & 3) return LFSR_E_ARG;
   // fuse.0 dgrad (64 -> 144, masked by the saved concat buffer): the row-streaming kernel (LFSR_NO_ROWGEMM keeps the gather-GEMM: A/B runs)
-  if (g.in_mode == LFSR_IN_SAME && g.out_mode == LFSR_OUT_SAME && g.cin == 64 && g.N == 144 && g.ntaps == 1 && !g.R1 && g.M >= 2048 && !lfsr_sel("LFSR_NO_ROWGEMM") && !lfsr_gemm_sel().dgrad_gather) {     // (LFSR_DGRAD_PW=gather: the gather-GEMM for this data gradient only -- the forward keeps its kernel)
+  if (g.in_mode == LFSR_IN_SAME && g.out_mode == LFSR_OUT_SAME && g.cin == 64 && g.N == 144 && g.ntaps == 1 && !g.R1 && g.M >= LFSR_ROWGEMM_MIN_ROWS && lfsr_rowgemm_enabled() && !lfsr_gemm_sel().dgrad_gather) {     // (LFSR_DGRAD_PW=gather: the gather-GEMM for this data gradient only -- the forward keeps its kernel)
     LfsrLin c{};
     c.x = g.X; c.x_stride = g.x_stride; c.x_choff = g.x_choff; c.K = 64; c.w_packed = g.Wp; c.mk = g.Mk; c.mk_stride = g.mk_stride; c.mk_choff = g.mk_choff; c.mk_slope = g.mk_slope;
     c.y = g.Y; c.y_stride = g.y_stride; c.y_choff = g.y_choff; c.M = g.M; c.N = 144; c.slope = 1.0f;

@@ -492,7 +492,7 @@ int device_cus(int& cus_out) {
   static std::atomic<bool> attr_set[64];
   static std::atomic<int> cus[64];
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_HIP_ERR(hipErrorInvalidDevice);
   if (!attr_set[dev]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_bf16), hipFuncAttributeMaxDynamicSharedMemorySize, EK_SMEM);
     if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_distg_tail_bf16), hipFuncAttributeMaxDynamicSharedMemorySize, BT_SMEM);
@@ -507,21 +507,22 @@ int device_cus(int& cus_out) {
 
 }  // namespace
 
-// Stage 1 of both EPI passes on bf16 operands: t_h, t_v written as lfsr_epi_b3_launch(..., y = NULL, ..., which = 3) writes them.  w1_direct: the fp32 direct
-// pack of EPIConv.0.  LFSR_E_ARG = not covered, nothing launched (the caller keeps lfsr_epi_b3_launch).
-int lfsr_epi_bf16_launch(const float* x, int x_stride, int x_choff, const float* w1_direct, float* t_h, float* t_v, int B, int A, int h, int w, float slope,
-                         hipStream_t st) {
-  if (A != 5 || h > 32 || w > 32 || h <= 0 || w <= 0 || B <= 0 || !x || !w1_direct || !t_h || !t_v) return LFSR_E_ARG;
-  if ((x_stride | x_choff) & 3 || x_stride < x_choff + 64) return LFSR_E_ARG;
-  if (((uintptr_t)x | (uintptr_t)w1_direct | (uintptr_t)t_h | (uintptr_t)t_v) & 15) return LFSR_E_ARG;
-  if ((long long)B * A * A * h * w * x_stride * 4 >= (1LL << 31) || (long long)B * A * h * w * 32 * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
-  if (!(slope >= 0.f && slope <= 1.f)) return LFSR_E_ARG;      // LeakyReLU as max(v, slope v)
+// Stage 1 of both EPI passes on bf16 operands (e.y null, which = 3): t_h, t_v written as lfsr_epi_b3_launch writes them for the same call.  Reads the fp32 direct
+// pack of EPIConv.0.  LFSR_E_ARG = not covered, nothing launched (the dispatcher keeps lfsr_epi_b3_launch).
+int lfsr_epi_bf16_launch(const LfsrEpi& e, hipStream_t st) {
+  const int B = e.B, A = e.A, h = e.h, w = e.w;
+  if (e.y || e.which != 3) return LFSR_E_ARG;
+  if (A != 5 || h > 32 || w > 32 || h <= 0 || w <= 0 || B <= 0 || !e.x || !e.w0 || !e.t_h || !e.t_v) return LFSR_E_ARG;
+  if ((e.x_stride | e.x_choff) & 3 || e.x_stride < e.x_choff + 64) return LFSR_E_ARG;
+  if (((uintptr_t)e.x | (uintptr_t)e.w0 | (uintptr_t)e.t_h | (uintptr_t)e.t_v) & 15) return LFSR_E_ARG;
+  if ((long long)B * A * A * h * w * e.x_stride * 4 >= (1LL << 31) || (long long)B * A * h * w * 32 * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
+  if (!(e.slope >= 0.f && e.slope <= 1.f)) return LFSR_E_ARG;      // LeakyReLU as max(v, slope v)
   int cus = 0;
   LFSR_RC(device_cus(cus));
   EpiBf16Args p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.x_bytes = (int)((long long)B * A * A * h * w * x_stride * 4);
-  p.W1 = w1_direct; p.TH = t_h; p.TV = t_v; p.te_bytes = (int)((long long)B * A * h * w * 32 * 4);
-  p.B = B; p.H = h; p.W = w; p.slope = slope;
+  p.X = e.x; p.x_stride = e.x_stride; p.x_choff = e.x_choff; p.x_bytes = (int)((long long)B * A * A * h * w * e.x_stride * 4);
+  p.W1 = e.w0_direct(); p.TH = e.t_h; p.TV = e.t_v; p.te_bytes = (int)((long long)B * A * h * w * 32 * 4);
+  p.B = B; p.H = h; p.W = w; p.slope = e.slope;
   p.tilesH = (B * A * h + EK_LINES - 1) / EK_LINES;
   p.tilesV = (B * A * w + EK_LINES - 1) / EK_LINES;
   const int ngroups = p.tilesH + p.tilesV;
@@ -532,52 +533,30 @@ int lfsr_epi_bf16_launch(const float* x, int x_stride, int x_choff, const float*
   return LFSR_OK;
 }
 
-// The block tail on bf16 operands; the arguments of lfsr_distg_tail_launch except we2_direct: the fp32 direct pack of EPIConv.2 ([160][32]), not its planes.
-// LFSR_E_ARG = not covered, nothing launched (the caller keeps lfsr_distg_tail_launch).
-int lfsr_distg_tail_bf16_launch(const float* spa, int spa_stride, int spa_choff, const float* t_a, const float* t_h, const float* t_v, const float* wa2_packed,
-                                const float* we2_direct, const float* wf_packed, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope,
-                                hipStream_t st) {
-  if (A != 5 || B <= 0 || h <= 0 || w <= 0 || !spa || !t_a || !t_h || !t_v || !wa2_packed || !we2_direct || !wf_packed || !y) return LFSR_E_ARG;
-  if ((spa_stride | spa_choff | y_stride | y_choff) & 3 || spa_stride < spa_choff + 64 || y_stride < y_choff + 64) return LFSR_E_ARG;
-  if (((uintptr_t)spa | (uintptr_t)t_a | (uintptr_t)t_h | (uintptr_t)t_v | (uintptr_t)wa2_packed | (uintptr_t)we2_direct | (uintptr_t)wf_packed | (uintptr_t)y) & 15)
+// The block tail on bf16 operands: lfsr_distg_tail_launch's call, reading the fp32 direct pack of EPIConv.2 ([160][32]), not its planes.
+// LFSR_E_ARG = not covered, nothing launched (the dispatcher keeps lfsr_distg_tail_launch).
+int lfsr_distg_tail_bf16_launch(const LfsrDistgTail& t, hipStream_t st) {
+  const int B = t.B, A = t.A, h = t.h, w = t.w;
+  if (A != 5 || B <= 0 || h <= 0 || w <= 0 || !t.spa || !t.t_a || !t.t_h || !t.t_v || !t.w_ang2 || !t.w_epi2 || !t.w_fuse0 || !t.y) return LFSR_E_ARG;
+  if ((t.spa_stride | t.spa_choff | t.y_stride | t.y_choff) & 3 || t.spa_stride < t.spa_choff + 64 || t.y_stride < t.y_choff + 64) return LFSR_E_ARG;
+  if (((uintptr_t)t.spa | (uintptr_t)t.t_a | (uintptr_t)t.t_h | (uintptr_t)t.t_v | (uintptr_t)t.w_ang2 | (uintptr_t)t.w_epi2 | (uintptr_t)t.w_fuse0 | (uintptr_t)t.y) & 15)
     return LFSR_E_ARG;
-  if (!(slope >= 0.f && slope <= 1.f)) return LFSR_E_ARG;      // LeakyReLU as max(v, slope v) in the epipolar stage
+  if (!(t.slope >= 0.f && t.slope <= 1.f)) return LFSR_E_ARG;      // LeakyReLU as max(v, slope v) in the epipolar stage
   const long long npix = (long long)B * A * A * h * w;
-  if (npix * spa_stride * 4 >= (1LL << 31) || npix * y_stride * 4 >= (1LL << 31) || (long long)B * A * h * w * 32 * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
+  if (npix * t.spa_stride * 4 >= (1LL << 31) || npix * t.y_stride * 4 >= (1LL << 31) || (long long)B * A * h * w * 32 * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
   int cus = 0;
   LFSR_RC(device_cus(cus));
   TailBf16Args p{};
-  p.S = spa; p.s_stride = spa_stride; p.s_choff = spa_choff; p.s_bytes = (int)(npix * spa_stride * 4);
-  p.TA = t_a; p.ta_bytes = (int)((long long)B * h * w * 16 * 4);
-  p.TH = t_h; p.TV = t_v; p.te_bytes = (int)((long long)B * A * h * w * 32 * 4);
-  p.WA2 = wa2_packed; p.WE2 = we2_direct; p.WF = wf_packed;
-  p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff; p.y_bytes = (int)(npix * y_stride * 4);
-  p.B = B; p.H = h; p.W = w; p.slope = slope;
+  p.S = t.spa; p.s_stride = t.spa_stride; p.s_choff = t.spa_choff; p.s_bytes = (int)(npix * t.spa_stride * 4);
+  p.TA = t.t_a; p.ta_bytes = (int)((long long)B * h * w * 16 * 4);
+  p.TH = t.t_h; p.TV = t.t_v; p.te_bytes = (int)((long long)B * A * h * w * 32 * 4);
+  p.WA2 = t.w_ang2; p.WE2 = t.w_epi2_direct(); p.WF = t.w_fuse0;
+  p.Y = t.y; p.y_stride = t.y_stride; p.y_choff = t.y_choff; p.y_bytes = (int)(npix * t.y_stride * 4);
+  p.B = B; p.H = h; p.W = w; p.slope = t.slope;
   const long long ntiles = ((long long)B * h * w + 15) / 16;
   long long grid = (ntiles + BT_WAVES - 1) / BT_WAVES;
   if (grid > (long long)BT_BLOCKS_PER_CU * cus) grid = (long long)BT_BLOCKS_PER_CU * cus;
   hipLaunchKernelGGL(k_distg_tail_bf16, dim3((unsigned)grid), dim3(BT_WAVES * 64), BT_SMEM, st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
-}
-
-// ---- dispatch: the two launches of a fused block tail under the branch arithmetic.  The two are independent: either kernel is valid on the other form's
-//      t_H / t_V, which are fp32 in memory ----
-int lfsr_distg_epi1_launch(const float* x, int x_stride, int x_choff, const float* w_epi0, float* t_h, float* t_v, int B, int A, int h, int w, float slope,
-                           hipStream_t st) {
-  if (lfsr_branch_arith_bf16() && !lfsr_arith_f32()) {
-    const int rc = lfsr_epi_bf16_launch(x, x_stride, x_choff, w_epi0, t_h, t_v, B, A, h, w, slope, st);
-    if (rc != LFSR_E_ARG) return rc;
-  }
-  return lfsr_epi_b3_launch(x, x_stride, x_choff, w_epi0 + 25 * 32 * 64 + LFSR_EPI_WINO_FLOATS, nullptr, nullptr, 0, 0, 0, t_h, t_v, B, A, h, w, 3, slope, st);
-}
-
-int lfsr_distg_tail2_launch(const float* spa, int spa_stride, int spa_choff, const float* t_a, const float* t_h, const float* t_v, const float* wa2_packed,
-                            const float* w_epi2, const float* wf_packed, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope,
-                            hipStream_t st) {
-  if (lfsr_branch_arith_bf16() && !lfsr_arith_f32()) {
-    const int rc = lfsr_distg_tail_bf16_launch(spa, spa_stride, spa_choff, t_a, t_h, t_v, wa2_packed, w_epi2, wf_packed, y, y_stride, y_choff, B, A, h, w, slope, st);
-    if (rc != LFSR_E_ARG) return rc;
-  }
-  return lfsr_distg_tail_launch(spa, spa_stride, spa_choff, t_a, t_h, t_v, wa2_packed, w_epi2 + 160 * 32, wf_packed, y, y_stride, y_choff, B, A, h, w, slope, st);
 }

@@ -289,20 +289,20 @@ __global__ __launch_bounds__(512) void k_distg_tail(DistgTailArgs p) {
 }  // namespace
 
 // t_a / t_h / t_v: the stage-1 results (k_ang_fused / k_epi_b3 stage-1-only modes); spa: the SpaConv.2 output; y: fuse.0's output.  LFSR_E_ARG = not covered.
-int lfsr_distg_tail_launch(const float* spa, int spa_stride, int spa_choff, const float* t_a, const float* t_h, const float* t_v, const float* wa2_packed,
-                           const float* we2_planes, const float* wf_packed, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope,
-                           hipStream_t st) {
-  if (A != 5 || B <= 0 || h <= 0 || w <= 0 || !spa || !t_a || !t_h || !t_v || !wa2_packed || !we2_planes || !wf_packed || !y) return LFSR_E_ARG;
-  if ((spa_stride | spa_choff | y_stride | y_choff) & 3 || spa_stride < spa_choff + 64 || y_stride < y_choff + 64) return LFSR_E_ARG;
-  if (((uintptr_t)spa | (uintptr_t)t_a | (uintptr_t)t_h | (uintptr_t)t_v | (uintptr_t)wa2_packed | (uintptr_t)we2_planes | (uintptr_t)wf_packed | (uintptr_t)y) & 15)
+int lfsr_distg_tail_launch(const LfsrDistgTail& t, hipStream_t st) {
+  const int B = t.B, A = t.A, h = t.h, w = t.w;
+  const float* we2_planes = t.w_epi2_planes();
+  if (A != 5 || B <= 0 || h <= 0 || w <= 0 || !t.spa || !t.t_a || !t.t_h || !t.t_v || !t.w_ang2 || !we2_planes || !t.w_fuse0 || !t.y) return LFSR_E_ARG;
+  if ((t.spa_stride | t.spa_choff | t.y_stride | t.y_choff) & 3 || t.spa_stride < t.spa_choff + 64 || t.y_stride < t.y_choff + 64) return LFSR_E_ARG;
+  if (((uintptr_t)t.spa | (uintptr_t)t.t_a | (uintptr_t)t.t_h | (uintptr_t)t.t_v | (uintptr_t)t.w_ang2 | (uintptr_t)we2_planes | (uintptr_t)t.w_fuse0 | (uintptr_t)t.y) & 15)
     return LFSR_E_ARG;
-  if (!(slope >= 0.f && slope <= 1.f)) return LFSR_E_ARG;      // LeakyReLU as max(v, slope v) in the epipolar stage (as k_epi_b3)
+  if (!(t.slope >= 0.f && t.slope <= 1.f)) return LFSR_E_ARG;      // LeakyReLU as max(v, slope v) in the epipolar stage (as k_epi_b3)
   const long long npix = (long long)B * A * A * h * w;
-  if (npix * spa_stride * 4 >= (1LL << 31) || npix * y_stride * 4 >= (1LL << 31) || (long long)B * A * h * w * 32 * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
+  if (npix * t.spa_stride * 4 >= (1LL << 31) || npix * t.y_stride * 4 >= (1LL << 31) || (long long)B * A * h * w * 32 * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
   static std::atomic<bool> attr_set[64];
   static std::atomic<int> cus[64];
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_HIP_ERR(hipErrorInvalidDevice);
   if (!attr_set[dev]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_distg_tail), hipFuncAttributeMaxDynamicSharedMemorySize, DT_SMEM);
     if (e != hipSuccess) return LFSR_HIP_ERR(e);
@@ -311,46 +311,16 @@ int lfsr_distg_tail_launch(const float* spa, int spa_stride, int spa_choff, cons
     attr_set[dev] = true;
   }
   DistgTailArgs p{};
-  p.S = spa; p.s_stride = spa_stride; p.s_choff = spa_choff; p.s_bytes = (int)(npix * spa_stride * 4);
-  p.TA = t_a; p.ta_bytes = (int)((long long)B * h * w * 16 * 4);
-  p.TH = t_h; p.TV = t_v; p.te_bytes = (int)((long long)B * A * h * w * 32 * 4);
-  p.WA2 = wa2_packed; p.WE2p = reinterpret_cast<const uint4*>(we2_planes); p.WF = wf_packed;
-  p.Y = y; p.y_stride = y_stride; p.y_choff = y_choff; p.y_bytes = (int)(npix * y_stride * 4);
-  p.B = B; p.H = h; p.W = w; p.slope = slope;
+  p.S = t.spa; p.s_stride = t.spa_stride; p.s_choff = t.spa_choff; p.s_bytes = (int)(npix * t.spa_stride * 4);
+  p.TA = t.t_a; p.ta_bytes = (int)((long long)B * h * w * 16 * 4);
+  p.TH = t.t_h; p.TV = t.t_v; p.te_bytes = (int)((long long)B * A * h * w * 32 * 4);
+  p.WA2 = t.w_ang2; p.WE2p = reinterpret_cast<const uint4*>(we2_planes); p.WF = t.w_fuse0;
+  p.Y = t.y; p.y_stride = t.y_stride; p.y_choff = t.y_choff; p.y_bytes = (int)(npix * t.y_stride * 4);
+  p.B = B; p.H = h; p.W = w; p.slope = t.slope;
   const long long ntiles = ((long long)B * h * w + 15) / 16;
   long long grid = (ntiles + DT_WAVES - 1) / DT_WAVES;
   if (grid > cus[dev]) grid = cus[dev];
   hipLaunchKernelGGL(k_distg_tail, dim3((unsigned)grid), dim3(DT_WAVES * 64), DT_SMEM, st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
-}
-
-// The fused tail covers a call when the default arithmetic runs the three kernels it replaces in their three-term bf16 / fp32-MFMA forms at angRes 5
-// (none of the LFSR_EPI / LFSR_ROWGEMM / LFSR_ANG lab overrides set) and the stage-1 kernels take the geometry.
-bool lfsr_distg_tail_ok(int A, int h, int w, const float* x, int x_stride, int x_choff, const float* t_h, const float* t_v) {
-  if (A != 5 || h <= 0 || w <= 0 || h > 32 || w > 32 || !lfsr_ang_fused_ok(A) || !lfsr_epi_use_b3()) return false;
-  const char* rsel = lfsr_sel("LFSR_ROWGEMM");
-  const char* asel = lfsr_sel("LFSR_ANG");
-  if ((rsel && (rsel[0] == 'f' || rsel[0] == '1')) || lfsr_sel("LFSR_NO_ROWGEMM") || (asel && asel[0] == 'g')) return false;
-  if ((x_stride | x_choff) & 3 || x_stride < x_choff + 64 || (((uintptr_t)x | (uintptr_t)t_h | (uintptr_t)t_v) & 15)) return false;
-  return true;
-}
-
-extern "C" int lfsr_distg_branch_tail_fwd(const float* x, int x_stride, int x_choff, const float* spa, int spa_stride, int spa_choff,
-                                          const float* w_ang0, const float* w_ang2, const float* w_epi0, const float* w_epi2, const float* w_fuse0,
-                                          float* t_a, float* t_h, float* t_v, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope,
-                                          void* stream) {
-  LfsrOpTimer op_t("distg_tail", B, h * w, lfsr_stream(stream));
-  if (!x || !spa || !w_ang0 || !w_ang2 || !w_epi0 || !w_epi2 || !w_fuse0 || !t_a || !t_h || !t_v || !y || B <= 0) return LFSR_E_ARG;
-  if (!lfsr_distg_tail_ok(A, h, w, x, x_stride, x_choff, t_h, t_v)) return LFSR_E_ARG;
-  if ((spa_stride | spa_choff | y_stride | y_choff) & 3 || spa_stride < spa_choff + 64 || y_stride < y_choff + 64) return LFSR_E_ARG;
-  if (((uintptr_t)spa | (uintptr_t)t_a | (uintptr_t)w_ang2 | (uintptr_t)w_epi0 | (uintptr_t)w_epi2 | (uintptr_t)w_fuse0 | (uintptr_t)y) & 15) return LFSR_E_ARG;
-  if (!(slope >= 0.f && slope <= 1.f)) return LFSR_E_ARG;
-  const long long npix = (long long)B * A * A * h * w;
-  if (npix * x_stride * 4 >= (1LL << 31) || npix * spa_stride * 4 >= (1LL << 31) || npix * y_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
-  hipStream_t st = lfsr_stream(stream);
-  int rc = lfsr_ang_fused_launch(x, x_stride, x_choff, w_ang0, nullptr, t_a, nullptr, 0, 0, B, A, h, w, slope, st);
-  if (!rc) rc = lfsr_distg_epi1_launch(x, x_stride, x_choff, w_epi0, t_h, t_v, B, A, h, w, slope, st);      // (both follow lfsr_set_branch_arithmetic)
-  if (!rc) rc = lfsr_distg_tail2_launch(spa, spa_stride, spa_choff, t_a, t_h, t_v, w_ang2, w_epi2, w_fuse0, y, y_stride, y_choff, B, A, h, w, slope, st);
-  return rc;
 }

@@ -151,10 +151,10 @@ int lfsr_distgssr_load_param(lfsr_distgssr* c, const char* key, const float* dat
     else {
       c->d_gen.push_back(LfsrPackDesc{data, dst, nullptr, 0, sl->O, sl->C, sl->T, pad32(sl->O), sl->perm, sl->ch, 0});
       if (sl->O == 32 && sl->C == 64 && sl->T == 25 && sl->perm == 0) {
-        c->d_epi.push_back(LfsrPackDesc{dst, dst + 25 * 32 * 64, nullptr, 0, 32, 64, 25, 32, 0, 0, 0});
-        c->d_epib.push_back(LfsrPackDesc{dst, dst + 25 * 32 * 64 + LFSR_EPI_WINO_FLOATS, nullptr, 0, 32, 64, 25, 32, 0, 0, 0});     // the three bf16 planes (epi_b3.hip)
+        c->d_epi.push_back(LfsrPackDesc{dst, dst + LFSR_EPI0_WINO_OFF, nullptr, 0, 32, 64, 25, 32, 0, 0, 0});
+        c->d_epib.push_back(LfsrPackDesc{dst, dst + LFSR_EPI0_PLANES_OFF, nullptr, 0, 32, 64, 25, 32, 0, 0, 0});     // the three bf16 planes (epi_b3.hip)
       }
-      if (sl->O == 160 && sl->C == 32 && sl->T == 1 && sl->perm == 0) c->d_epib.push_back(LfsrPackDesc{dst, dst + 160 * 32, nullptr, 1, 160, 32, 1, 160, 0, 0, 0});
+      if (sl->O == 160 && sl->C == 32 && sl->T == 1 && sl->perm == 0) c->d_epib.push_back(LfsrPackDesc{dst, dst + LFSR_EPI2_PLANES_OFF, nullptr, 1, 160, 32, 1, 160, 0, 0, 0});
     }
     if (kindT == 1 && c3) c->d_c3.push_back(LfsrPackDesc{data, tdst, tdst + LFSR_CONV3_WINO4_OFF, 0, 64, 64, 9, 64, 0, 0, 1});
     else if (kindT == 1) c->d_gen.push_back(LfsrPackDesc{data, tdst, nullptr, 1, sl->O, sl->C, sl->T, pad32(sl->C), 0, 0, 1});
@@ -245,10 +245,15 @@ int lfsr_distgssr_forward_taps(lfsr_distgssr* c, const float* x, float* out, int
   const float L = 0.1f;  // LeakyReLU(0.1), DistgSSR.py:80-101
   // The block tail (AngConv.2, EPIConv.2 of both passes, the concat and fuse.0) as ONE kernel (distg_tail.hip) at angRes 5 under the default arithmetic: the
   // 144-channel concat never goes through HBM.  Same bits as the three-kernel sequence below, which stays for lfsr_set_arithmetic(F32), A != 5, the LFSR_EPI /
-  // LFSR_ROWGEMM / LFSR_ANG lab overrides, inputs whose fuse.0 would not run the bf16 row-GEMM (fewer than 2048 pixels), block (0,0) when the concat tap
-  // is asked for, and LFSR_DISTG_TAIL=0 (same-process A/B)
-  const char* tsel = lfsr_sel("LFSR_DISTG_TAIL");
-  const bool tail_ok = !(tsel && tsel[0] == '0') && (long long)nimg * h * w >= 2048 && lfsr_distg_tail_ok(A, h, w, nullptr, 64, 0, E32, EV32);
+  // LFSR_ROWGEMM / LFSR_ANG lab overrides, inputs whose fuse.0 would not run the bf16 row-GEMM (fewer than LFSR_ROWGEMM_MIN_ROWS pixels), block (0,0) when the
+  // concat tap is asked for, and LFSR_DISTG_TAIL=0 (same-process A/B).  Which kernels run either way: distg_branch.cpp
+  hipStream_t st = lfsr_stream(stream);
+  LfsrAng ang{nullptr, 64, 0, nullptr, nullptr, A16, CAT, 144, 64, B, A, h, w, L};                    // x and the weights: per block
+  LfsrEpi epi{nullptr, 64, 0, nullptr, nullptr, CAT, 144, 80, 112, nullptr, nullptr, B, A, h, w, 3, L};
+  LfsrAng ang1 = ang; ang1.y = nullptr; ang1.y_stride = ang1.y_choff = 0;                              // the fused tail's stage-1 halves
+  LfsrEpi epi1 = epi; epi1.y = nullptr; epi1.y_stride = epi1.choff_h = epi1.choff_v = 0; epi1.t_h = E32; epi1.t_v = EV32;
+  LfsrDistgTail tail{nullptr, 64, 0, A16, E32, EV32, nullptr, nullptr, nullptr, T, 64, 0, B, A, h, w, L};
+  const bool tail_ok = !lfsr_branch_sel().tail_off && (long long)nimg * h * w >= LFSR_ROWGEMM_MIN_ROWS && lfsr_distg_tail_covers(epi1);
   int rc;
 #define PROF(cls, call)                                                              \
   do {                                                                               \
@@ -289,20 +294,21 @@ int lfsr_distgssr_forward_taps(lfsr_distgssr* c, const float* x, float* out, int
       if (tail_ok && !(taps && taps[4] && g == 0 && b == 0)) {
         // SpaConv.2 into o (free until fuse.2 writes the block output there), the stage-1 halves of the branches, then the fused tail into T
         PROF(0, conv(T, p + "SpaConv.2.weight", o, 64, 0, nullptr, L));
-        hipStream_t st = lfsr_stream(stream);
-        PROF(1, lfsr_ang_fused_launch(cur, 64, 0, c->w(p + "AngConv.0.weight"), nullptr, A16, nullptr, 0, 0, B, A, h, w, L, st));
-        // (both follow lfsr_set_branch_arithmetic: distg_bf16.hip)
-        PROF(2, lfsr_distg_epi1_launch(cur, 64, 0, c->w(p + "EPIConv.0.weight"), E32, EV32, B, A, h, w, L, st));
-        PROF(3, lfsr_distg_tail2_launch(o, 64, 0, A16, E32, EV32, c->w(p + "AngConv.2.weight"), c->w(p + "EPIConv.2.weight"), c->w(p + "fuse.0.weight"), T, 64, 0,
-                                        B, A, h, w, L, st));
+        ang1.x = epi1.x = cur; ang1.w0 = c->w(p + "AngConv.0.weight"); epi1.w0 = c->w(p + "EPIConv.0.weight");
+        tail.spa = o; tail.w_ang2 = c->w(p + "AngConv.2.weight"); tail.w_epi2 = c->w(p + "EPIConv.2.weight"); tail.w_fuse0 = c->w(p + "fuse.0.weight");
+        PROF(1, lfsr_distg_ang1_run(ang1, st));
+        PROF(2, lfsr_distg_epi1_run(epi1, st));      // (this and the next follow lfsr_set_branch_arithmetic)
+        PROF(3, lfsr_distg_tail2_run(tail, st));
         PROF(0, conv(T, p + "fuse.2.weight", o, 64, 0, cur, 1.0f));
         cur = o;
         if (g == 0 && b == 0) LFSR_RC(tap(1, cur, 64, 64));
         continue;
       }
       PROF(0, conv(T, p + "SpaConv.2.weight", CAT, 144, 0, nullptr, L));
-      PROF(1, lfsr_angconv_fwd(cur, 64, 0, c->w(p + "AngConv.0.weight"), c->w(p + "AngConv.2.weight"), A16, CAT, 144, 64, B, A, h, w, L, stream));
-      PROF(2, lfsr_epiconv_hv_fwd(cur, 64, 0, c->w(p + "EPIConv.0.weight"), c->w(p + "EPIConv.2.weight"), E32, CAT, 144, 80, 112, B, A, h, w, L, stream));
+      ang.x = epi.x = cur; ang.w0 = c->w(p + "AngConv.0.weight"); ang.w2 = c->w(p + "AngConv.2.weight");
+      epi.w0 = c->w(p + "EPIConv.0.weight"); epi.w2 = c->w(p + "EPIConv.2.weight");
+      PROF(1, lfsr_ang_run(ang, st));
+      PROF(2, lfsr_epi_run(epi, E32, st));
       if (g == 0 && b == 0) LFSR_RC(tap(4, CAT, 144, 144));
       PROF(3, lfsr_pointwise_fwd(CAT, 144, 0, 144, c->w(p + "fuse.0.weight"), nullptr, T, 64, 0, nimg * h * w, 64, L, stream));
       PROF(0, conv(T, p + "fuse.2.weight", o, 64, 0, cur, 1.0f));
@@ -446,13 +452,11 @@ int lfsr_distgssr_forward_train(lfsr_distgssr* c, const float* x, float* out, in
       std::string p = "disentg.Group." + std::to_string(g) + ".Block." + std::to_string(b) + ".";
       LFSR_RC(conv(cur, p + "SpaConv.0.weight", t.S1[i], 64, nullptr, L));
       LFSR_RC(conv(t.S1[i], p + "SpaConv.2.weight", t.CAT[i], 144, nullptr, L));
-      LFSR_RC(lfsr_angconv_fwd(cur, 64, 0, c->w(p + "AngConv.0.weight"), c->w(p + "AngConv.2.weight"), t.A16[i], t.CAT[i], 144, 64, B, A, h, w, L, stream));
-      if (lfsr_epi_fused_ok(A, h, w)) {
-        LFSR_RC(lfsr_epi_fused_launch(cur, 64, 0, c->w(p + "EPIConv.0.weight"), c->w(p + "EPIConv.2.weight"), t.CAT[i], 144, 80, 112, t.EH[i], t.EV[i], B, A, h, w, 3, L, st));
-      } else {
-        LFSR_RC(lfsr_epiconv_gather(cur, 64, 0, c->w(p + "EPIConv.0.weight"), c->w(p + "EPIConv.2.weight"), t.EH[i], t.CAT[i], 144, 80, B, A, h, w, 0, L, st));
-        LFSR_RC(lfsr_epiconv_gather(cur, 64, 0, c->w(p + "EPIConv.0.weight"), c->w(p + "EPIConv.2.weight"), t.EV[i], t.CAT[i], 144, 112, B, A, h, w, 1, L, st));
-      }
+      // the branches into the saved concat, their stage-1 results kept for the backward (which kernels: distg_branch.cpp)
+      const LfsrAng ang{cur, 64, 0, c->w(p + "AngConv.0.weight"), c->w(p + "AngConv.2.weight"), t.A16[i], t.CAT[i], 144, 64, B, A, h, w, L};
+      const LfsrEpi epi{cur, 64, 0, c->w(p + "EPIConv.0.weight"), c->w(p + "EPIConv.2.weight"), t.CAT[i], 144, 80, 112, t.EH[i], t.EV[i], B, A, h, w, 3, L};
+      LFSR_RC(lfsr_ang_run(ang, st));
+      LFSR_RC(lfsr_epi_run(epi, nullptr, st));
       LFSR_RC(lfsr_pointwise_fwd(t.CAT[i], 144, 0, 144, c->w(p + "fuse.0.weight"), nullptr, t.FZ[i], 64, 0, nimg * h * w, 64, L, stream));
       LFSR_RC(conv(t.FZ[i], p + "fuse.2.weight", t.OUT[i], 64, cur, 1.0f));
       cur = t.OUT[i];

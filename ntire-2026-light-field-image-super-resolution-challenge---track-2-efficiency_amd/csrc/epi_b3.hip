@@ -434,41 +434,42 @@ int lfsr_pack_epi_b3_batch(const LfsrPackDesc* table_dev, int n, hipStream_t st)
   return LFSR_OK;
 }
 
-// LFSR_E_ARG = not covered (the caller keeps epi_fused.hip's fp32-MFMA kernels)
-int lfsr_epi_b3_launch(const float* x, int x_stride, int x_choff, const float* w1_planes, const float* w2_planes, float* y, int y_stride,
-                       int choffH, int choffV, float* t_h, float* t_v, int B, int A, int h, int w, int which, float slope, hipStream_t st) {
+// LFSR_E_ARG = not covered (the dispatcher keeps epi_fused.hip's fp32-MFMA kernels)
+int lfsr_epi_b3_launch(const LfsrEpi& e, hipStream_t st) {
+  const int B = e.B, A = e.A, h = e.h, w = e.w;
   if (A != 5 || h > 32 || w > 32 || h <= 0 || w <= 0 || B <= 0) return LFSR_E_ARG;
-  if (!y && (which != 3 || !t_h || !t_v)) return LFSR_E_ARG;      // y = NULL: stage 1 of both passes only (t_h, t_v written; w2_planes unused)
-  if ((x_stride | x_choff | y_stride | choffH | choffV) & 3) return LFSR_E_ARG;
-  if (((uintptr_t)x | (uintptr_t)y | (uintptr_t)w1_planes | (uintptr_t)w2_planes | (uintptr_t)t_h | (uintptr_t)t_v) & 15) return LFSR_E_ARG;
-  if ((long long)B * A * A * h * w * x_stride * 4 >= (1LL << 31) || (y && (long long)B * A * A * h * w * y_stride * 4 >= (1LL << 31))) return LFSR_E_ARG;   // 32-bit byte offsets
-  if (!(slope >= 0.f && slope <= 1.f)) return LFSR_E_ARG;      // LeakyReLU as max(v, slope v)
+  if (!e.y && (e.which != 3 || !e.t_h || !e.t_v)) return LFSR_E_ARG;      // y = NULL: stage 1 of both passes only (t_h, t_v written; w2 unused)
+  if ((e.x_stride | e.x_choff | e.y_stride | e.choff_h | e.choff_v) & 3) return LFSR_E_ARG;
+  if (((uintptr_t)e.x | (uintptr_t)e.y | (uintptr_t)e.w0_planes() | (uintptr_t)e.w2_planes() | (uintptr_t)e.t_h | (uintptr_t)e.t_v) & 15) return LFSR_E_ARG;
+  const long long npix = (long long)B * A * A * h * w;
+  if (npix * e.x_stride * 4 >= (1LL << 31) || (e.y && npix * e.y_stride * 4 >= (1LL << 31))) return LFSR_E_ARG;   // 32-bit byte offsets
+  if (!(e.slope >= 0.f && e.slope <= 1.f)) return LFSR_E_ARG;      // LeakyReLU as max(v, slope v)
   static std::atomic<bool> attr_set[64];
   static std::atomic<int> cus[64];
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_HIP_ERR(hipErrorInvalidDevice);
   if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_b3<true>), hipFuncAttributeMaxDynamicSharedMemorySize, EB_SMEM);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_b3<false>), hipFuncAttributeMaxDynamicSharedMemorySize, EB_SMEM1);
-    if (e != hipSuccess) return LFSR_HIP_ERR(e);
+    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_b3<true>), hipFuncAttributeMaxDynamicSharedMemorySize, EB_SMEM);
+    if (err == hipSuccess) err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_b3<false>), hipFuncAttributeMaxDynamicSharedMemorySize, EB_SMEM1);
+    if (err != hipSuccess) return LFSR_HIP_ERR(err);
     int v = 0;
     cus[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
     attr_set[dev] = true;
   }
   EpiB3Args p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.x_bytes = (int)((long long)B * A * A * h * w * x_stride * 4);
-  p.W1p = reinterpret_cast<const uint4*>(w1_planes); p.W2p = reinterpret_cast<const uint4*>(w2_planes);
-  p.Y = y; p.y_stride = y_stride; p.choffH = choffH; p.choffV = choffV; p.TH = t_h; p.TV = t_v;
-  p.y_bytes = y ? (int)((long long)B * A * A * h * w * y_stride * 4) : 0;
-  p.B = B; p.H = h; p.W = w; p.slope = slope;
-  p.tilesH = (which & 1) ? (B * A * h + EB_LINES - 1) / EB_LINES : 0;
-  p.tilesV = (which & 2) ? (B * A * w + EB_LINES - 1) / EB_LINES : 0;
+  p.X = e.x; p.x_stride = e.x_stride; p.x_choff = e.x_choff; p.x_bytes = (int)(npix * e.x_stride * 4);
+  p.W1p = reinterpret_cast<const uint4*>(e.w0_planes()); p.W2p = reinterpret_cast<const uint4*>(e.w2_planes());
+  p.Y = e.y; p.y_stride = e.y_stride; p.choffH = e.choff_h; p.choffV = e.choff_v; p.TH = e.t_h; p.TV = e.t_v;
+  p.y_bytes = e.y ? (int)(npix * e.y_stride * 4) : 0;
+  p.B = B; p.H = h; p.W = w; p.slope = e.slope;
+  p.tilesH = (e.which & 1) ? (B * A * h + EB_LINES - 1) / EB_LINES : 0;
+  p.tilesV = (e.which & 2) ? (B * A * w + EB_LINES - 1) / EB_LINES : 0;
   const int ngroups = p.tilesH + p.tilesV;
   if (ngroups <= 0) return LFSR_E_ARG;
-  if (which == 3 && (A * h) % EB_LINES == 0 && (A * w) % EB_LINES == 0) { p.tpiH = A * h / EB_LINES; p.tpiV = A * w / EB_LINES; }
+  if (e.which == 3 && (A * h) % EB_LINES == 0 && (A * w) % EB_LINES == 0) { p.tpiH = A * h / EB_LINES; p.tpiV = A * w / EB_LINES; }
   int grid = cus[dev];
   if (grid > ngroups) grid = ngroups;
-  if (y) hipLaunchKernelGGL(k_epi_b3<true>, dim3((unsigned)grid), dim3(512), EB_SMEM, st, p);
+  if (e.y) hipLaunchKernelGGL(k_epi_b3<true>, dim3((unsigned)grid), dim3(512), EB_SMEM, st, p);
   else hipLaunchKernelGGL(k_epi_b3<false>, dim3((unsigned)grid), dim3(512), EB_SMEM1, st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;

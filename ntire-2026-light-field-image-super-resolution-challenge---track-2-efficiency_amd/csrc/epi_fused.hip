@@ -509,12 +509,6 @@ int lfsr_pack_epi_wino(const float* w1_direct_packed, float* out, hipStream_t st
   return LFSR_OK;
 }
 
-bool lfsr_epi_use_b3() {
-  if (lfsr_arith_f32()) return false;
-  const char* esel = lfsr_sel("LFSR_EPI");
-  return !(esel && (esel[0] == 'w' || esel[0] == 'd' || esel[0] == 'f' || esel[0] == 'g'));     // wino | direct | f32 | gather select an fp32-MFMA form
-}
-
 static size_t epi_wino_smem() { return (size_t)(LINES * 36 * LROW + 6 * 32 * LROW) * 4 + (LINES + 4) * 4 + (size_t)5 * 32 * TROW * 4; }
 
 size_t lfsr_epi_fused_smem(int A) {
@@ -525,46 +519,37 @@ bool lfsr_epi_fused_ok(int A, int h, int w) {
   return (A & 1) && A >= 1 && A <= 5 && h <= 32 && w <= 32 && lfsr_epi_fused_smem(A) <= 160 * 1024;
 }
 
-int lfsr_epi_fused_launch(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed, float* y, int y_stride,
-                          int choffH, int choffV, float* t_h, float* t_v, int B, int A, int h, int w, int which, float slope, hipStream_t st) {
-  LfsrOpTimer op_t("epi_fused", B, h * w, st);
-  // which: 1 = horizontal only, 2 = vertical only, 3 = both
-  if (!lfsr_epi_fused_ok(A, h, w)) return LFSR_E_ARG;
-  if (A == 5 && lfsr_epi_use_b3()) {   // default at angRes 5: epi_b3.hip (exact three-term bf16 operands on the bf16 MFMA pipe); LFSR_EPI=wino | direct: this file's fp32-MFMA kernels
-    const int rc = lfsr_epi_b3_launch(x, x_stride, x_choff, w1_packed + 25 * 32 * 64 + LFSR_EPI_WINO_FLOATS, w2_packed + 160 * 32, y, y_stride, choffH, choffV,
-                                      t_h, t_v, B, A, h, w, which, slope, st);
-    if (rc != LFSR_E_ARG) return rc;
-  }
-  if ((long long)B * A * A * h * w * x_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets into x
+// The fp32-MFMA kernels of this file (the default at angRes 5 is epi_b3.hip).  t_h / t_v: optional, the passes' stage-1 activations for the backward.
+// sel: as the dispatcher read it -- epi_direct keeps stage 1 at angRes 5 in direct form (A/B runs), order_pass / order_item the block order below.
+int lfsr_epi_f32_launch(const LfsrEpi& e, const LfsrBranchSel& sel, hipStream_t st) {
+  const int B = e.B, A = e.A, h = e.h, w = e.w, which = e.which;
+  if (!lfsr_epi_fused_ok(A, h, w) || !e.y) return LFSR_E_ARG;
+  if ((long long)B * A * A * h * w * e.x_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets into x
   static std::atomic<bool> attr_set[64];
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_HIP_ERR(hipErrorInvalidDevice);
   const int smem = (int)lfsr_epi_fused_smem(5);
   if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_fused<5>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_fused<0>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_wino5), hipFuncAttributeMaxDynamicSharedMemorySize, (int)epi_wino_smem());
-    if (e != hipSuccess) return LFSR_HIP_ERR(e);
+    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_fused<5>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (err == hipSuccess) err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_fused<0>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (err == hipSuccess) err = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi_wino5), hipFuncAttributeMaxDynamicSharedMemorySize, (int)epi_wino_smem());
+    if (err != hipSuccess) return LFSR_HIP_ERR(err);
     attr_set[dev] = true;
   }
   EpiArgs p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.W1 = w1_packed; p.W2 = w2_packed;
-  p.Y = y; p.y_stride = y_stride; p.choffH = choffH; p.choffV = choffV; p.TH = t_h; p.TV = t_v;
-  p.B = B; p.A = A; p.H = h; p.W = w; p.slope = slope;
-  p.x_bytes = (int)((long long)B * A * A * h * w * x_stride * 4);
+  p.X = e.x; p.x_stride = e.x_stride; p.x_choff = e.x_choff; p.W1 = e.w0_direct(); p.W2 = e.w2_direct();
+  p.Y = e.y; p.y_stride = e.y_stride; p.choffH = e.choff_h; p.choffV = e.choff_v; p.TH = e.t_h; p.TV = e.t_v;
+  p.B = B; p.A = A; p.H = h; p.W = w; p.slope = e.slope;
+  p.x_bytes = (int)((long long)B * A * A * h * w * e.x_stride * 4);
   p.tilesH = (which & 1) ? (B * A * h + LINES - 1) / LINES : 0;
   p.tilesV = (which & 2) ? (B * A * w + LINES - 1) / LINES : 0;
   int grid = p.tilesH + p.tilesV;
   if (grid <= 0) return LFSR_E_ARG;
   // item-major block order when both passes run and an item's lines fill whole tiles (LFSR_EPI_ORDER=pass keeps pass-major order: A/B runs)
-  {
-    const char* osel = lfsr_sel("LFSR_EPI_ORDER");
-    if (which == 3 && (A * h) % LINES == 0 && (A * w) % LINES == 0 && !(osel && osel[0] == 'p')) { p.tpiH = A * h / LINES; p.tpiV = A * w / LINES; p.xcd_swz = (grid % 8 == 0) && !(osel && osel[0] == 'i'); }
-  }
+  if (which == 3 && (A * h) % LINES == 0 && (A * w) % LINES == 0 && !sel.order_pass) { p.tpiH = A * h / LINES; p.tpiV = A * w / LINES; p.xcd_swz = (grid % 8 == 0) && !sel.order_item; }
   // A = 5: stage 1 in Winograd F(2,5) form (the pack appended to the direct one by lfsr_pack_conv_weight); LFSR_EPI=direct keeps the direct form (A/B runs)
-  const char* esel = lfsr_sel("LFSR_EPI");
-  p.W1u = w1_packed + 25 * 32 * 64;
-  if (A == 5 && !(esel && esel[0] == 'd')) hipLaunchKernelGGL(k_epi_wino5, dim3((unsigned)grid), dim3(512), epi_wino_smem(), st, p);
+  p.W1u = e.w0_wino();
+  if (A == 5 && !sel.epi_direct) hipLaunchKernelGGL(k_epi_wino5, dim3((unsigned)grid), dim3(512), epi_wino_smem(), st, p);
   else if (A == 5) hipLaunchKernelGGL(k_epi_fused<5>, dim3((unsigned)grid), dim3(512), lfsr_epi_fused_smem(A), st, p);
   else hipLaunchKernelGGL(k_epi_fused<0>, dim3((unsigned)grid), dim3(512), lfsr_epi_fused_smem(A), st, p);
   LFSR_CHECK_LAUNCH();

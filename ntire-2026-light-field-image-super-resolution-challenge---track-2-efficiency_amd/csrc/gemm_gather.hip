@@ -277,11 +277,47 @@ int lfsr_pack_conv_weight_m(const float* w, float* packed, int O, int C, int tap
   LFSR_CHECK_LAUNCH();
   if (O == 64 && C == 64 && taps == 9 && perm == 0) return lfsr_pack_wino_m(packed, packed + LFSR_CONV3_WINO2_OFF, mask, lfsr_stream(stream));
   if (O == 32 && C == 64 && taps == 25 && perm == 0) {
-    const int rc = lfsr_pack_epi_wino(packed, packed + 25 * 32 * 64, lfsr_stream(stream));
-    return rc ? rc : lfsr_pack_epi_b3(packed, packed + 25 * 32 * 64 + LFSR_EPI_WINO_FLOATS, 0, lfsr_stream(stream));
+    const int rc = lfsr_pack_epi_wino(packed, packed + LFSR_EPI0_WINO_OFF, lfsr_stream(stream));
+    return rc ? rc : lfsr_pack_epi_b3(packed, packed + LFSR_EPI0_PLANES_OFF, 0, lfsr_stream(stream));
   }
-  if (O == 160 && C == 32 && taps == 1 && perm == 0) return lfsr_pack_epi_b3(packed, packed + 160 * 32, 1, lfsr_stream(stream));
+  if (O == 160 && C == 32 && taps == 1 && perm == 0) return lfsr_pack_epi_b3(packed, packed + LFSR_EPI2_PLANES_OFF, 1, lfsr_stream(stream));
   return LFSR_OK;
+}
+
+// the AngConv branch as two gather-GEMM launches, every angRes: a.t receives the stage-1 result
+int lfsr_ang_gather_launch(const LfsrAng& a, hipStream_t st) {
+  if (!a.t || !a.y) return LFSR_E_ARG;
+  GemmArgs p{};
+  p.X = a.x; p.x_stride = a.x_stride; p.x_choff = a.x_choff; p.Wp = a.w0;
+  p.Y = a.t; p.y_stride = 16; p.y_choff = 0;
+  p.M = a.B * a.h * a.w; p.N = 16; p.Npad = 32; p.A = a.A; p.AA = a.A * a.A; p.H = a.h; p.W = a.w; p.ntaps = a.A * a.A; p.CH = 16; p.slope = a.slope;
+  LFSR_RC((launch_gemm<IN_ANG, OUT_SAME, 64, 1>(p, st)));
+  GemmArgs q{};
+  q.X = a.t; q.x_stride = 16; q.x_choff = 0; q.Wp = a.w2;
+  q.Y = a.y; q.y_stride = a.y_stride; q.y_choff = a.y_choff;
+  q.M = a.B * a.h * a.w; q.N = 16 * a.A * a.A; q.Npad = npad32(q.N); q.A = a.A; q.AA = a.A * a.A; q.H = a.h; q.W = a.w; q.ntaps = 1; q.CH = 16; q.slope = a.slope;
+  return launch_gemm<IN_SAME, OUT_VIEWS, 16, 1>(q, st);
+}
+
+// one EPI pass as two gather-GEMM launches: tmp (B*A*h*w, 32) receives the stage-1 activations
+static int epi_gather_pass(const LfsrEpi& e, float* tmp, int y_choff, bool vertical, hipStream_t st) {
+  GemmArgs p{};
+  p.X = e.x; p.x_stride = e.x_stride; p.x_choff = e.x_choff; p.Wp = e.w0_direct();
+  p.Y = tmp; p.y_stride = 32; p.y_choff = 0;
+  p.M = e.B * e.A * e.h * e.w; p.N = 32; p.Npad = 32; p.A = e.A; p.AA = e.A * e.A; p.H = e.h; p.W = e.w; p.ntaps = e.A * e.A; p.CH = 32; p.slope = e.slope;
+  LFSR_RC(vertical ? (launch_gemm<IN_EPIV, OUT_SAME, 64, 1>(p, st)) : (launch_gemm<IN_EPIH, OUT_SAME, 64, 1>(p, st)));
+  GemmArgs q{};
+  q.X = tmp; q.x_stride = 32; q.x_choff = 0; q.Wp = e.w2_direct();
+  q.Y = e.y; q.y_stride = e.y_stride; q.y_choff = y_choff;
+  q.M = e.B * e.A * e.h * e.w; q.N = 32 * e.A; q.Npad = npad32(q.N); q.A = e.A; q.AA = e.A * e.A; q.H = e.h; q.W = e.w; q.ntaps = 1; q.CH = 32; q.slope = e.slope;
+  return vertical ? launch_gemm<IN_SAME, OUT_EPIV, 32, 1>(q, st) : launch_gemm<IN_SAME, OUT_EPIH, 32, 1>(q, st);
+}
+
+// the passes of e.which, horizontal first, every angRes; t_h and t_v may be one buffer
+int lfsr_epi_gather_launch(const LfsrEpi& e, hipStream_t st) {
+  if (!e.y || !(e.which & 3) || ((e.which & 1) && !e.t_h) || ((e.which & 2) && !e.t_v)) return LFSR_E_ARG;
+  if (e.which & 1) LFSR_RC(epi_gather_pass(e, e.t_h, e.choff_h, false, st));
+  return (e.which & 2) ? epi_gather_pass(e, e.t_v, e.choff_v, true, st) : LFSR_OK;
 }
 
 extern "C" {
@@ -324,75 +360,6 @@ int lfsr_pointwise_fwd(const float* x, int x_stride, int x_choff, int cin, const
     case 144: return two ? launch_gemm<IN_SAME, OUT_SAME, 144, 2>(p, st) : launch_gemm<IN_SAME, OUT_SAME, 144, 1>(p, st);
     default: return LFSR_E_ARG;
   }
-}
-
-int lfsr_angconv_fwd(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed,
-                     float* tmp, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope, void* stream) {
-  LfsrOpTimer op_t("angconv", B, h * w, lfsr_stream(stream));
-  if (!x || !w1_packed || !w2_packed || !tmp || !y || B <= 0 || A <= 0 || h <= 0 || w <= 0) return LFSR_E_ARG;
-  if (x_stride < x_choff + 64 || y_stride < y_choff + 16 || (x_stride | x_choff) & 3) return LFSR_E_ARG;
-  hipStream_t st = lfsr_stream(stream);
-  {
-    const char* sel = lfsr_sel("LFSR_ANG");   // LFSR_ANG=gather forces the two-launch gather-GEMM path (A/B runs)
-    if (!(sel && sel[0] == 'g') && lfsr_ang_fused_ok(A) && !((y_stride | y_choff) & 3))
-      return lfsr_ang_fused_launch(x, x_stride, x_choff, w1_packed, w2_packed, tmp, y, y_stride, y_choff, B, A, h, w, slope, st);
-  }
-  GemmArgs p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wp = w1_packed;
-  p.Y = tmp; p.y_stride = 16; p.y_choff = 0;
-  p.M = B * h * w; p.N = 16; p.Npad = 32; p.A = A; p.AA = A * A; p.H = h; p.W = w; p.ntaps = A * A; p.CH = 16; p.slope = slope;
-  int rc = launch_gemm<IN_ANG, OUT_SAME, 64, 1>(p, st);
-  if (rc) return rc;
-  GemmArgs q{};
-  q.X = tmp; q.x_stride = 16; q.x_choff = 0; q.Wp = w2_packed;
-  q.Y = y; q.y_stride = y_stride; q.y_choff = y_choff;
-  q.M = B * h * w; q.N = 16 * A * A; q.Npad = npad32(q.N); q.A = A; q.AA = A * A; q.H = h; q.W = w; q.ntaps = 1; q.CH = 16; q.slope = slope;
-  return launch_gemm<IN_SAME, OUT_VIEWS, 16, 1>(q, st);
-}
-
-int lfsr_epiconv_gather(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed,
-                          float* tmp, float* y, int y_stride, int y_choff, int B, int A, int h, int w, int vertical, float slope, hipStream_t st) {
-  GemmArgs p{};
-  p.X = x; p.x_stride = x_stride; p.x_choff = x_choff; p.Wp = w1_packed;
-  p.Y = tmp; p.y_stride = 32; p.y_choff = 0;
-  p.M = B * A * h * w; p.N = 32; p.Npad = 32; p.A = A; p.AA = A * A; p.H = h; p.W = w; p.ntaps = A * A; p.CH = 32; p.slope = slope;
-  int rc = vertical ? launch_gemm<IN_EPIV, OUT_SAME, 64, 1>(p, st) : launch_gemm<IN_EPIH, OUT_SAME, 64, 1>(p, st);
-  if (rc) return rc;
-  GemmArgs q{};
-  q.X = tmp; q.x_stride = 32; q.x_choff = 0; q.Wp = w2_packed;
-  q.Y = y; q.y_stride = y_stride; q.y_choff = y_choff;
-  q.M = B * A * h * w; q.N = 32 * A; q.Npad = npad32(q.N); q.A = A; q.AA = A * A; q.H = h; q.W = w; q.ntaps = 1; q.CH = 32; q.slope = slope;
-  return vertical ? launch_gemm<IN_SAME, OUT_EPIV, 32, 1>(q, st) : launch_gemm<IN_SAME, OUT_EPIH, 32, 1>(q, st);
-}
-
-static bool epi_use_fused(int A, int h, int w) {
-  const char* sel = lfsr_sel("LFSR_EPI");   // LFSR_EPI=gather forces the two-launch gather-GEMM path (A/B runs)
-  return !(sel && sel[0] == 'g') && lfsr_epi_fused_ok(A, h, w);
-}
-
-int lfsr_epiconv_fwd(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed,
-                     float* tmp, float* y, int y_stride, int y_choff, int B, int A, int h, int w, int vertical, float slope, void* stream) {
-  LfsrOpTimer op_t("epiconv", B, h * w, lfsr_stream(stream));
-  if (!x || !w1_packed || !w2_packed || !y || B <= 0 || A <= 0 || h <= 0 || w <= 0) return LFSR_E_ARG;
-  if (x_stride < x_choff + 64 || y_stride < y_choff + 32 || (x_stride | x_choff) & 3) return LFSR_E_ARG;
-  if (epi_use_fused(A, h, w) && !((y_stride | y_choff) & 3) && (long long)B * A * A * h * w * x_stride * 4 < (1LL << 31))   // (16-B output vectors, 32-bit offsets)
-    return lfsr_epi_fused_launch(x, x_stride, x_choff, w1_packed, w2_packed, y, y_stride, y_choff, y_choff, vertical ? nullptr : tmp, vertical ? tmp : nullptr, B, A, h, w,
-                                 vertical ? 2 : 1, slope, lfsr_stream(stream));     // tmp (may be NULL here): receives the pass's stage-1 activation, as the gather path leaves it
-  if (!tmp) return LFSR_E_ARG;
-  return lfsr_epiconv_gather(x, x_stride, x_choff, w1_packed, w2_packed, tmp, y, y_stride, y_choff, B, A, h, w, vertical, slope, lfsr_stream(stream));
-}
-
-int lfsr_epiconv_hv_fwd(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed,
-                        float* tmp, float* y, int y_stride, int choff_h, int choff_v, int B, int A, int h, int w, float slope, void* stream) {
-  LfsrOpTimer op_t("epiconv_hv", B, h * w, lfsr_stream(stream));
-  if (!x || !w1_packed || !w2_packed || !y || B <= 0 || A <= 0 || h <= 0 || w <= 0) return LFSR_E_ARG;
-  if (x_stride < x_choff + 64 || y_stride < choff_h + 32 || y_stride < choff_v + 32 || (x_stride | x_choff) & 3) return LFSR_E_ARG;
-  if (epi_use_fused(A, h, w) && !((y_stride | choff_h | choff_v) & 3) && (long long)B * A * A * h * w * x_stride * 4 < (1LL << 31))
-    return lfsr_epi_fused_launch(x, x_stride, x_choff, w1_packed, w2_packed, y, y_stride, choff_h, choff_v, nullptr, nullptr, B, A, h, w, 3, slope, lfsr_stream(stream));
-  if (!tmp) return LFSR_E_ARG;
-  int rc = lfsr_epiconv_gather(x, x_stride, x_choff, w1_packed, w2_packed, tmp, y, y_stride, choff_h, B, A, h, w, 0, slope, lfsr_stream(stream));
-  if (rc) return rc;
-  return lfsr_epiconv_gather(x, x_stride, x_choff, w1_packed, w2_packed, tmp, y, y_stride, choff_v, B, A, h, w, 1, slope, lfsr_stream(stream));
 }
 
 int lfsr_initconv_fwd(const float* x, const float* w, float* y, int y_stride, int y_choff, int B, int A, int h, int wd, void* stream) {

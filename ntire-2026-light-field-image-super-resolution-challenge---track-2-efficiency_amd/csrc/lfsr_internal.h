@@ -115,42 +115,86 @@ int lfsr_pack_wino_m(const float* direct_packed, float* out, int mask, hipStream
 int lfsr_pack_conv_weight_m(const float* w, float* packed, int O, int C, int taps, int perm, int ch, int mask, void* stream);
 int lfsr_pack_weight_T_m(const float* w, float* out, int O, int C, int T, int flip, int mask, hipStream_t st);
 int lfsr_pack_wino4(const float* direct_packed, float* out, hipStream_t st);
-// ang_fused.hip: the AngConv branch (conv AxA stride A 64->16, 1x1 16->16AA, PixelShuffle(A)) in one launch
-bool lfsr_ang_fused_ok(int A);
-int lfsr_ang_fused_launch(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed, float* t, float* y,
-                          int y_stride, int y_choff, int B, int A, int h, int w, float slope, hipStream_t st);     // y = NULL: stage 1 only
-// epi_fused.hip: Winograd F(2,5) pack of an EPIConv.0 weight (O = 32, C = 64, taps = 25 = 5 x 5): LFSR_EPI_WINO_FLOATS after the direct pack
+// ---- DistgSSR's angular and epipolar branches and the fused block tail: three operand structs, their launchers, one dispatcher (distg_branch.cpp) ----
+// The packs of the EPI branch's weights (lfsr_pack_conv_weight).  EPIConv.0 (O = 32, C = 64, taps = 25 = 5 x 5) at angRes 5: the direct pack, its Winograd F(2,5) copy
+// (epi_fused.hip), then its three bf16 planes in the order k_epi_b3 stages them (epi_b3.hip).  EPIConv.2 (O = 160, C = 32, taps = 1): the direct pack, then its planes.
+// Both plane images are 16-B aligned.  The _OFF names are the only place that spells the layout out.
+#define LFSR_EPI0_DIRECT_FLOATS (25 * 32 * 64)
 #define LFSR_EPI_WINO_FLOATS (5 * 6 * 32 * 64)
-// epi_b3.hip: the three bf16 planes of the EPI branch's weights in the order k_epi_b3 stages them: after the F(2,5) copy of EPIConv.0 (O = 32, C = 64, taps = 25)
-// and after the direct pack of EPIConv.2 (O = 160, C = 32, taps = 1), both 16-B aligned
 #define LFSR_EPI_B3_W1_FLOATS (25 * 32 * 64 * 3 / 2)
+#define LFSR_EPI2_DIRECT_FLOATS (160 * 32)
 #define LFSR_EPI_B3_W2_FLOATS (160 * 32 * 3 / 2)
-bool lfsr_epi_use_b3();     // (epi_fused.hip) LFSR_EPI unset: the three-term bf16 kernel at angRes 5
+#define LFSR_EPI0_WINO_OFF LFSR_EPI0_DIRECT_FLOATS
+#define LFSR_EPI0_PLANES_OFF (LFSR_EPI0_DIRECT_FLOATS + LFSR_EPI_WINO_FLOATS)
+#define LFSR_EPI2_PLANES_OFF LFSR_EPI2_DIRECT_FLOATS
+int lfsr_pack_epi_wino(const float* w1_direct_packed, float* out, hipStream_t st);
 int lfsr_pack_epi_b3(const float* direct_packed, float* out, int kind, hipStream_t st);              // kind 0: EPIConv.0, 1: EPIConv.2
 int lfsr_pack_epi_b3_batch(const LfsrPackDesc* table_dev, int n, hipStream_t st);                     // src = the direct pack, dst = its planes, kind as above
-int lfsr_epi_b3_launch(const float* x, int x_stride, int x_choff, const float* w1_planes, const float* w2_planes, float* y, int y_stride,
-                       int choffH, int choffV, float* t_h, float* t_v, int B, int A, int h, int w, int which, float slope, hipStream_t st);   // y = NULL (which = 3): stage 1 only
-int lfsr_pack_epi_wino(const float* w1_direct_packed, float* out, hipStream_t st);
-// distg_tail.hip: DistgSSR's block tail at angRes 5 -- the branches' second stages, the concat and fuse.0 in one launch (t_a / t_h / t_v: the stage-1 results
-// of lfsr_ang_fused_launch / lfsr_epi_b3_launch with y = NULL; we2_planes: EPIConv.2's three bf16 planes; wf_packed: fuse.0 [64][144])
-bool lfsr_distg_tail_ok(int A, int h, int w, const float* x, int x_stride, int x_choff, const float* t_h, const float* t_v);
-int lfsr_distg_tail_launch(const float* spa, int spa_stride, int spa_choff, const float* t_a, const float* t_h, const float* t_v, const float* wa2_packed,
-                           const float* we2_planes, const float* wf_packed, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope,
-                           hipStream_t st);
-// distg_bf16.hip: the EPI stage 1 and the block tail on bf16 operands (lfsr_set_branch_arithmetic(LFSR_BRANCH_ARITH_BF16)); w1_direct / we2_direct: the fp32 direct
-// packs of EPIConv.0 / EPIConv.2 (rounded while a block stages them).  LFSR_E_ARG = not covered, nothing launched
-int lfsr_epi_bf16_launch(const float* x, int x_stride, int x_choff, const float* w1_direct, float* t_h, float* t_v, int B, int A, int h, int w, float slope,
-                         hipStream_t st);
-int lfsr_distg_tail_bf16_launch(const float* spa, int spa_stride, int spa_choff, const float* t_a, const float* t_h, const float* t_v, const float* wa2_packed,
-                                const float* we2_direct, const float* wf_packed, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope,
-                                hipStream_t st);
-// the two launches of a fused block tail as the branch arithmetic selects them (w_epi0 / w_epi2: the whole packs): the bf16 form under the mode unless
-// LFSR_ARITH_F32 is set, falling back to the default launcher where it does not cover the call
-int lfsr_distg_epi1_launch(const float* x, int x_stride, int x_choff, const float* w_epi0, float* t_h, float* t_v, int B, int A, int h, int w, float slope,
-                           hipStream_t st);
-int lfsr_distg_tail2_launch(const float* spa, int spa_stride, int spa_choff, const float* t_a, const float* t_h, const float* t_v, const float* wa2_packed,
-                            const float* w_epi2, const float* wf_packed, float* y, int y_stride, int y_choff, int B, int A, int h, int w, float slope,
-                            hipStream_t st);
+// The AngConv branch (DistgSSR.py:84-90): t = lrelu(conv AxA stride A, 64 -> 16) (16 floats per LR pixel, kept for the backward), y = lrelu(1x1 16 -> 16 A A) after
+// PixelShuffle(A).  y = null: stage 1 only (w2 unused).
+struct LfsrAng {
+  const float* x; int x_stride, x_choff;
+  const float *w0, *w2;                             // AngConv.0 (perm 0), AngConv.2 (perm 1, ch 16)
+  float* t;
+  float* y; int y_stride, y_choff;
+  int B, A, h, w;
+  float slope;
+};
+// The EPIConv branch (DistgSSR.py:91-97,108), one pass or both: t = lrelu(conv 1 x A A over the lines of a pass, 64 -> 32), y = lrelu(1x1 32 -> 32 A) after the 1-D
+// PixelShuffle.  which: 1 = the horizontal pass, 2 = the vertical one, 3 = both; t_h / t_v ((B A h w), 32) receive a pass's stage-1 result, optional for the fused
+// kernels; y = null: stage 1 only (w2 unused).  w0 / w2: the bases of the whole packs.
+struct LfsrEpi {
+  const float* x; int x_stride, x_choff;
+  const float *w0, *w2;
+  float* y; int y_stride, choff_h, choff_v;
+  float *t_h, *t_v;
+  int B, A, h, w, which;
+  float slope;
+  const float* w0_direct() const { return w0; }
+  const float* w0_wino() const { return w0 ? w0 + LFSR_EPI0_WINO_OFF : nullptr; }          // (the copies exist at angRes 5 only)
+  const float* w0_planes() const { return w0 ? w0 + LFSR_EPI0_PLANES_OFF : nullptr; }
+  const float* w2_direct() const { return w2; }
+  const float* w2_planes() const { return w2 ? w2 + LFSR_EPI2_PLANES_OFF : nullptr; }
+};
+// The block tail at angRes 5: the branches' second stages on their stage-1 results t_a / t_h / t_v, the concat with spa (the SpaConv.2 output) and fuse.0 ([64][144])
+struct LfsrDistgTail {
+  const float* spa; int spa_stride, spa_choff;
+  const float *t_a, *t_h, *t_v;
+  const float *w_ang2, *w_epi2, *w_fuse0;           // w_epi2: the base of the whole pack
+  float* y; int y_stride, y_choff;
+  int B, A, h, w;
+  float slope;
+  const float* w_epi2_direct() const { return w_epi2; }
+  const float* w_epi2_planes() const { return w_epi2 ? w_epi2 + LFSR_EPI2_PLANES_OFF : nullptr; }
+};
+// which kernel runs.  lfsr_branch_sel: LFSR_EPI=wino | direct | f32 | gather, LFSR_EPI_ORDER=pass | item, LFSR_ANG=gather, LFSR_DISTG_TAIL=0 with lfsr_set_arithmetic(f32)
+// folded in, parsed at every call, never cached; the only reader of their characters.  epi_f32: an fp32-MFMA form of the EPI branch (any value above, or the arithmetic)
+struct LfsrBranchSel { bool epi_gather, epi_direct, epi_f32, ang_gather, tail_off, order_pass, order_item; };
+LfsrBranchSel lfsr_branch_sel();
+// A launcher launches its own kernel(s) only; LFSR_E_ARG = the call is not covered and nothing was launched or written: the dispatcher goes down its chain.
+bool lfsr_ang_fused_ok(int A);
+bool lfsr_epi_fused_ok(int A, int h, int w);
+int lfsr_ang_fused_launch(const LfsrAng& a, hipStream_t st);                              // ang_fused.hip: the branch in one launch, A <= 5
+int lfsr_ang_gather_launch(const LfsrAng& a, hipStream_t st);                             // gemm_gather.hip: the gather-GEMM pair, every A; needs y
+int lfsr_epi_b3_launch(const LfsrEpi& e, hipStream_t st);                                 // epi_b3.hip: the exact three-term bf16 split, A = 5; y = null with which = 3
+int lfsr_epi_f32_launch(const LfsrEpi& e, const LfsrBranchSel& sel, hipStream_t st);      // epi_fused.hip, fp32 MFMA: F(2,5) (A = 5) | direct<5> (sel.epi_direct) | direct (A < 5); needs y
+int lfsr_epi_gather_launch(const LfsrEpi& e, hipStream_t st);                             // gemm_gather.hip: the gather-GEMM pair per pass, every A; needs y and the passes' t
+int lfsr_epi_bf16_launch(const LfsrEpi& e, hipStream_t st);                               // distg_bf16.hip, bf16 operands (LFSR_BRANCH_ARITH_BF16): stage 1 of both passes only
+int lfsr_distg_tail_launch(const LfsrDistgTail& t, hipStream_t st);                       // distg_tail.hip: reads EPIConv.2's planes
+int lfsr_distg_tail_bf16_launch(const LfsrDistgTail& t, hipStream_t st);                  // distg_bf16.hip: reads EPIConv.2's direct pack
+// distg_branch.cpp: what lfsr_angconv_fwd, lfsr_epiconv_fwd / _hv_fwd and lfsr_distg_branch_tail_fwd run behind their argument checks, and what the DistgSSR drivers
+// call; op timers "angconv", "epiconv" (one pass) / "epiconv_hv" (both), "epi_fused" (around any fused EPI launch) and "distg_tail".
+int lfsr_ang_run(const LfsrAng& a, hipStream_t st);
+int lfsr_epi_run(const LfsrEpi& e, float* scratch, hipStream_t st);     // scratch ((B A h w), 32; may be null): the gather pair's stage 1 for a pass without t_h / t_v
+// The fused tail covers a block when the default arithmetic runs the three kernels it replaces in their three-term bf16 / fp32-MFMA forms at angRes 5 (no lab
+// selector moves one of them) and the stage-1 kernels take e's geometry and operands; e.x may be null (not yet known)
+bool lfsr_distg_tail_covers(const LfsrEpi& e);
+// ... and its three launches, one by one (the inference driver brackets each with its profiling events) and together: the angular stage 1, the EPI stage 1 and the
+// tail, the last two on bf16 operands under lfsr_set_branch_arithmetic unless LFSR_ARITH_F32 is set, where those kernels cover the call
+int lfsr_distg_ang1_run(const LfsrAng& a, hipStream_t st);
+int lfsr_distg_epi1_run(const LfsrEpi& e, hipStream_t st);
+int lfsr_distg_tail2_run(const LfsrDistgTail& t, hipStream_t st);
+int lfsr_distg_block_tail_run(const LfsrAng& a, const LfsrEpi& e, const LfsrDistgTail& t, hipStream_t st);
 // ang3x3_bf16.hip: lfsr_angconv3x3_fwd's kernel on bf16 operands (lfsr_set_ang_arithmetic(LFSR_ANG_ARITH_BF16)); the caller has checked the operands
 int lfsr_ang3x3_bf16_launch(const float* x, int x_stride, int x_choff, const float* w_packed, const float* bias, const float* in_bias, float* y, int y_stride,
                             int y_choff, int B, int A, int npix, hipStream_t st);
@@ -161,15 +205,6 @@ int lfsr_conv3x3_wide_run(const float* x, int x_stride, int x_choff, int cin, co
                           int r1_stride, int r1_choff, int n_img, int h, int w, float slope, int A, hipStream_t st);
 int lfsr_conv3x3_wide_bf16_launch(const float* x, int x_stride, int x_choff, int cin, const float* w_packed, float* y, int y_stride, int y_choff,
                                   const float* r1, int r1_stride, int r1_choff, int n_img, int h, int w, float slope, hipStream_t st);
-// epi_fused.hip  (t_h / t_v: optional (B*A*h*w, 32) buffers receiving the post-LeakyReLU stage-1 activations for backward)
-bool lfsr_epi_fused_ok(int A, int h, int w);
-int lfsr_epi_fused_launch(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed, float* y, int y_stride,
-                          int choffH, int choffV, float* t_h, float* t_v, int B, int A, int h, int w, int which, float slope, hipStream_t st);
-
-// gemm_gather.hip: two-launch gather-GEMM EPI path; tmp (B*A*h*w, 32) receives the stage-1 activations
-extern "C" int lfsr_epiconv_gather(const float* x, int x_stride, int x_choff, const float* w1_packed, const float* w2_packed,
-                        float* tmp, float* y, int y_stride, int y_choff, int B, int A, int h, int w, int vertical, float slope, hipStream_t st);
-
 // bwd_ops.hip: one entry for every backward gather-GEMM (dgrad) instantiation
 struct LfsrGemm {
   int in_mode, out_mode, cin;
@@ -228,6 +263,8 @@ bool lfsr_rowgemm_ok(const LfsrLin& c), lfsr_rowgemm_ln_ok(const LfsrLin& c), lf
 // in, parsed at every call, never cached; the only reader of their characters.  f32 / ffn_f32 / dgrad_f32: the fp32-MFMA kernels; wide: LFSR_ROWGEMM=128
 struct LfsrGemmSel { bool f32, wide, ffn_f32, ffn_chunks, lnlin, dgrad_f32, dgrad_gather; };
 LfsrGemmSel lfsr_gemm_sel();
+#define LFSR_ROWGEMM_MIN_ROWS 2048      // a linear over fewer rows leaves the family (lfsr_linear_run); what a caller needs to know to tell which kernel its linear runs
+bool lfsr_rowgemm_enabled();            // LFSR_NO_ROWGEMM not set (A/B runs: every plain linear on its caller's gather-GEMM)
 LfsrLinFn lfsr_linear_run, lfsr_linear_ln_run, lfsr_dgrad144_run; LfsrFfnFn lfsr_ffn_run;   // lfsr_linear_run's LFSR_E_ARG: no row-streaming kernel covers the call, the caller runs its gather-GEMM
 size_t lfsr_ffn_b3_presplit_bytes(int K1, int H, int N2);
 int lfsr_ffn_b3_presplit(const float* w1_packed, const float* w2_packed, int K1, int H, int N2, void* out, hipStream_t st);

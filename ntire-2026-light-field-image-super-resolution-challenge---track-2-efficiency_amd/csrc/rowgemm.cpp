@@ -22,8 +22,10 @@ LfsrGemmSel lfsr_gemm_sel() {
   return s;
 }
 
+bool lfsr_rowgemm_enabled() { return !lfsr_sel("LFSR_NO_ROWGEMM"); }
+
 int lfsr_linear_run(const LfsrLin& c, hipStream_t st) {
-  if (c.M < 2048 || lfsr_sel("LFSR_NO_ROWGEMM") || !lfsr_rowgemm_ok(c)) return LFSR_E_ARG;
+  if (c.M < LFSR_ROWGEMM_MIN_ROWS || !lfsr_rowgemm_enabled() || !lfsr_rowgemm_ok(c)) return LFSR_E_ARG;
   int rc = LFSR_E_ARG;
   if (!lfsr_gemm_sel().f32 && !c.bias && (c.K == 64 || c.K == 128 || c.K == 144)) {
     if (lfsr_gemm_arith_bf16() && c.K != 144) rc = lfsr_gemm_bf16_launch(c, st);      // K = 144 (DistgSSR's fuse.0) keeps the default

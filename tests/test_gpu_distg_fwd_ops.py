@@ -186,7 +186,7 @@ EPI_X = (80, 16)
 
 
 def epi_kernel(geom, sel="", f32=False, slope=0.1):
-    """the kernel behind lfsr_epiconv_fwd / _hv_fwd on 16-byte aligned outputs, read from gemm_gather.hip (the entry points) and epi_fused.hip (lfsr_epi_fused_launch)"""
+    """the kernel behind lfsr_epiconv_fwd / _hv_fwd on 16-byte aligned outputs, read from distg_branch.cpp (lfsr_epi_run, the chain behind both entry points) and the launchers it names (epi_b3.hip, epi_fused.hip)"""
     _, A, h, w = geom
     if sel == "gather" or not (A % 2 == 1 and A <= 5 and h <= 32 and w <= 32):
         return "gather-GEMM"
@@ -335,7 +335,7 @@ def test_epiconv_gather_only_geometries(B, A, h, w, monkeypatch):
 
 @pytest.mark.parametrize("B,A,h,w", [(1, 5, 8, 8), (4, 5, 8, 8), (1, 5, 8, 16), (1, 3, 8, 8)])
 def test_epiconv_hv_block_order_changes_no_bit(B, A, h, w, monkeypatch):
-    """LFSR_EPI_ORDER is read by lfsr_epi_fused_launch (k_epi_wino5, k_epi_fused<5>, k_epi_fused<0>) for the two-pass call on geometries whose lines fill whole
+    """LFSR_EPI_ORDER reaches lfsr_epi_f32_launch (k_epi_wino5, k_epi_fused<5>, k_epi_fused<0>) for the two-pass call on geometries whose lines fill whole
     tiles: unset = item-major blocks with the XCD swizzle when the grid is a multiple of 8, `item` = item-major without it, `pass` = pass-major.  Only which block
     computes which tile changes: equal bits, and right.  epi_b3.hip (the default at angRes 5) does not read it"""
     run = _EpiRun((B, A, h, w))
@@ -355,7 +355,7 @@ def test_epiconv_hv_block_order_changes_no_bit(B, A, h, w, monkeypatch):
 
 @pytest.mark.parametrize("B,A,h,w", [(1, 5, 8, 8), (1, 3, 8, 8), (2, 1, 9, 7)])
 def test_epiconv_selector_reaches_the_named_launcher(B, A, h, w, monkeypatch):
-    """an observable beside the bits (at angRes 1 the fused kernel and the gather-GEMM give the same): lfsr_epi_fused_launch brackets its launch with an `epi_fused`
+    """an observable beside the bits (at angRes 1 the fused kernel and the gather-GEMM give the same): lfsr_epi_run brackets any fused launch with an `epi_fused`
     record of the operator timing hooks, the gather-GEMM path has none.  Unset, wino and direct reach it; gather does not"""
     run = _EpiRun((B, A, h, w))
     for sel in ("", "wino", "direct", "gather"):

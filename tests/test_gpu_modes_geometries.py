@@ -59,10 +59,10 @@ def reach(model, geom, train):
     # internet_train.hip:347-348); DistgSSR's fuse.0 has K = 144 and keeps the default (rowgemm.cpp:29)
     if transformer or (model == "LF_InterNet" and B * h * w >= 2048):
         out.add("gemm")
-    # BRANCH_ARITH_BF16: the two launches of the fused block tail (distg_bf16.hip:568, 578), which only the inference forward takes (distgssr.cpp:289-297; the
-    # training forward keeps the three-kernel sequence, distgssr.cpp:447-457) and only where tail_ok holds (distgssr.cpp:251: 2048 view pixels or more, and
-    # distg_tail.hip:331: A = 5, h <= 32, w <= 32).  At lines of 33 the driver runs the unfused fp32 branches and the switch reaches nothing
-    # (distg_bf16.hip:514, 540 are the launchers' own bounds; lfsr_distg_tail_ok, which lfsr_distg_branch_tail_fwd checks too, is narrower than both, so neither
+    # BRANCH_ARITH_BF16: the two launches of the fused block tail (lfsr_distg_epi1_run / _tail2_run, distg_branch.cpp), which only the inference forward takes (the
+    # training forward keeps the three-kernel sequence) and only where its tail_ok holds (LFSR_ROWGEMM_MIN_ROWS = 2048 view pixels or more, and
+    # lfsr_distg_tail_covers: A = 5, h <= 32, w <= 32).  At lines of 33 the driver runs the unfused fp32 branches and the switch reaches nothing
+    # (the launchers of distg_bf16.hip have bounds of their own; lfsr_distg_tail_covers, which lfsr_distg_branch_tail_fwd checks too, is narrower than both, so neither
     # launcher is ever asked for a view it declines)
     if model == "DistgSSR" and not train and A == 5 and h <= 32 and w <= 32 and B * A * A * h * w >= 2048:
         out.add("branch")
