@@ -4,6 +4,8 @@
 // caller's workspace first).
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include "lfsr_internal.h"
 
 namespace {
@@ -33,6 +35,24 @@ int mask_lrelu(const float* dy, int dy_stride, int dy_choff, const float* y, int
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }
+
+// the four weight gradients of the branches, pointers apart: what the backward submits and what lfsr_branch_bwd_partial_floats sizes
+LfsrWgrad ang2_wgrad(int B, int A, int h, int w) {      // AngConv.2 (16 A A, 16): G gathered from the A A views, the taps are the pixel shuffle's chunks
+  LfsrWgrad g = lfsr_wgrad_gather(LFSR_IN_ANG, LFSR_IN_SAME, B * h * w, 16, 16, A * A, A, h, w);
+  g.O = 16 * A * A; g.C = 16; g.T = A * A; g.perm = 1; g.ch = 16; g.chunk_mode = 1;
+  return g;
+}
+LfsrWgrad ang0_wgrad(int B, int A, int h, int w) { return lfsr_wgrad_gather(LFSR_IN_SAME, LFSR_IN_ANG, B * h * w, 16, 64, A * A, A, h, w); }      // AngConv.0 (16, 64, A, A)
+LfsrWgrad epi2_wgrad(int B, int A, int h, int w) {      // EPIConv.2 (32 A, 32), one pass (gmode: LFSR_IN_CHK_H / _V)
+  LfsrWgrad g = lfsr_wgrad_gather(LFSR_IN_CHK_H, LFSR_IN_SAME, B * A * h * w, 32, 32, A, A, h, w);
+  g.O = 32 * A; g.C = 32; g.T = A; g.ch = 32; g.chunk_mode = 1;
+  return g;
+}
+LfsrWgrad epi0_wgrad(int B, int A, int h, int w) {      // EPIConv.0 (32, 64, 1, A A)
+  LfsrWgrad g{};
+  g.form = LFSR_WG_EPI0; g.g_stride = 32; g.x_stride = 64; g.B = B; g.A = A; g.h = h; g.w = w;
+  return g;
+}
 }  // namespace
 
 // AngConv: y = PixelShuffle_A(lrelu(W2 . a16)), a16 = lrelu(W0 (*) x) (A x A, stride A).  dcat: dLoss/dy inside a VCL buffer (16 channels at dc_choff).
@@ -41,8 +61,10 @@ int mask_lrelu(const float* dy, int dy_stride, int dy_choff, const float* y, int
 int lfsr_ang_branch_bwd_p1(const float* dcat, int dc_stride, int dc_choff, const float* xin, const float* a16, const float* w2T_packed, float* dw0, float* dw2,
                            float* dA16, float* P, int B, int A, int h, int w, float slope, hipStream_t st) {
   const int AA = A * A, nlr = B * h * w;
-  LFSR_RC(lfsr_wgrad_launch(LFSR_IN_ANG, LFSR_IN_SAME, dcat, dc_stride, dc_choff, a16, 16, 0, P, nlr, 16, 16, A, h, w, AA, st));
-  LFSR_RC(lfsr_wgrad_reduce(P, lfsr_wgrad_splits(nlr, AA, 16), nullptr, 0, dw2, 16 * AA, 16, AA, 1, 16, 0, 0, 1, st));
+  LfsrWgrad g2 = ang2_wgrad(B, A, h, w), g0 = ang0_wgrad(B, A, h, w);
+  g2.G = dcat; g2.g_stride = dc_stride; g2.g_choff = dc_choff; g2.X = a16; g2.dW = dw2; g2.part = P; g2.part_floats = lfsr_branch_bwd_partial_floats(B, A, h, w);
+  g0.G = dA16; g0.X = xin; g0.dW = dw0; g0.part = P; g0.part_floats = g2.part_floats;
+  LFSR_RC(lfsr_wgrad_run(g2, st));
   {
     LfsrGemm q{};
     q.in_mode = LFSR_IN_ANG; q.out_mode = LFSR_OUT_SAME; q.cin = 16; q.X = dcat; q.x_stride = dc_stride; q.x_choff = dc_choff; q.Wp = w2T_packed;
@@ -50,9 +72,7 @@ int lfsr_ang_branch_bwd_p1(const float* dcat, int dc_stride, int dc_choff, const
     q.M = nlr; q.N = 16; q.A = A; q.h = h; q.w = w; q.ntaps = AA; q.CH = 16;
     LFSR_RC(lfsr_bwd_gemm(q, st));
   }
-  LFSR_RC(lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_ANG, dA16, 16, 0, xin, 64, 0, P, nlr, 16, 64, A, h, w, AA, st));
-  LFSR_RC(lfsr_wgrad_reduce(P, lfsr_wgrad_splits(nlr, AA, 64), nullptr, 0, dw0, 16, 64, AA, 0, 0, 0, 0, 0, st));
-  return LFSR_OK;
+  return lfsr_wgrad_run(g0, st);
 }
 
 int lfsr_ang_branch_bwd_p2(const float* dA16, const float* w0_packed, const float* w0T_packed, float* dx, int B, int A, int h, int w, hipStream_t st) {
@@ -79,20 +99,23 @@ int lfsr_ang_branch_bwd(const float* dcat, int dc_stride, int dc_choff, const fl
 int lfsr_epi_branch_bwd_p1(const float* dcat, int dc_stride, int choff_h, int choff_v, const float* eh, const float* ev, const float* w2T_packed, float* dw2,
                            float* dEh, float* dEv, float* const P[4], int B, int A, int h, int w, float slope, hipStream_t st) {
   const int nepi = B * A * h * w;
+  LfsrWgrad g = epi2_wgrad(B, A, h, w);      // the passes share EPIConv.2's weights: two slab sets, one reduce
+  g.G = dcat; g.g_stride = dc_stride; g.dW = dw2; g.part_floats = lfsr_branch_bwd_partial_floats(B, A, h, w);
+  int slabs[2] = {0, 0};
   for (int vert = 0; vert < 2; ++vert) {
     const float* E = vert ? ev : eh;
     float* dE = vert ? dEv : dEh;
     const int choff = vert ? choff_v : choff_h;
-    float* Pa = P[vert ? 2 : 0];   // EPIConv.2 partials
-    LFSR_RC(lfsr_wgrad_launch(vert ? LFSR_IN_CHK_V : LFSR_IN_CHK_H, LFSR_IN_SAME, dcat, dc_stride, choff, E, 32, 0, Pa, nepi, 32, 32, A, h, w, A, st));
+    g.gmode = vert ? LFSR_IN_CHK_V : LFSR_IN_CHK_H; g.g_choff = choff; g.X = E; g.part = P[vert ? 2 : 0];
+    LFSR_RC(lfsr_wgrad_partials(g, &slabs[vert], st));
     LfsrGemm q{};
     q.in_mode = vert ? LFSR_IN_CHK_V : LFSR_IN_CHK_H; q.out_mode = LFSR_OUT_SAME; q.cin = 32; q.X = dcat; q.x_stride = dc_stride; q.x_choff = choff;
     q.Wp = w2T_packed; q.Y = dE; q.y_stride = 32; q.Mk = E; q.mk_stride = 32; q.mk_slope = slope;
     q.M = nepi; q.N = 32; q.A = A; q.h = h; q.w = w; q.ntaps = A; q.CH = 32;
     LFSR_RC(lfsr_bwd_gemm(q, st));
   }
-  LFSR_RC(lfsr_wgrad_reduce(P[0], lfsr_wgrad_splits(nepi, A, 32), P[2], lfsr_wgrad_splits(nepi, A, 32), dw2, 32 * A, 32, A, 0, 32, 0, 0, 1, st));
-  return LFSR_OK;
+  g.part = P[0];
+  return lfsr_wgrad_sum(g, slabs[0], P[2], slabs[1], st);
 }
 
 int lfsr_epi_branch_bwd_p2d(const float* dEh, const float* dEv, const float* w0_packed, const float* w0T_packed, float* dx, int B, int A, int h, int w, hipStream_t st) {
@@ -112,24 +135,20 @@ int lfsr_epi_branch_bwd_p2d(const float* dEh, const float* dEv, const float* w0_
 }
 
 int lfsr_epi_branch_bwd_p2w(const float* dEh, const float* dEv, const float* xin, float* dw0, float* const P[4], int B, int A, int h, int w, hipStream_t st) {
-  const int AA = A * A, nepi = B * A * h * w;
-  const long long npix = (long long)B * AA * h * w;
   // the two passes share EPIConv.0's weights: where the EPI-line kernel applies, ONE weight-gradient launch covers both (one slab per block instead of
   // two sets); else the gather form per pass
-  const char* wsel = lfsr_sel("LFSR_WGRAD_EPI");
-  const bool epi_merged = lfsr_wgrad_epi0_blocks(B, A, h, w, 2) > 0 && A == 5 && h <= 32 && w <= 32 && npix * 64 * 4 < (1LL << 31) && !(wsel && wsel[0] == 'g');
-  int epi_slabs[2] = {0, 0};
-  if (epi_merged) {
-    LFSR_RC(lfsr_wgrad_epi0_launch(dEh, dEv, xin, 64, 0, P[1], B, A, h, w, 2, st));
-    epi_slabs[0] = lfsr_wgrad_epi0_blocks(B, A, h, w, 2);
-  } else {
-    for (int vert = 0; vert < 2; ++vert) {
-      LFSR_RC(lfsr_wgrad_launch(LFSR_IN_SAME, vert ? LFSR_IN_EPIV : LFSR_IN_EPIH, vert ? dEv : dEh, 32, 0, xin, 64, 0, P[vert ? 3 : 1], nepi, 32, 64, A, h, w, AA, st));
-      epi_slabs[vert] = lfsr_wgrad_splits(nepi, AA, 64);
-    }
+  LfsrWgrad g = epi0_wgrad(B, A, h, w);
+  g.G = dEh; g.G2 = dEv; g.X = xin; g.dW = dw0; g.part = P[1]; g.part_floats = lfsr_branch_bwd_partial_floats(B, A, h, w);
+  int slabs[2] = {0, 0};
+  int rc = lfsr_wgrad_partials(g, &slabs[0], st);
+  if (rc == LFSR_E_ARG) {
+    g.G2 = nullptr; g.xmode = LFSR_IN_EPIH;
+    LFSR_RC(lfsr_wgrad_partials(g, &slabs[0], st));
+    g.G = dEv; g.xmode = LFSR_IN_EPIV; g.part = P[3];
+    rc = lfsr_wgrad_partials(g, &slabs[1], st);
+    g.part = P[1];
   }
-  LFSR_RC(lfsr_wgrad_reduce(P[1], epi_slabs[0], epi_slabs[1] ? P[3] : nullptr, epi_slabs[1], dw0, 32, 64, AA, 0, 0, 0, 0, 0, st));
-  return LFSR_OK;
+  return rc ? rc : lfsr_wgrad_sum(g, slabs[0], slabs[1] ? P[3] : nullptr, slabs[1], st);
 }
 
 int lfsr_epi_branch_bwd(const float* dcat, int dc_stride, int choff_h, int choff_v, const float* xin, const float* eh, const float* ev,
@@ -142,15 +161,8 @@ int lfsr_epi_branch_bwd(const float* dcat, int dc_stride, int choff_h, int choff
 }
 
 size_t lfsr_branch_bwd_partial_floats(int B, int A, int h, int w) {
-  const int AA = A * A;
-  const int nlr = B * h * w, nepi = B * A * h * w;
   size_t m = 0;
-  auto up = [&](size_t v) { if (v > m) m = v; };
-  up((size_t)256 * AA * 32 * 64);   // EPI-line weight gradient: one slab per block
-  up(lfsr_wgrad_partial_floats(nlr, AA, 16, 64));
-  up(lfsr_wgrad_partial_floats(nlr, AA, 16, 16));
-  up(lfsr_wgrad_partial_floats(nepi, AA, 32, 64));
-  up(lfsr_wgrad_partial_floats(nepi, A, 32, 32));
+  for (const LfsrWgrad& g : {ang2_wgrad(B, A, h, w), ang0_wgrad(B, A, h, w), epi2_wgrad(B, A, h, w), epi0_wgrad(B, A, h, w)}) m = std::max(m, lfsr_wgrad_part_floats(g));
   return m;
 }
 

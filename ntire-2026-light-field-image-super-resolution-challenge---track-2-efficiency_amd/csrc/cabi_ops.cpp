@@ -36,9 +36,19 @@ int lfsr_conv3x3_dgrad(const float* dy, int dy_stride, int dy_choff, const float
                                n_img, h, w, lfsr_stream(stream));
 }
 
+namespace {
+LfsrWgrad conv3_wgrad(int n_img, int h, int w) {
+  LfsrWgrad g{};
+  g.form = LFSR_WG_CONV3; g.B = n_img; g.A = 1; g.h = h; g.w = w;
+  return g;
+}
+// stays the GATHER form at every shape: this operator never reaches the pw144 kernel (other bits, other speed)
+LfsrWgrad pointwise_wgrad(long long M, int cout, int cin) { return lfsr_wgrad_gather(LFSR_IN_SAME, LFSR_IN_SAME, M, cout, cin, 1, 1, 1, 1); }
+}  // namespace
+
 size_t lfsr_conv3x3_wgrad_workspace_floats(int n_img, int h, int w) {
   if (n_img <= 0 || h <= 0 || w <= 0) return 0;
-  return (size_t)lfsr_wgrad_conv3_blocks(n_img, h, w) * 9 * 64 * 64;
+  return lfsr_wgrad_part_floats(conv3_wgrad(n_img, h, w));
 }
 
 int lfsr_conv3x3_wgrad(const float* dy, int dy_stride, int dy_choff, const float* x, int x_stride, int x_choff, float* dw,
@@ -46,10 +56,10 @@ int lfsr_conv3x3_wgrad(const float* dy, int dy_stride, int dy_choff, const float
   if (!dy || !x || !dw || !workspace || n_img <= 0 || h <= 0 || w <= 0) return LFSR_E_ARG;
   if (dy_stride < dy_choff + 64 || x_stride < x_choff + 64) return LFSR_E_ARG;
   if (workspace_floats < lfsr_conv3x3_wgrad_workspace_floats(n_img, h, w)) return LFSR_E_WS;
-  hipStream_t st = lfsr_stream(stream);
-  int rc = lfsr_wgrad_conv3_launch(dy, dy_stride, dy_choff, x, x_stride, x_choff, workspace, n_img, h, w, st);
-  if (rc) return rc;
-  return lfsr_wgrad_reduce(workspace, lfsr_wgrad_conv3_blocks(n_img, h, w), nullptr, 0, dw, 64, 64, 9, 0, 0, accumulate, 0, 0, st);
+  LfsrWgrad g = conv3_wgrad(n_img, h, w);
+  g.G = dy; g.g_stride = dy_stride; g.g_choff = dy_choff; g.X = x; g.x_stride = x_stride; g.x_choff = x_choff;
+  g.dW = dw; g.accumulate = accumulate; g.part = workspace; g.part_floats = workspace_floats;
+  return lfsr_wgrad_run(g, lfsr_stream(stream));
 }
 
 // ---- pointwise (1x1) conv: y = act(x W^T), W (cout, cin) -----------------------------------------------------------------------
@@ -68,7 +78,7 @@ int lfsr_pointwise_dgrad(const float* dy, int dy_stride, int dy_choff, int cout,
 
 size_t lfsr_pointwise_wgrad_workspace_floats(long long M, int cout, int cin) {
   if (M <= 0 || M > 0x7fffffffLL || cout <= 0 || cin <= 0) return 0;
-  return lfsr_wgrad_partial_floats((int)M, 1, cout, cin);
+  return lfsr_wgrad_part_floats(pointwise_wgrad(M, cout, cin));
 }
 
 int lfsr_pointwise_wgrad(const float* dy, int dy_stride, int dy_choff, int cout, const float* x, int x_stride, int x_choff, int cin, float* dw,
@@ -76,10 +86,10 @@ int lfsr_pointwise_wgrad(const float* dy, int dy_stride, int dy_choff, int cout,
   if (!dy || !x || !dw || !workspace || M <= 0 || M > 0x7fffffffLL || cout <= 0 || cout > 64 || cin <= 0) return LFSR_E_ARG;
   if (dy_stride < dy_choff + cout || x_stride < x_choff + cin) return LFSR_E_ARG;
   if (workspace_floats < lfsr_pointwise_wgrad_workspace_floats(M, cout, cin)) return LFSR_E_WS;
-  hipStream_t st = lfsr_stream(stream);
-  int rc = lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_SAME, dy, dy_stride, dy_choff, x, x_stride, x_choff, workspace, (int)M, cout, cin, 1, 1, 1, 1, st);
-  if (rc) return rc;
-  return lfsr_wgrad_reduce(workspace, lfsr_wgrad_splits((int)M, 1, cin), nullptr, 0, dw, cout, cin, 1, 0, 0, accumulate, 0, 0, st);
+  LfsrWgrad g = pointwise_wgrad(M, cout, cin);
+  g.G = dy; g.g_stride = dy_stride; g.g_choff = dy_choff; g.X = x; g.x_stride = x_stride; g.x_choff = x_choff;
+  g.dW = dw; g.accumulate = accumulate; g.part = workspace; g.part_floats = workspace_floats;
+  return lfsr_wgrad_run(g, lfsr_stream(stream));
 }
 
 // ---- upsample head (DistgSSR.py:24-27,34-35): d(out)/d(f) through PixelShuffle(s), the folded s^2 x 64 matrix and MacPI2SAI ----

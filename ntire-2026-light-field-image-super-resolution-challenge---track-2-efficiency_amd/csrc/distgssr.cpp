@@ -1,6 +1,7 @@
 // Host driver for the DistgSSR forward (get_model.forward, model/SR/DistgSSR.py:29-36) on VCL buffers.
 // Pure host code above the C-ABI operator entry points: owns the packed-weight table keyed by the
 // reference's state_dict names and the launch sequence; allocates nothing on the device.
+#include <algorithm>
 #include <cstring>
 #include <map>
 #include <string>
@@ -352,21 +353,24 @@ struct TrainWs {
   size_t pfloats;
 };
 
+// the driver's own weight gradients, pointers apart: what lfsr_distgssr_backward submits and what max_partial_floats sizes
+LfsrWgrad conv3_wgrad(int B, int A, int h, int w) {
+  LfsrWgrad g{};
+  g.form = LFSR_WG_CONV3; g.x_stride = 64; g.B = B; g.A = A; g.h = h; g.w = w;
+  return g;
+}
+LfsrWgrad pw_wgrad(int form, int M, int N, int K, int h, int w) {      // 1x1 over all pixels: fuse.0 (PW144), the head fold (16, 64), init_conv on its 9 gathered taps (64, 16)
+  LfsrWgrad g = lfsr_wgrad_gather(LFSR_IN_SAME, LFSR_IN_SAME, M, N, K, 1, 1, h, w);
+  g.form = form;
+  return g;
+}
+
 size_t max_partial_floats(const lfsr_distgssr* c, int B, int h, int w) {
-  const int A = c->A, AA = A * A;
-  const int npix = B * AA * h * w, nlr = B * h * w, nepi = B * A * h * w;
-  size_t m = 0;
-  auto up = [&](size_t v) { if (v > m) m = v; };
-  up(lfsr_wgrad_partial_floats(npix, 9, 64, 64));
-  up((size_t)256 * 9 * 64 * 64);
-  up(lfsr_branch_bwd_partial_floats(B, A, h, w));   // (incl. the EPI-line weight gradient's one slab per block)
-  up(lfsr_wgrad_partial_floats(npix, 1, 64, 144));
-  up(lfsr_wgrad_partial_floats(nlr, AA, 16, 64));
-  up(lfsr_wgrad_partial_floats(nlr, AA, 16, 16));
-  up(lfsr_wgrad_partial_floats(nepi, AA, 32, 64));
-  up(lfsr_wgrad_partial_floats(nepi, A, 32, 32));
-  up(lfsr_wgrad_partial_floats(npix, 1, 16, 64));
-  up(lfsr_wgrad_partial_floats(npix, 1, 64, 16));
+  const int A = c->A, npix = B * A * A * h * w;
+  size_t m = lfsr_branch_bwd_partial_floats(B, A, h, w);
+  for (const LfsrWgrad& g : {conv3_wgrad(B, A, h, w), pw_wgrad(LFSR_WG_PW144, npix, 64, 144, h, w), pw_wgrad(LFSR_WG_GATHER, npix, 16, 64, h, w),
+                             pw_wgrad(LFSR_WG_GATHER, npix, 64, 16, h, w)})
+    m = std::max(m, lfsr_wgrad_part_floats(g));
   return m;
 }
 
@@ -513,11 +517,13 @@ static int distgssr_backward_impl(lfsr_distgssr* c, const float* x, const float*
     }
   }
   // weight gradient of a 3x3 conv: dW[tap][n][k] = sum_m g[m][n] * xin[conv3 src(m,tap)][k]
-  auto wgrad3 = [&](const std::string& key, const float* xin, const float* g, int g_stride) -> int {
-    int r = lfsr_wgrad_conv3_launch(g, g_stride, 0, xin, 64, 0, t.P[0], nimg, h, w, st);
-    if (!r) r = lfsr_wgrad_reduce(t.P[0], lfsr_wgrad_conv3_blocks(nimg, h, w), nullptr, 0, G(key), 64, 64, 9, 0, 0, 0, 0, 0, st);
-    return r;
+  // every weight gradient of the driver's own stream through P[0]: each is reduced before the next is launched, and the branches' use of P (both streams) is joined
+  // at the end of a block, before the next block's first weight gradient
+  auto wgrad = [&](LfsrWgrad g, const float* gr, int g_stride, const float* xin, float* dW) -> int {
+    g.G = gr; g.g_stride = g_stride; g.X = xin; g.dW = dW; g.part = t.P[0]; g.part_floats = t.pfloats;
+    return lfsr_wgrad_run(g, st);
   };
+  auto wgrad3 = [&](const std::string& key, const float* xin, const float* g, int g_stride) -> int { return wgrad(conv3_wgrad(B, A, h, w), g, g_stride, xin, G(key)); };
   auto dgrad3 = [&](const float* dy, int dy_stride, const std::string& key, float* dx, const float* r1, const float* mk, int mk_stride) -> int {
     return lfsr_conv3x3_bwd_data(dy, dy_stride, 0, c->wT(key), dx, 64, 0, r1, 64, 0, mk, mk_stride, 0, L, nimg, h, w, st);
   };
@@ -533,8 +539,7 @@ static int distgssr_backward_impl(lfsr_distgssr* c, const float* x, const float*
   {
     float* dWf = t.small;                 // (s*s, 64), rows >= s*s unused
     float* colp = t.small + 16 * 64;      // column-sum partials
-    LFSR_RC(lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_SAME, t.G16, 16, 0, t.D, 64, 0, t.P[0], npix, 16, 64, 1, h, w, 1, st));
-    LFSR_RC(lfsr_wgrad_reduce(t.P[0], lfsr_wgrad_splits(npix, 1, 64), nullptr, 0, dWf, 16, 64, 1, 0, 0, 0, 0, 0, st));
+    LFSR_RC(wgrad(pw_wgrad(LFSR_WG_GATHER, npix, 16, 64, h, w), t.G16, 16, t.D, dWf));
     int nblk = 0;
     LFSR_RC(lfsr_colsum(t.G16, npix, 16, colp, &nblk, st));
     if ((size_t)(16 * 64 + nblk * 16) > 64 * 1024) return LFSR_E_WS;
@@ -564,17 +569,7 @@ static int distgssr_backward_impl(lfsr_distgssr* c, const float* x, const float*
       LFSR_RC(wgrad3(p + "fuse.2.weight", t.FZ[i], gy, 64));
       LFSR_RC(dgrad3(gy, 64, p + "fuse.2.weight", t.dF, nullptr, t.FZ[i], 64));
       // fuse.0 : FZ = lrelu(1x1(CAT))
-      {   // streaming kernel (every row of dF and CAT read once, one slab per block); else the generic split-K kernel
-        float* Pw = t.PA;
-        int rc5 = lfsr_wgrad_pw144_launch(t.dF, 64, 0, t.CAT[i], 144, 0, Pw, npix, st);
-        int slabs = lfsr_wgrad_pw144_blocks(npix);
-        if (rc5 == LFSR_E_ARG) {
-          Pw = t.P[0];                    // generic split-K kernel: larger slabs
-          rc5 = lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_SAME, t.dF, 64, 0, t.CAT[i], 144, 0, Pw, npix, 64, 144, 1, h, w, 1, st); slabs = lfsr_wgrad_splits(npix, 1, 144);
-        }
-        LFSR_RC(rc5);
-        LFSR_RC(lfsr_wgrad_reduce(Pw, slabs, nullptr, 0, G(p + "fuse.0.weight"), 64, 144, 1, 0, 0, 0, 0, 0, st));
-      }
+      LFSR_RC(wgrad(pw_wgrad(LFSR_WG_PW144, npix, 64, 144, h, w), t.dF, 64, t.CAT[i], G(p + "fuse.0.weight")));
       {
         LfsrGemm q{};
         q.in_mode = LFSR_IN_SAME; q.out_mode = LFSR_OUT_SAME; q.cin = 64; q.X = t.dF; q.x_stride = 64; q.Wp = c->wT(p + "fuse.0.weight");
@@ -626,9 +621,9 @@ static int distgssr_backward_impl(lfsr_distgssr* c, const float* x, const float*
   // ---- init_conv: F0 = conv(x) ; dF0 = (through the groups) + dD (cascade skip) -------------------------------
   LFSR_RC(lfsr_add_inplace(gcur, dD, (long long)npix * 64, st));
   LFSR_RC(lfsr_init_gather9(x, t.XG9, B, A, h, w, st));
-  LFSR_RC(lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_SAME, gcur, 64, 0, t.XG9, 16, 0, t.P[0], npix, 64, 16, 1, h, w, 1, st));
-  LFSR_RC(lfsr_wgrad_reduce(t.P[0], lfsr_wgrad_splits(npix, 1, 16), nullptr, 0, G("init_conv.weight"), 64, 16, 1, 0, 0, 0, 9, 0, st));
-  return LFSR_OK;
+  LfsrWgrad gi = pw_wgrad(LFSR_WG_GATHER, npix, 64, 16, h, w);
+  gi.c_valid = 9;
+  return wgrad(gi, gcur, 64, t.XG9, G("init_conv.weight"));
 }
 
 }  // extern "C"

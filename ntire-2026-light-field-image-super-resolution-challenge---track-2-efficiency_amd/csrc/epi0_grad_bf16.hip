@@ -260,17 +260,18 @@ __global__ __launch_bounds__(512) void k_epi0_dgrad_bf16(EpiDgradB16Args p) {
 
 }  // namespace
 
-// The callers (lfsr_wgrad_epi0_launch, lfsr_epi0_dgrad_launch) have checked coverage (A = 5, line lengths, 32-bit byte spans, alignment) and the A/B selectors.
-int lfsr_wgrad_epi0_bf16_launch(const float* dE, const float* dE_v, const float* X, int x_stride, int x_choff, float* P, int B, int h, int w, int vert, int blocks,
-                                hipStream_t st) {
-  if (!dE || !X || !P || B <= 0 || h <= 0 || w <= 0 || blocks <= 0 || vert < 0 || vert > 2 || (vert == 2 && !dE_v)) return LFSR_E_ARG;
-  if ((vert != 0 && h > 32) || (vert != 1 && w > 32) || ((x_stride | x_choff) & 3) || x_stride < x_choff + 64) return LFSR_E_ARG;
-  if ((long long)B * EA * EA * h * w * x_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;
+// Both passes in one launch (G / G2), the geometry lfsr_wgrad_epi0_launch covers; lfsr_epi0_dgrad_launch has checked the data gradient's coverage and selector.
+int lfsr_wgrad_epi0_bf16_launch(const LfsrWgrad& g, hipStream_t st) {
+  const int B = g.B, h = g.h, w = g.w;
+  if (!g.G || !g.G2 || !g.X || !g.part || B <= 0 || h <= 0 || w <= 0 || g.A != EA || h > 32 || w > 32) return LFSR_E_ARG;
+  if (((g.x_stride | g.x_choff) & 3) || g.x_stride < g.x_choff + 64) return LFSR_E_ARG;
+  if ((long long)B * EA * EA * h * w * g.x_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;
+  LfsrOpTimer op_t("epi0_wgrad", B, h * w, st);
   WgradEpiB16Args p{};
-  p.G = dE; p.G2 = dE_v; p.X = X; p.x_stride = x_stride; p.x_choff = x_choff; p.P = P;
-  p.g_bytes = (int)((long long)B * EA * h * w * 32 * 4); p.x_bytes = (int)((long long)B * EA * EA * h * w * x_stride * 4);
-  p.B = B; p.H = h; p.W = w; p.vert = vert;
-  hipLaunchKernelGGL(k_wgrad_epi0_bf16, dim3((unsigned)blocks), dim3(512), WG_SMEM, st, p);
+  p.G = g.G; p.G2 = g.G2; p.X = g.X; p.x_stride = g.x_stride; p.x_choff = g.x_choff; p.P = g.part;
+  p.g_bytes = (int)((long long)B * EA * h * w * 32 * 4); p.x_bytes = (int)((long long)B * EA * EA * h * w * g.x_stride * 4);
+  p.B = B; p.H = h; p.W = w; p.vert = 2;
+  hipLaunchKernelGGL(k_wgrad_epi0_bf16, dim3((unsigned)lfsr_wgrad_epi0_blocks(B, EA, h, w)), dim3(512), WG_SMEM, st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }
@@ -280,7 +281,7 @@ int lfsr_epi0_dgrad_bf16_launch(const float* dE, const float* w_direct, float* d
   if ((long long)B * EA * EA * h * w * dx_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;
   static std::atomic<bool> attr_set[64];
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_HIP_ERR(hipErrorInvalidDevice);
   if (!attr_set[dev]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_epi0_dgrad_bf16), hipFuncAttributeMaxDynamicSharedMemorySize, DG_SMEM);
     if (e != hipSuccess) return LFSR_HIP_ERR(e);

@@ -57,7 +57,7 @@ void train_layout(const lfsr_epit* c, int B, int h, int w, LfsrArena& ws, EpitTr
   t.gtmp = ws.take(block_grad_floats(c));
   t.hid.clear();
   for (int j = 0; j < 2 * nb; ++j) t.hid.push_back(ws.take(npix * 256));
-  t.part = ws.take(lfsr_trans_wgrad_partial_max(B, c->A, h, w)); t.pln = ws.take((size_t)LFSR_RED_BLOCKS * 256); t.ptail = ws.take((size_t)LFSR_RED_BLOCKS * 9 * 64);
+  t.part_floats = lfsr_trans_wgrad_partial_max(B, c->A, h, w); t.part = ws.take(t.part_floats); t.pln = ws.take((size_t)LFSR_RED_BLOCKS * 256); t.ptail = ws.take((size_t)LFSR_RED_BLOCKS * 9 * 64);
   // the forward body's scratch (unfused LayerNorm outputs, two-launch feed-forward hidden rows, the unfused tail's HR map)
   f.tn = t.lnt; f.lnx = t.dln; f.hid = t.dh; f.hr = t.hr;
   t.up0T = ws.take((size_t)64 * 64 * s2);

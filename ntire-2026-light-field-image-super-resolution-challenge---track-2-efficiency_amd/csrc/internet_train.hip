@@ -12,9 +12,10 @@
 // (no float atomics: bitwise reproducible).  ReconBlock's folded conv is differentiated through the fold (k_fold_bwd).
 //
 // lfsr_set_wide_train_arithmetic (read at every launch) reaches the wide per-view 3x3 convs, the sixteen SpaConvSq (128 -> 64) and SpaBottle (320 -> 64), and nothing
-// else: in modes 1 and 2 their weight gradients run wgrad_wide_bf16.hip through lfsr_wide_wgrad_run, the launcher lfsr_conv3x3_wide_wgrad shares; in mode 2 the
+// else: in modes 1 and 2 their weight gradients run wgrad_wide_bf16.hip through the WIDE3 form of lfsr_wgrad_run, which lfsr_conv3x3_wide_wgrad shares; in mode 2 the
 // training forward computes ReLU(SpaConvSq) and ReLU(SpaBottle) with conv3x3_wide_bf16.hip (unless LFSR_ARITH_F32 is set) and keeps the separate residual add,
 // because the backward reads the ReLU results as masks.  lfsr_set_wide_arithmetic is not read here.
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -154,18 +155,25 @@ struct InterTrainWs {
   float *G16, *dBO, *dZ, *dCS, *dOs[2], *dSP, *dOa[2], *dzA, *dG2, *dCA, *dZa, *XG9, *XA, *P, *dWf;
 };
 
+// the backward's weight gradients, pointers apart: what lfsr_internet_backward submits and what partial_floats sizes
+LfsrWgrad wide_wgrad(int cin, int B, int A, int h, int w) {      // SpaConvSq (128) / SpaBottle (320): follows lfsr_set_wide_train_arithmetic
+  LfsrWgrad g{};
+  g.form = LFSR_WG_WIDE3; g.g_stride = 64; g.K = cin; g.B = B; g.A = A; g.h = h; g.w = w;
+  return g;
+}
+
 size_t partial_floats(int A, int B, int h, int w) {
   const int AA = A * A, npix = B * AA * h * w, nlr = B * h * w;
+  const int S = LFSR_IN_SAME;
   size_t m = 0;
-  auto up = [&](size_t v) { if (v > m) m = v; };
-  up(lfsr_wgrad_partial_floats(npix, 9, 16, 64));         // ReconBlock fold
-  up(lfsr_wide_wgrad_part_floats(64 * (NG + 1), B * AA, h, w));   // SpaBottle: the generic kernel's slabs or wgrad_wide_bf16.hip's, whichever are more, in every mode
-  up(lfsr_wgrad_partial_floats(nlr, AA, 64, 64));          // Ang2Spa / Spa2Ang
-  up(lfsr_wgrad_partial_floats(nlr, 1, 64, 64 * NG));      // AngBottle
-  up(lfsr_wgrad_partial_floats(nlr, 1, 64, 128));          // AngConvSq
-  up(lfsr_wide_wgrad_part_floats(128, B * AA, h, w));      // SpaConvSq: likewise
-  up(lfsr_wgrad_partial_floats(npix, 1, 64, 16));          // SpaFE
-  up(lfsr_wgrad_partial_floats(nlr, 1, 64, angfe_kpad(A)));   // AngFE
+  for (const LfsrWgrad& g : {lfsr_wgrad_gather(S, LFSR_IN_CONV3, npix, 16, 64, 9, A, h, w),      // ReconBlock fold
+                             wide_wgrad(64 * (NG + 1), B, A, h, w), wide_wgrad(128, B, A, h, w),   // SpaBottle, SpaConvSq
+                             lfsr_wgrad_gather(S, LFSR_IN_ANG, nlr, 64, 64, AA, A, h, w),         // Ang2Spa / Spa2Ang
+                             lfsr_wgrad_gather(S, S, nlr, 64, 64 * NG, 1, A, h, w),               // AngBottle
+                             lfsr_wgrad_gather(S, S, nlr, 64, 128, 1, A, h, w),                   // AngConvSq
+                             lfsr_wgrad_gather(S, S, npix, 64, 16, 1, A, h, w),                   // SpaFE
+                             lfsr_wgrad_gather(S, S, nlr, 64, angfe_kpad(A), 1, A, h, w)})        // AngFE
+    m = std::max(m, lfsr_wgrad_part_floats(g));
   return m;
 }
 
@@ -206,26 +214,6 @@ std::string chain_key(int g, int l, const char* leaf) {
 
 }  // namespace
 
-size_t lfsr_wide_wgrad_part_floats(int cin, int n_img, int h, int w) {
-  const int blocks = lfsr_wgrad_wide_bf16_blocks(cin, n_img, h, w);
-  if (blocks <= 0 || (long long)n_img * h * w >= (1LL << 31)) return 0;
-  const size_t generic = lfsr_wgrad_partial_floats(n_img * h * w, 9, 64, cin), tile = (size_t)blocks * 9 * 64 * cin;
-  return generic > tile ? generic : tile;
-}
-
-int lfsr_wide_wgrad_run(const float* dy, int dy_stride, int dy_choff, const float* x, int x_stride, int x_choff, int cin, float* dw, float* part,
-                        int n_img, int h, int w, int accumulate, int A, hipStream_t st) {
-  if (lfsr_wide_train_arith() != LFSR_WIDE_TRAIN_ARITH_DEFAULT) {
-    const int rc = lfsr_wgrad_wide_bf16_launch(dy, dy_stride, dy_choff, x, x_stride, x_choff, cin, part, n_img, h, w, st);
-    if (rc == LFSR_OK) return lfsr_wgrad_reduce(part, lfsr_wgrad_wide_bf16_blocks(cin, n_img, h, w), nullptr, 0, dw, 64, cin, 9, 0, 0, accumulate, 0, 0, st);
-    if (rc != LFSR_E_ARG) return rc;   // LFSR_E_ARG: not covered, nothing launched
-  }
-  const int M = n_img * h * w;
-  int r = lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_CONV3, dy, dy_stride, dy_choff, x, x_stride, x_choff, part, M, 64, cin, A, h, w, 9, st);
-  if (!r) r = lfsr_wgrad_reduce(part, lfsr_wgrad_splits(M, 9, cin), nullptr, 0, dw, 64, cin, 9, 0, 0, accumulate, 0, 0, st);
-  return r;
-}
-
 int lfsr_pack_T_from_fwd(const float* Wp, float* out, int T, int Npad_in, int C, int O, int k0, int Kc, int flip, hipStream_t st) {
   hipLaunchKernelGGL(k_pack_T_from_fwd, dim3(lfsr_cap_grid((long long)T * Kc * O)), dim3(256), 0, st, Wp, out, T, Npad_in, C, O, k0, Kc, flip);
   LFSR_CHECK_LAUNCH();
@@ -234,7 +222,7 @@ int lfsr_pack_T_from_fwd(const float* Wp, float* out, int T, int Npad_in, int C,
 
 extern "C" {
 
-size_t lfsr_conv3x3_wide_wgrad_workspace_floats(int cin, int n_img, int h, int w) { return lfsr_wide_wgrad_part_floats(cin, n_img, h, w); }
+size_t lfsr_conv3x3_wide_wgrad_workspace_floats(int cin, int n_img, int h, int w) { return lfsr_wgrad_part_floats(wide_wgrad(cin, n_img, 1, h, w)); }
 
 int lfsr_conv3x3_wide_wgrad(const float* dy, int dy_stride, int dy_choff, const float* x, int x_stride, int x_choff, int cin, float* dw, float* workspace,
                             size_t workspace_floats, int n_img, int h, int w, int accumulate, void* stream) {
@@ -244,10 +232,13 @@ int lfsr_conv3x3_wide_wgrad(const float* dy, int dy_stride, int dy_choff, const 
   if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dw | (uintptr_t)workspace) & 15) return LFSR_E_ARG;
   const long long rows = (long long)n_img * h * w, lim = (1LL << 31) / 4;   // an operand span of 2 GiB or more
   if (rows * x_stride >= lim || rows * dy_stride >= lim) return LFSR_E_ARG;
-  const size_t need = lfsr_wide_wgrad_part_floats(cin, n_img, h, w);
+  const size_t need = lfsr_conv3x3_wide_wgrad_workspace_floats(cin, n_img, h, w);
   if (!need) return LFSR_E_ARG;
   if (workspace_floats < need) return LFSR_E_WS;
-  return lfsr_wide_wgrad_run(dy, dy_stride, dy_choff, x, x_stride, x_choff, cin, dw, workspace, n_img, h, w, accumulate ? 1 : 0, 1, lfsr_stream(stream));
+  LfsrWgrad g = wide_wgrad(cin, n_img, 1, h, w);
+  g.G = dy; g.g_stride = dy_stride; g.g_choff = dy_choff; g.X = x; g.x_stride = x_stride; g.x_choff = x_choff;
+  g.dW = dw; g.accumulate = accumulate ? 1 : 0; g.part = workspace; g.part_floats = workspace_floats;
+  return lfsr_wgrad_run(g, lfsr_stream(stream));
 }
 
 size_t lfsr_internet_num_params(const lfsr_internet* c) { return c ? c->P.num_params() : 0; }
@@ -382,15 +373,20 @@ int lfsr_internet_backward(lfsr_internet* c, const float* x, const float* dout, 
     p.M = M; p.N = N; p.Npad = npad32(N); p.A = A; p.AA = AA; p.H = h; p.W = w; p.ntaps = ntaps; p.CH = CH; p.slope = 1.0f; p.S = c->s;
     return launcher(p, st);
   };
-  // weight gradient: partial slabs, then the fixed-order reduce into the bucket (raw PyTorch layout)
+  // weight gradient: partial slabs, then the fixed-order reduce into the bucket (raw PyTorch layout); (O, C, T) = 0: (N, K, ntaps)
+  const size_t pfloats = partial_floats(A, B, h, w);
   auto wgrad = [&](int gm, int xm, const float* Gr, int gs, int go, const float* X, int xs, int xo, int M, int N, int K, int ntaps, float* dW,
                    int O, int C, int T, int perm, int ch, int c_valid, int chunk) -> int {
-    int r = lfsr_wgrad_launch(gm, xm, Gr, gs, go, X, xs, xo, t.P, M, N, K, A, h, w, ntaps, st);
-    if (!r) r = lfsr_wgrad_reduce(t.P, lfsr_wgrad_splits(M, ntaps, K), nullptr, 0, dW, O, C, T, perm, ch, 0, c_valid, chunk, st);
-    return r;
+    LfsrWgrad g = lfsr_wgrad_gather(gm, xm, M, N, K, ntaps, A, h, w);
+    g.G = Gr; g.g_stride = gs; g.g_choff = go; g.X = X; g.x_stride = xs; g.x_choff = xo;
+    g.dW = dW; g.O = O; g.C = C; g.T = T; g.perm = perm; g.ch = ch; g.c_valid = c_valid; g.chunk_mode = chunk; g.part = t.P; g.part_floats = pfloats;
+    return lfsr_wgrad_run(g, st);
   };
-  // the wide convs' weight gradients follow lfsr_set_wide_train_arithmetic (lfsr_wide_wgrad_run: the default is the generic launch and reduce above)
-  auto wgrad_wide = [&](const float* X, int xs, int cin, float* dW) -> int { return lfsr_wide_wgrad_run(t.dZ, 64, 0, X, xs, 0, cin, dW, t.P, nimg, h, w, 0, A, st); };
+  auto wgrad_wide = [&](const float* X, int xs, int cin, float* dW) -> int {
+    LfsrWgrad g = wide_wgrad(cin, B, A, h, w);
+    g.G = t.dZ; g.X = X; g.x_stride = xs; g.dW = dW; g.part = t.P; g.part_floats = pfloats;
+    return lfsr_wgrad_run(g, st);
+  };
   auto dgrad3 = [&](const float* dy, const float* wT, float* dx, int dxs, int dxo, const float* r1) -> int {
     return lfsr_conv3x3_bwd_data(dy, 64, 0, wT, dx, dxs, dxo, r1, 64, 0, nullptr, 0, 0, 1.0f, nimg, h, w, st);
   };

@@ -317,59 +317,73 @@ int lfsr_tail_bwd_launch(const float* dout, const float* w3, const float* hr, fl
                          hipStream_t st);
 int lfsr_pack_up0_T_launch(const float* Wp, float* out, int s2, hipStream_t st);   // dgrad pack of upsampling.0 from its forward (perm 1) pack
 
-// wgrad.hip
-int lfsr_wgrad_splits(int M, int ntaps, int K);
-size_t lfsr_wgrad_partial_floats(int M, int ntaps, int N, int K);
-int lfsr_wgrad_launch(int gmode, int xmode, const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff,
-                      float* P, int M, int N, int K, int A, int h, int w, int ntaps, hipStream_t st);
-// halo-tile 3x3 conv weight gradient: partials P [lfsr_wgrad_conv3_blocks()][9][64][64], reduce with nsplit = that count
-int lfsr_wgrad_conv3_blocks(int n_img, int h, int w);
-int lfsr_wgrad_pw144_blocks(int M);
-int lfsr_wgrad_pw144_launch(const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff, float* P, int M, hipStream_t st);
-int lfsr_wgrad_epi0_blocks(int B, int A, int h, int w, int vert);
 int lfsr_ang0_dgrad_launch(const float* dA16, const float* w_direct, float* dx, int dx_stride, int dx_choff, int B, int A, int h, int w, hipStream_t st);
 int lfsr_epi0_dgrad_launch(const float* dE, const float* w_direct, float* dx, int dx_stride, int dx_choff, int B, int A, int h, int w, int vert, hipStream_t st);
-int lfsr_wgrad_epi0_launch(const float* dE, const float* dE_v, const float* X, int x_stride, int x_choff, float* P, int B, int A, int h, int w, int vert, hipStream_t st);
-// epi0_grad_bf16.hip: the two EPI-line kernels on bf16-rounded operands (LFSR_BRANCH_GRAD_ARITH_BF16), A = 5; the two launchers above call them after their own coverage
-// checks and selectors.  The weight gradient writes all `blocks` slabs [25][32][64].
-int lfsr_wgrad_epi0_bf16_launch(const float* dE, const float* dE_v, const float* X, int x_stride, int x_choff, float* P, int B, int h, int w, int vert, int blocks,
-                                hipStream_t st);
+// epi0_grad_bf16.hip: lfsr_epi0_dgrad_launch's kernel on bf16-rounded operands (LFSR_BRANCH_GRAD_ARITH_BF16), A = 5, behind that launcher's coverage checks and selector
 int lfsr_epi0_dgrad_bf16_launch(const float* dE, const float* w_direct, float* dx, int dx_stride, int dx_choff, int B, int h, int w, int vert, hipStream_t st);
-// wgrad_bf16.hip: the same contract on bf16-rounded operands (LFSR_GRAD_ARITH_BF16); writes all `blocks` slabs; LFSR_E_ARG = not covered, the fp32 kernel runs
-int lfsr_wgrad_conv3_bf16_launch(const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff, float* P,
-                                 int n_img, int h, int w, int blocks, hipStream_t st);
-int lfsr_wgrad_conv3_launch(const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff, float* P,
-                            int n_img, int h, int w, hipStream_t st);
-// lin_wgrad_bf16.hip: a linear's weight gradient on bf16-rounded operands (LFSR_LIN_GRAD_ARITH_BF16): `blocks` blocks along x, each writing
-// lfsr_lin_wgrad_bf16_slabs_per_block(cout, cin) slabs [cout][cin]; _blocks: one per row tile up to 256 blocks in all, and no more than cap_floats holds (0: not one)
-int lfsr_lin_wgrad_bf16_slabs_per_block(int cout, int cin);
-int lfsr_lin_wgrad_bf16_blocks(long long M, int cout, int cin, size_t cap_floats);
-int lfsr_lin_wgrad_bf16_launch(const float* G, int g_stride, const float* X, int x_stride, float* P, long long M, int cout, int cin, int blocks, hipStream_t st);
 // lin_dgrad_bf16.hip: lfsr_linear_dgrad's kernel on bf16-rounded operands behind the default's argument checks; LFSR_E_ARG = not covered, the default kernel runs
 int lfsr_lin_dgrad_bf16_launch(const float* dy, int cout, const float* wT_packed, float* dx, int dx_stride, const float* r1, int r1_stride, const float* act,
                                int act_stride, long long M, int cin, hipStream_t st);
-// trans_bwd.hip: the weight gradient of a (cout, cin) linear as lfsr_set_lin_grad_arithmetic selects it at this launch, what lfsr_linear_wgrad and
-// LfsrTransBwd::wgrad_lin both run.  Default: every 64-row slice through lfsr_wgrad_launch(IN_SAME, IN_SAME) + lfsr_wgrad_reduce.  part: part_floats floats,
-// at least lfsr_linear_wgrad_part_floats (LFSR_E_WS otherwise, nothing launched); the bf16 form sizes its grid to what part holds
-size_t lfsr_linear_wgrad_part_floats(long long M, int cout, int cin);   // what either mode needs at least; 0: shape not covered
-int lfsr_linear_wgrad_run(const float* dy, int dy_stride, const float* x, int x_stride, float* dw, float* part, size_t part_floats, long long M, int cout, int cin,
-                          int accumulate, int A, int h, int w, hipStream_t st);
-// wgrad_wide_bf16.hip: the weight gradient of LF_InterNet's wide per-view 3x3 convs (cin in {128, 320} -> 64) on bf16-rounded operands.  _blocks: the
-// pixel blocks of the launch, one per 4 x 32 tile up to 256 / ceil(cin / 128) (0: cin not covered); the launch writes that many slabs [9][64][cin], which
-// lfsr_wgrad_reduce sums with nsplit = _blocks.  LFSR_E_ARG = not covered (a span of 2 GiB or more), the generic kernel runs
-int lfsr_wgrad_wide_bf16_blocks(int cin, int n_img, int h, int w);
-int lfsr_wgrad_wide_bf16_launch(const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff, int cin, float* P,
-                                int n_img, int h, int w, hipStream_t st);
-// internet_train.hip: that weight gradient as lfsr_set_wide_train_arithmetic selects it at this launch, what lfsr_conv3x3_wide_wgrad and lfsr_internet_backward
-// both run.  Default, and whatever the bf16 kernel declines: lfsr_wgrad_launch(IN_SAME, IN_CONV3, N = 64, K = cin, 9 taps) + lfsr_wgrad_reduce.  part holds
-// at least lfsr_wide_wgrad_part_floats floats (the larger of the two forms' slabs: the same in every mode; 0: shape not covered)
-size_t lfsr_wide_wgrad_part_floats(int cin, int n_img, int h, int w);
-int lfsr_wide_wgrad_run(const float* dy, int dy_stride, int dy_choff, const float* x, int x_stride, int x_choff, int cin, float* dw, float* part,
-                        int n_img, int h, int w, int accumulate, int A, hipStream_t st);
-// c_valid < C: only the first c_valid input channels are written, with row length c_valid (init_conv's 9 taps)
-int lfsr_wgrad_reduce(const float* P, int nsplit, const float* P2, int nsplit2, float* dW, int O, int C, int T, int perm, int ch,
-                      int accumulate, int c_valid, int chunk_mode, hipStream_t st);
-// chunk_mode = 1: the T 'taps' of the partials are the chunks of a (1-D) pixel shuffle: row = perm ? n*T + t : t*ch + n (n < ch), dW (T*ch, C)
+// ---- the weight gradients: one operand struct, its launchers, one dispatcher (wgrad.cpp) ----
+// One weight gradient dW[t][n][k] = sum_m G[src_g(m, t)][n] X[src_x(m, t)][k] in two steps: a kernel writes partial slabs [ntaps][pad32(N)][K] into `part`, then
+// lfsr_wgrad_reduce sums them in a fixed order and scatters to the PyTorch layout.  form: the operator the caller means; the dispatcher derives what it fixes.
+//   GATHER   gmode / xmode (LFSR_IN_*), M rows, N <= 64 columns of G, K of X, ntaps; A, h, w: the gathers' geometry
+//   CONV3    the 64 -> 64 3x3 conv over B A A images of h x w                      PW144   fuse.0's shape, 64 x 144 over M rows
+//   EPI0     EPIConv.0 (32 x 64 x A A) over the EPI lines: G / G2 = the horizontal / vertical pass's gradient, both in one launch; G2 = null: the one pass xmode names
+//   LINEAR   a dense (N, K) linear over M rows, N in {64, 128, 256, 576, 1024}, K in {64, 128, 256}; part_floats also sizes the bf16 form's grid
+//   WIDE3    LF_InterNet's wide 3x3 conv, K in {128, 320} -> 64, over B A A images
+// Where the result lands: dW as (O, C, T) (0: N, K, ntaps), perm / ch / chunk_mode as lfsr_pack_conv_weight's inverse (chunk_mode = 1: the T 'taps' are the chunks of a
+// pixel shuffle: row = perm ? n T + t : t ch + n (n < ch), dW (T ch, C)); c_valid < C: only the first c_valid input channels, with row length c_valid (init_conv's 9 taps)
+enum { LFSR_WG_GATHER = 0, LFSR_WG_CONV3, LFSR_WG_PW144, LFSR_WG_EPI0, LFSR_WG_LINEAR, LFSR_WG_WIDE3 };
+#define LFSR_WGRAD_MAX_BLOCKS 256      // the persistent weight-gradient kernels run at most this many blocks, one slab each
+struct LfsrWgrad {
+  int form, gmode, xmode;
+  const float* G; int g_stride, g_choff;
+  const float* G2;
+  const float* X; int x_stride, x_choff;
+  long long M; int N, K, ntaps;
+  int B, A, h, w;
+  float* dW; int O, C, T, perm, ch, c_valid, chunk_mode, accumulate;
+  float* part; size_t part_floats;
+  int n_img() const { return B * A * A; }
+};
+// The launchers: each launches its own kernel only and fills all the slabs its count function names; LFSR_E_ARG = the call is not covered, nothing was launched.
+// They read the operand as the dispatcher has shaped it (M, N, K, ntaps filled for every form).
+int lfsr_wgrad_splits(int M, int ntaps, int K);
+size_t lfsr_wgrad_partial_floats(int M, int ntaps, int N, int K);
+int lfsr_wgrad_gather_launch(const LfsrWgrad& g, hipStream_t st);                    // wgrad.hip: the generic split-K gather kernel; lfsr_wgrad_splits slabs
+int lfsr_wgrad_conv3_blocks(int n_img, int h, int w, bool direct);                   // one slab [9][64][64] per block of ...
+int lfsr_wgrad_conv3_wino_launch(const LfsrWgrad& g, hipStream_t st);                // ... the Winograd form (2-row tiles), spans below 2 GiB
+int lfsr_wgrad_conv3_halo_launch(const LfsrWgrad& g, hipStream_t st);                // ... the direct form (direct = true: 4-row tiles)
+int lfsr_wgrad_conv3_bf16_launch(const LfsrWgrad& g, hipStream_t st);                // wgrad_bf16.hip: bf16-rounded operands, the Winograd form's block count
+int lfsr_wgrad_pw144_blocks(long long M);
+int lfsr_wgrad_pw144_launch(const LfsrWgrad& g, hipStream_t st);                     // wgrad.hip: streaming, one slab [64][144] per block
+int lfsr_wgrad_epi0_blocks(int B, int A, int h, int w);                              // one per line of both passes: one slab set for the shared weights
+int lfsr_wgrad_epi0_launch(const LfsrWgrad& g, hipStream_t st);                      // wgrad.hip: both passes' EPI lines (A = 5, lines of <= 32 pixels), one slab [25][32][64] per block
+int lfsr_wgrad_epi0_bf16_launch(const LfsrWgrad& g, hipStream_t st);                 // epi0_grad_bf16.hip: the same lines, slabs and block count on bf16-rounded operands
+// lin_wgrad_bf16.hip: `blocks` blocks along x, each writing _slabs_per_block slabs [N][K]; _blocks: one per row tile up to 256 blocks in all, and no more than
+// cap_floats holds (0: not one)
+int lfsr_lin_wgrad_bf16_slabs_per_block(int cout, int cin);                          // 0: shape not covered
+int lfsr_lin_wgrad_bf16_blocks(long long M, int cout, int cin, size_t cap_floats);
+int lfsr_lin_wgrad_bf16_launch(const LfsrWgrad& g, hipStream_t st);                  // the grid lfsr_lin_wgrad_bf16_blocks(.., g.part_floats) names
+int lfsr_wgrad_wide_bf16_blocks(int cin, int n_img, int h, int w);                   // one per 4 x 32 tile up to 256 / ceil(cin / 128) (0: cin not covered); slabs [9][64][cin]
+int lfsr_wgrad_wide_bf16_launch(const LfsrWgrad& g, hipStream_t st);                 // wgrad_wide_bf16.hip: spans below 2 GiB
+int lfsr_wgrad_reduce(const LfsrWgrad& g, int slabs, const float* part2, int slabs2, hipStream_t st);   // wgrad.hip: g.part's slabs, then part2's (same geometry; may be null)
+// wgrad.cpp: which kernel runs (the table stands there).  lfsr_wgrad_sel: LFSR_WGRAD3, LFSR_WGRAD_EPI, LFSR_WGRAD_PW with the four gradient arithmetics folded in, parsed
+// at every call, never cached; the only reader of their characters
+struct LfsrWgradSel { bool conv3_direct, conv3_bf16, epi_gather, epi_bf16, pw_gather, lin_bf16, wide_bf16; };
+LfsrWgradSel lfsr_wgrad_sel();
+int lfsr_wgrad_partials(const LfsrWgrad& g, int* slabs, hipStream_t st);             // one kernel of the form's chain; *slabs: how many slabs it wrote
+int lfsr_wgrad_sum(const LfsrWgrad& g, int slabs, const float* part2, int slabs2, hipStream_t st);   // the reduce of one or two slab sets (two passes that share weights)
+int lfsr_wgrad_run(const LfsrWgrad& g, hipStream_t st);                              // both; LFSR_E_WS: part_floats below lfsr_wgrad_part_floats
+// the most any kernel of the chain needs, in any mode; 0: not covered.  LINEAR: at least, and with full_grid what lets its bf16 form run its whole grid (an operator's workspace)
+size_t lfsr_wgrad_part_floats(const LfsrWgrad& g, bool full_grid = false);
+// the GATHER form on dense operands (g_stride = N, x_stride = K), pointers apart: what the sites fill in and the sizing loops submit as it is
+inline LfsrWgrad lfsr_wgrad_gather(int gmode, int xmode, long long M, int N, int K, int ntaps, int A, int h, int w) {
+  LfsrWgrad g{};
+  g.form = LFSR_WG_GATHER; g.gmode = gmode; g.xmode = xmode; g.g_stride = N; g.x_stride = K; g.M = M; g.N = N; g.K = K; g.ntaps = ntaps; g.A = A; g.h = h; g.w = w;
+  return g;
+}
 int lfsr_pack_weight_T(const float* w, float* out, int O, int C, int T, int flip, hipStream_t st);
 
 // branch_bwd.cpp: backward of the angular / epipolar branches (DistgSSR.py:84-97,108) on packed weights; C-ABI wrappers lfsr_angconv_bwd / lfsr_epiconv_hv_bwd
@@ -418,11 +432,12 @@ int lfsr_trans_tail(const LfsrTransSel& sel, const LfsrParamTable& P, const floa
 inline size_t lfsr_tr3_floats() { return lfsr_packed_weight_tr_floats(64, 64, 9); }   // the 64 -> 64 3x3 data gradient's pack
 // geometry the training paths cover: every activation below 2 GiB (the widest rows: the 256-float q | k, and the HR map of 64 s^2 floats per LR pixel)
 bool lfsr_trans_train_geometry_ok(int A, int s, int B, int h, int w);
-size_t lfsr_trans_wgrad_partial_max(int B, int A, int h, int w);   // the largest partial slab of the weight gradients over all B A^2 h w pixels, and at least one (1024, 64) slab of lin_wgrad_bf16.hip
+size_t lfsr_trans_wgrad_partial_max(int B, int A, int h, int w);   // the most lfsr_wgrad_part_floats asks for over the weight gradients the shared stages submit (at any scale)
 // the scratch of the shared stages (rows = VCL pixels): the tail's hr / du (64 s^2), ptail and up0T; the head's r4 / d64 / t64 (64), xg9 (16) and
 // initT; a sublayer's lnt / dln / dsm / dso / dv (128), dh / dqk (256); part / pln: the weight gradients' and the LayerNorm backward's partials
 struct LfsrTransBwdWs {
   float *hr, *du, *ptail, *up0T, *r4, *d64, *t64, *xg9, *initT[3], *lnt, *dh, *dln, *dsm, *dso, *dqk, *dv, *part, *pln;
+  size_t part_floats;   // what part holds
 };
 // One backward's context and the launches its driver and the stages below are written in.
 struct LfsrTransBwd {
@@ -438,9 +453,9 @@ struct LfsrTransBwd {
   // 1x1 data gradient Y (N columns) = X (dense rows of cin in {64, 128, 256, 576, 1024}) . WT, then * (Mk > 0 ? 1 : 0) (ReLU'), then + R1 (may alias Y);
   // follows lfsr_set_lin_grad_arithmetic
   int dgemm(const float* X, int cin, const float* WT, float* Y, int ys, const float* R1, int r1s, const float* Mk, int mks, int N) const;
-  // weight gradient of output rows [n0, n0 + N) (N <= 64) of a raw (O, C, T) weight: partial slabs, then the fixed-order reduce
+  // weight gradient of a raw (N <= 64, K, ntaps) weight from the columns [go, go + N) of Gr: the GATHER form (IN_SAME, xm) over M rows into ws.part
   int wgrad(int xm, const float* Gr, int gs, int go, const float* X, int xs, int M, int N, int K, int ntaps, float* dW, int accumulate, int c_valid = 0) const;
-  // a (O, K) linear weight's gradient: Gr (O columns, stride gs) against X (K columns), over all pixels (lfsr_linear_wgrad_run: follows lfsr_set_lin_grad_arithmetic)
+  // a (O, K) linear weight's gradient: Gr (O columns, stride gs) against X (K columns), over all pixels: the LINEAR form
   int wgrad_lin(const float* Gr, int gs, int O, const float* X, int xs, int K, float* dW) const;
   int ew(int C, const float* a, const float* b, const float* mk, float slope, float* d) const;   // lfsr_ew_launch on dense rows of C, over all pixels
   // LayerNorm backward with the gradients of its affine parameters written to G(gkey) / G(bkey); no position embedding: pe = nullptr, pe_rows = pe_div = 1

@@ -40,6 +40,14 @@ struct LftTrainWs : LfsrTransBwdWs {  // the base: the scratch of the stages EPI
 
 bool train_geometry_ok(const lfsr_lft* c, int B, int h, int w) { return c && lfsr_trans_train_geometry_ok(c->A, c->s, B, h, w); }
 
+// the position map's share of MLP.weight (one 64-column half): a 3x3 conv over the h w pixels of ONE view; the GATHER form like the other 3x3 weight gradients of
+// EPIT / LFT, not CONV3 -- the Winograd kernel would change bits and speed
+LfsrWgrad spe_wgrad(int h, int w) {
+  LfsrWgrad g = lfsr_wgrad_gather(LFSR_IN_SAME, LFSR_IN_CONV3, h * w, 64, 64, 9, 1, h, w);
+  g.g_stride = 128;
+  return g;
+}
+
 void train_layout(const lfsr_lft* c, int B, int h, int w, LfsrArena& ws, LftTrainWs& t) {
   const int nl = c->nlayer, s2 = c->s * c->s;
   const size_t npix = (size_t)B * c->A * c->A * h * w, HW = (size_t)h * w;
@@ -63,8 +71,9 @@ void train_layout(const lfsr_lft* c, int B, int h, int w, LfsrArena& ws, LftTrai
   t.stats = reinterpret_cast<float4*>(ws.take(npix * 8 * 4));
   t.hid_a.clear(); t.hid_s.clear();
   for (int b = 0; b < nl; ++b) { t.hid_a.push_back(ws.take(npix * 128)); t.hid_s.push_back(ws.take(npix * 256)); }
-  // part: the position map's share of MLP.weight runs over the h w pixels of one view
-  t.part = ws.take(std::max(lfsr_trans_wgrad_partial_max(B, c->A, h, w), lfsr_wgrad_partial_floats(h * w, 9, 64, 64)));
+  // part: the position map's share of MLP.weight runs over the h w pixels of one view; part_floats: what the shared stages use of it
+  t.part_floats = lfsr_trans_wgrad_partial_max(B, c->A, h, w);
+  t.part = ws.take(std::max(t.part_floats, lfsr_wgrad_part_floats(spe_wgrad(h, w))));
   t.pln = ws.take((size_t)LFSR_RED_BLOCKS * 256); t.ptail = ws.take((size_t)LFSR_RED_BLOCKS * 9 * 64);
   // the forward body's scratch (unfused LayerNorm outputs, two-launch feed-forward hidden rows, the unfused tail's HR map)
   f.n64 = t.t64; f.tn = t.lnt; f.lnf = t.dln2; f.ha = t.dh; f.hs = t.hid; f.hr = t.hr;
@@ -187,8 +196,9 @@ int lfsr_lft_backward(lfsr_lft* c, const float* x, const float* dout, int B, int
     float* dWm = k.G(sp + "MLP.weight");
     for (int half = 0; half < 2; ++half) {
       LFSR_RC(k.wgrad(LFSR_IN_CONV3, t.dst, 128, 64 * half, f.ay[b], 64, npix, 64, 64, 9, dWm + half * 64 * 576, 0));
-      LFSR_RC(lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_CONV3, t.dspe, 128, 64 * half, f.spos, 64, 0, t.part, HW, 64, 64, 1, h, w, 9, st));
-      LFSR_RC(lfsr_wgrad_reduce(t.part, lfsr_wgrad_splits(HW, 9, 64), nullptr, 0, dWm + half * 64 * 576, 64, 64, 9, 0, 0, 1, 0, 0, st));
+      LfsrWgrad g = spe_wgrad(h, w);
+      g.G = t.dspe; g.g_choff = 64 * half; g.X = f.spos; g.dW = dWm + half * 64 * 576; g.accumulate = 1; g.part = t.part; g.part_floats = lfsr_wgrad_part_floats(g);
+      LFSR_RC(lfsr_wgrad_run(g, st));
     }
     LFSR_RC(k.dgrad3(t.dst, 128, 0, t.mloT[b], t.d64, nullptr, nullptr));
     LFSR_RC(k.dgrad3(t.dst, 128, 64, t.mhiT[b], t.t64, t.d64, nullptr));   // t64 = dL/d ay

@@ -1,4 +1,4 @@
-// Weight gradient of a linear with bf16 OPERANDS: the kernel of lfsr_set_lin_grad_arithmetic(LFSR_LIN_GRAD_ARITH_BF16) behind lfsr_linear_wgrad_run (trans_bwd.hip).
+// Weight gradient of a linear with bf16 OPERANDS: the kernel of lfsr_set_lin_grad_arithmetic(LFSR_LIN_GRAD_ARITH_BF16) behind the LINEAR form of lfsr_wgrad_run (wgrad.cpp).
 //   dW[n][k] = sum over rows m of dY[m][n] * X[m][k]        n < cout in {64, 128, 256, 576, 1024}, k < cin in {64, 128, 256}
 // dY and X are rounded to bf16 (v_cvt_pk_bf16_f32: nearest even) on their way into LDS, the products are exact and run on v_mfma_f32_32x32x16_bf16 with the ROW index m
 // as the MFMA's K, accumulation and the partial slabs are fp32.  Gradients and activations stay fp32 in memory: the mode changes arithmetic, not storage.
@@ -220,14 +220,15 @@ int lfsr_lin_wgrad_bf16_blocks(long long M, int cout, int cin, size_t cap_floats
   return (int)(bx < fit ? bx : fit);
 }
 
-// the caller has checked the operands (pointers 16-B aligned, strides multiples of 4 and at least the row width, 0 < M < 2^31 - 128) and holds blocks x
-// lfsr_lin_wgrad_bf16_slabs_per_block slabs at P.  LFSR_E_ARG: shape not covered, nothing written
-int lfsr_lin_wgrad_bf16_launch(const float* G, int g_stride, const float* X, int x_stride, float* P, long long M, int cout, int cin, int blocks, hipStream_t st) {
-  const LwShape* s = lw_shape(cout, cin);
-  if (!s || !G || !X || !P || M <= 0 || blocks <= 0) return LFSR_E_ARG;
+// the caller has checked the operands (pointers 16-B aligned, strides multiples of 4 and at least the row width, 0 < M < 2^31 - 128); the grid is what g.part_floats
+// holds.  LFSR_E_ARG: shape not covered or not one block's slabs fit, nothing written
+int lfsr_lin_wgrad_bf16_launch(const LfsrWgrad& g, hipStream_t st) {
+  const LwShape* s = lw_shape(g.N, g.K);
+  const int blocks = lfsr_lin_wgrad_bf16_blocks(g.M, g.N, g.K, g.part_floats);
+  if (!s || !g.G || !g.X || !g.part || g.M <= 0 || blocks <= 0) return LFSR_E_ARG;
   LinWgradArgs p{};
-  p.G = G; p.g_stride = g_stride; p.X = X; p.x_stride = x_stride; p.P = P; p.M = M; p.cout = cout;
-  p.ntiles = (int)((M + lw_mt(s->ct, cin) - 1) / lw_mt(s->ct, cin));
+  p.G = g.G; p.g_stride = g.g_stride; p.X = g.X; p.x_stride = g.x_stride; p.P = g.part; p.M = g.M; p.cout = g.N;
+  p.ntiles = (int)((g.M + lw_mt(s->ct, g.K) - 1) / lw_mt(s->ct, g.K));
   s->launch(p, blocks, lw_ny(*s), st);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;

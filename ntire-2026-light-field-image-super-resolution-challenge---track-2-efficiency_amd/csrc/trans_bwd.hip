@@ -415,51 +415,28 @@ extern "C" int lfsr_linear_dgrad(const float* dy, int cout, const float* wT_pack
   return dgemm_launch(dy, cout, wT_packed, dx, dx_stride, r1, r1 ? r1_stride : 0, act, act ? act_stride : 0, (int)M, cin, 1, 1, 1, 1, lfsr_stream(stream));
 }
 
-// ---- a linear's weight gradient: one launcher for the operator and the drivers ------------------------------------------------------------
-static bool lin_wgrad_shape_ok(int cout, int cin) {
-  return (cout == 64 || cout == 128 || cout == 256 || cout == 576 || cout == 1024) && (cin == 64 || cin == 128 || cin == 256);
-}
-
-// the default's slabs of one 64-row slice (every slice reuses them)
-size_t lfsr_linear_wgrad_part_floats(long long M, int cout, int cin) {
-  if (!lin_wgrad_shape_ok(cout, cin) || M <= 0 || M > 0x7fffffffLL - 128) return 0;
-  const size_t slice = lfsr_wgrad_partial_floats((int)M, 1, 64, cin);
-  const size_t one = (size_t)lfsr_lin_wgrad_bf16_slabs_per_block(cout, cin) * cout * cin;      // the bf16 form's smallest grid
-  return std::max(slice, one);
-}
-
-int lfsr_linear_wgrad_run(const float* dy, int dy_stride, const float* x, int x_stride, float* dw, float* part, size_t part_floats, long long M, int cout, int cin,
-                          int accumulate, int A, int h, int w, hipStream_t st) {
-  const size_t need = lfsr_linear_wgrad_part_floats(M, cout, cin);
-  if (!need) return LFSR_E_ARG;
-  if (part_floats < need) return LFSR_E_WS;
-  if (lfsr_lin_grad_arith_bf16()) {
-    const int blocks = lfsr_lin_wgrad_bf16_blocks(M, cout, cin, part_floats);
-    LFSR_RC(lfsr_lin_wgrad_bf16_launch(dy, dy_stride, x, x_stride, part, M, cout, cin, blocks, st));
-    return lfsr_wgrad_reduce(part, blocks * lfsr_lin_wgrad_bf16_slabs_per_block(cout, cin), nullptr, 0, dw, cout, cin, 1, 0, 0, accumulate, 0, 0, st);
-  }
-  for (int n0 = 0; n0 < cout; n0 += 64) {
-    LFSR_RC(lfsr_wgrad_launch(LFSR_IN_SAME, LFSR_IN_SAME, dy, dy_stride, n0, x, x_stride, 0, part, (int)M, 64, cin, A, h, w, 1, st));
-    LFSR_RC(lfsr_wgrad_reduce(part, lfsr_wgrad_splits((int)M, 1, cin), nullptr, 0, dw + (size_t)n0 * cin, 64, cin, 1, 0, 0, accumulate, 0, 0, st));
-  }
-  return LFSR_OK;
+// ---- a linear's weight gradient: the LINEAR form, as the operator and the drivers submit it --------------------------------------------------
+static LfsrWgrad linear_wgrad(const float* dy, int dy_stride, const float* x, int x_stride, float* dw, long long M, int cout, int cin, int A, int h, int w) {
+  LfsrWgrad g{};
+  g.form = LFSR_WG_LINEAR; g.G = dy; g.g_stride = dy_stride; g.X = x; g.x_stride = x_stride; g.M = M; g.N = cout; g.K = cin; g.A = A; g.h = h; g.w = w; g.dW = dw;
+  return g;
 }
 
 // one size for both modes: the default's slabs, or the bf16 form's full grid where that is more
 extern "C" size_t lfsr_linear_wgrad_workspace_floats(long long M, int cout, int cin) {
-  const size_t need = lfsr_linear_wgrad_part_floats(M, cout, cin);
-  if (!need) return 0;
-  const size_t full = (size_t)lfsr_lin_wgrad_bf16_blocks(M, cout, cin, (size_t)-1) * lfsr_lin_wgrad_bf16_slabs_per_block(cout, cin) * cout * cin;
-  return std::max(need, full);
+  return lfsr_wgrad_part_floats(linear_wgrad(nullptr, 0, nullptr, 0, nullptr, M, cout, cin, 1, 1, 1), true);
 }
 
 extern "C" int lfsr_linear_wgrad(const float* dy, int dy_stride, const float* x, int x_stride, float* dw, float* workspace, size_t workspace_floats, long long M,
                                  int cout, int cin, int accumulate, void* stream) {
-  if (!dy || !x || !dw || !workspace || M <= 0 || M > 0x7fffffffLL - 128 || !lin_wgrad_shape_ok(cout, cin)) return LFSR_E_ARG;
+  const size_t need = lfsr_linear_wgrad_workspace_floats(M, cout, cin);      // 0: rows or shape not covered
+  if (!dy || !x || !dw || !workspace || !need) return LFSR_E_ARG;
   if (dy_stride < cout || x_stride < cin || ((dy_stride | x_stride) & 3)) return LFSR_E_ARG;
   if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)dw | (uintptr_t)workspace) & 15) return LFSR_E_ARG;
-  if (workspace_floats < lfsr_linear_wgrad_workspace_floats(M, cout, cin)) return LFSR_E_WS;
-  return lfsr_linear_wgrad_run(dy, dy_stride, x, x_stride, dw, workspace, workspace_floats, M, cout, cin, accumulate ? 1 : 0, 1, 1, 1, lfsr_stream(stream));
+  if (workspace_floats < need) return LFSR_E_WS;
+  LfsrWgrad g = linear_wgrad(dy, dy_stride, x, x_stride, dw, M, cout, cin, 1, 1, 1);
+  g.accumulate = accumulate ? 1 : 0; g.part = workspace; g.part_floats = workspace_floats;
+  return lfsr_wgrad_run(g, lfsr_stream(stream));
 }
 
 extern "C" size_t lfsr_up_tail_bwd_workspace_floats(void) { return (size_t)LFSR_RED_BLOCKS * 9 * 64; }
@@ -486,10 +463,14 @@ bool lfsr_trans_train_geometry_ok(int A, int s, int B, int h, int w) {
 }
 
 size_t lfsr_trans_wgrad_partial_max(int B, int A, int h, int w) {
-  const size_t npix = (size_t)B * A * A * h * w;
-  size_t m = lfsr_wgrad_partial_floats((int)npix, 9, 64, 64);
-  for (int K : {16, 64, 128, 256}) m = std::max(m, lfsr_wgrad_partial_floats((int)npix, 1, 64, K));
-  return std::max(m, (size_t)1024 * 64);      // lin_wgrad_bf16.hip's smallest grid at the widest linear (upsampling.0 at scale 4); more than the rest only up to 256 pixels
+  const long long npix = (long long)B * A * A * h * w;
+  // the 64 -> 64 3x3 convs as EPIT / LFT submit them: the GATHER form, not CONV3 -- the Winograd kernel would change bits and speed; conv_init0 on its 9 gathered taps
+  size_t m = std::max(lfsr_wgrad_part_floats(lfsr_wgrad_gather(LFSR_IN_SAME, LFSR_IN_CONV3, npix, 64, 64, 9, A, h, w)),
+                      lfsr_wgrad_part_floats(lfsr_wgrad_gather(LFSR_IN_SAME, LFSR_IN_SAME, npix, 64, 16, 1, A, h, w)));
+  auto lin = [&](int O, int K) { m = std::max(m, lfsr_wgrad_part_floats(linear_wgrad(nullptr, 0, nullptr, 0, nullptr, npix, O, K, A, h, w))); };
+  for (int E : {64, 128}) { lin(E, 2 * E); lin(2 * E, E); lin(E, E); }      // the sublayers' and the drivers' own linears
+  for (int s : {2, 3, 4}) lin(64 * s * s, 64);                               // upsampling.0
+  return m;
 }
 
 float* LfsrTransBwd::G(const std::string& k) const { return gbase + P.grad_off(k); }
@@ -500,12 +481,16 @@ int LfsrTransBwd::dgemm(const float* X, int cin, const float* WT, float* Y, int 
 
 int LfsrTransBwd::wgrad(int xm, const float* Gr, int gs, int go, const float* X, int xs, int M, int N, int K, int ntaps, float* dW, int accumulate,
                         int c_valid) const {
-  LFSR_RC(lfsr_wgrad_launch(LFSR_IN_SAME, xm, Gr, gs, go, X, xs, 0, ws.part, M, N, K, A, h, w, ntaps, st));
-  return lfsr_wgrad_reduce(ws.part, lfsr_wgrad_splits(M, ntaps, K), nullptr, 0, dW, N, K, ntaps, 0, 0, accumulate, c_valid, 0, st);
+  LfsrWgrad g = lfsr_wgrad_gather(LFSR_IN_SAME, xm, M, N, K, ntaps, A, h, w);
+  g.G = Gr; g.g_stride = gs; g.g_choff = go; g.X = X; g.x_stride = xs;
+  g.dW = dW; g.accumulate = accumulate; g.c_valid = c_valid; g.part = ws.part; g.part_floats = ws.part_floats;
+  return lfsr_wgrad_run(g, st);
 }
 
 int LfsrTransBwd::wgrad_lin(const float* Gr, int gs, int O, const float* X, int xs, int K, float* dW) const {
-  return lfsr_linear_wgrad_run(Gr, gs, X, xs, dW, ws.part, lfsr_trans_wgrad_partial_max(B, A, h, w), npix, O, K, 0, A, h, w, st);
+  LfsrWgrad g = linear_wgrad(Gr, gs, X, xs, dW, npix, O, K, A, h, w);
+  g.part = ws.part; g.part_floats = ws.part_floats;
+  return lfsr_wgrad_run(g, st);
 }
 
 int LfsrTransBwd::ew(int C, const float* a, const float* b, const float* mk, float slope, float* d) const {

@@ -646,18 +646,18 @@ size_t lfsr_wgrad_partial_floats(int M, int ntaps, int N, int K) {
   return (size_t)lfsr_wgrad_splits(M, ntaps, K) * ntaps * npad32(N) * K;
 }
 
-int lfsr_wgrad_launch(int gmode, int xmode, const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff,
-                      float* P, int M, int N, int K, int A, int h, int w, int ntaps, hipStream_t st) {
-  LfsrOpTimer op_t("wgrad_generic", gmode * 16 + xmode, N * 1000 + K, st);
-  if (!G || !X || !P || M <= 0 || N <= 0 || N > 64 || (N & 3) || K <= 0 || (K & 3) || ntaps <= 0) return LFSR_E_ARG;
-  if ((g_stride | g_choff | x_stride | x_choff) & 3) return LFSR_E_ARG;
+int lfsr_wgrad_gather_launch(const LfsrWgrad& g, hipStream_t st) {
+  LfsrOpTimer op_t("wgrad_generic", g.gmode * 16 + g.xmode, g.N * 1000 + g.K, st);
+  if (!g.G || !g.X || !g.part || g.M <= 0 || g.M > 0x7fffffffLL || g.N <= 0 || g.N > 64 || (g.N & 3) || g.K <= 0 || (g.K & 3) || g.ntaps <= 0) return LFSR_E_ARG;
+  if ((g.g_stride | g.g_choff | g.x_stride | g.x_choff) & 3) return LFSR_E_ARG;
+  const int M = (int)g.M;
   WgradArgs p{};
-  p.G = G; p.g_stride = g_stride; p.g_choff = g_choff; p.X = X; p.x_stride = x_stride; p.x_choff = x_choff; p.P = P;
-  p.M = M; p.N = N; p.Npad = npad32(N); p.K = K; p.A = A; p.AA = A * A; p.H = h; p.W = w; p.ntaps = ntaps;
-  p.nsplit = lfsr_wgrad_splits(M, ntaps, K);
+  p.G = g.G; p.g_stride = g.g_stride; p.g_choff = g.g_choff; p.X = g.X; p.x_stride = g.x_stride; p.x_choff = g.x_choff; p.P = g.part;
+  p.M = M; p.N = g.N; p.Npad = npad32(g.N); p.K = g.K; p.A = g.A; p.AA = g.A * g.A; p.H = g.h; p.W = g.w; p.ntaps = g.ntaps;
+  p.nsplit = lfsr_wgrad_splits(M, g.ntaps, g.K);
   long long rows = ((long long)M + p.nsplit - 1) / p.nsplit;
   p.rows_per_split = (int)((rows + WG_ROWS - 1) / WG_ROWS * WG_ROWS);
-#define WG(GM, XM) if (gmode == GM && xmode == XM) return launch_wgrad<GM, XM>(p, st);
+#define WG(GM, XM) if (g.gmode == GM && g.xmode == XM) return launch_wgrad<GM, XM>(p, st);
   WG(IN_SAME, IN_CONV3)   // conv3x3
   WG(IN_SAME, IN_SAME)    // 1x1
   WG(IN_SAME, IN_ANG)     // AngConv.0
@@ -670,64 +670,68 @@ int lfsr_wgrad_launch(int gmode, int xmode, const float* G, int g_stride, int g_
   return LFSR_E_ARG;
 }
 
-
-// LFSR_WGRAD3=direct keeps the direct-form kernel (A/B runs); the Winograd form is the default
-static bool wgrad3_wino() { const char* s = lfsr_sel("LFSR_WGRAD3"); return !(s && s[0] == 'd'); }
-
-int lfsr_wgrad_conv3_blocks(int n_img, int h, int w) {
-  const int tr = wgrad3_wino() ? 2 : WT_R;
-  long long tiles = (long long)n_img * ((h + tr - 1) / tr) * ((w + WT_C - 1) / WT_C);
-  return (int)(tiles < 256 ? tiles : 256);
-}
-
-int lfsr_wgrad_conv3_launch(const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff, float* P,
-                            int n_img, int h, int w, hipStream_t st) {
-  LfsrOpTimer op_t("conv3x3_wgrad", n_img, h * w, st);
-  if (!G || !X || !P || n_img <= 0 || h <= 0 || w <= 0 || ((g_stride | g_choff | x_stride | x_choff) & 3)) return LFSR_E_ARG;
-  if ((long long)n_img * h * w * (x_stride > g_stride ? x_stride : g_stride) * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
-  static std::atomic<bool> attr_set[64];
+namespace {
+// the >64 KB dynamic-LDS opt-in is a per-device function attribute: set once per device and kernel
+int lds_opt_in(std::atomic<bool>* attr_set, const void* kernel, int smem) {
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
-  const int smem = (WX_PIX + WG_PIX) * LDS_ROW * 4;
-  constexpr int smem_w = 2 * W2BUF * 4;
-  static_assert(smem_w >= 8 * 8 * 64 * 4 * 4, "the epilogue's exchange fits the staging buffers");
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_HIP_ERR(hipErrorInvalidDevice);
   if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_conv3_halo), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_conv3_wino), hipFuncAttributeMaxDynamicSharedMemorySize, smem_w);
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     if (e != hipSuccess) return LFSR_HIP_ERR(e);
     attr_set[dev] = true;
   }
-  // lfsr_set_grad_arithmetic(LFSR_GRAD_ARITH_BF16) with nothing selected: bf16 operands, the same slabs; what that kernel does not cover runs below in fp32
-  if (lfsr_grad_arith_bf16() && !lfsr_sel("LFSR_WGRAD3")) {
-    const int rc = lfsr_wgrad_conv3_bf16_launch(G, g_stride, g_choff, X, x_stride, x_choff, P, n_img, h, w, lfsr_wgrad_conv3_blocks(n_img, h, w), st);
-    if (rc != LFSR_E_ARG) return rc;
-  }
-  if (wgrad3_wino()) {
-    Wgrad3Args q{};
-    q.G = G; q.g_stride = g_stride; q.g_choff = g_choff; q.X = X; q.x_stride = x_stride; q.x_choff = x_choff; q.P = P;
-    q.g_bytes = (int)((long long)n_img * h * w * g_stride * 4); q.x_bytes = (int)((long long)n_img * h * w * x_stride * 4);
-    q.n_img = n_img; q.H = h; q.W = w; q.tiles_y = (h + 1) / 2; q.tiles_x = (w + WT_C - 1) / WT_C;
-    hipLaunchKernelGGL(k_wgrad_conv3_wino, dim3((unsigned)lfsr_wgrad_conv3_blocks(n_img, h, w)), dim3(512), smem_w, st, q);
-    LFSR_CHECK_LAUNCH();
-    return LFSR_OK;
-  }
+  return LFSR_OK;
+}
+
+// what both 3x3 forms check and fill; tile_rows: 2 (Winograd) or WT_R
+int conv3_args(const LfsrWgrad& g, int tile_rows, Wgrad3Args& p) {
+  const int n_img = g.n_img(), h = g.h, w = g.w;
+  if (!g.G || !g.X || !g.part || n_img <= 0 || h <= 0 || w <= 0 || ((g.g_stride | g.g_choff | g.x_stride | g.x_choff) & 3)) return LFSR_E_ARG;
+  if ((long long)n_img * h * w * (g.x_stride > g.g_stride ? g.x_stride : g.g_stride) * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
+  p.G = g.G; p.g_stride = g.g_stride; p.g_choff = g.g_choff; p.X = g.X; p.x_stride = g.x_stride; p.x_choff = g.x_choff; p.P = g.part;
+  p.g_bytes = (int)((long long)n_img * h * w * g.g_stride * 4); p.x_bytes = (int)((long long)n_img * h * w * g.x_stride * 4);
+  p.n_img = n_img; p.H = h; p.W = w; p.tiles_y = (h + tile_rows - 1) / tile_rows; p.tiles_x = (w + WT_C - 1) / WT_C;
+  return LFSR_OK;
+}
+}  // namespace
+
+int lfsr_wgrad_conv3_blocks(int n_img, int h, int w, bool direct) {
+  const int tr = direct ? WT_R : 2;
+  long long tiles = (long long)n_img * ((h + tr - 1) / tr) * ((w + WT_C - 1) / WT_C);
+  return (int)(tiles < LFSR_WGRAD_MAX_BLOCKS ? tiles : LFSR_WGRAD_MAX_BLOCKS);
+}
+
+int lfsr_wgrad_conv3_wino_launch(const LfsrWgrad& g, hipStream_t st) {
   Wgrad3Args p{};
-  p.G = G; p.g_stride = g_stride; p.g_choff = g_choff; p.X = X; p.x_stride = x_stride; p.x_choff = x_choff; p.P = P;
-  p.g_bytes = (int)((long long)n_img * h * w * g_stride * 4); p.x_bytes = (int)((long long)n_img * h * w * x_stride * 4);
-  p.n_img = n_img; p.H = h; p.W = w; p.tiles_y = (h + WT_R - 1) / WT_R; p.tiles_x = (w + WT_C - 1) / WT_C;
-  hipLaunchKernelGGL(k_wgrad_conv3_halo, dim3((unsigned)lfsr_wgrad_conv3_blocks(n_img, h, w)), dim3(512), smem, st, p);
+  LFSR_RC(conv3_args(g, 2, p));
+  constexpr int smem_w = 2 * W2BUF * 4;
+  static_assert(smem_w >= 8 * 8 * 64 * 4 * 4, "the epilogue's exchange fits the staging buffers");
+  static std::atomic<bool> attr_set[64];
+  LFSR_RC(lds_opt_in(attr_set, reinterpret_cast<const void*>(k_wgrad_conv3_wino), smem_w));
+  hipLaunchKernelGGL(k_wgrad_conv3_wino, dim3((unsigned)lfsr_wgrad_conv3_blocks(p.n_img, p.H, p.W, false)), dim3(512), smem_w, st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }
 
-int lfsr_wgrad_reduce(const float* P, int nsplit, const float* P2, int nsplit2, float* dW, int O, int C, int T, int perm, int ch,
-                      int accumulate, int c_valid, int chunk_mode, hipStream_t st) {
-  LfsrOpTimer op_t("wgrad_reduce", O, C * T, st);
-  if (c_valid <= 0 || c_valid > C) c_valid = C;
-  if (!P || !dW || O <= 0 || C <= 0 || T <= 0) return LFSR_E_ARG;
-  const int Npad = chunk_mode ? npad32(ch) : npad32(O);
-  long long total = (long long)T * Npad * C;
-  hipLaunchKernelGGL(k_wgrad_reduce, dim3(lfsr_blocks(total, 64)), dim3(64, 8), 0, st, P, nsplit, P2, P2 ? nsplit2 : 0, dW, O, C, T, Npad, perm, ch, accumulate, c_valid, chunk_mode);
+int lfsr_wgrad_conv3_halo_launch(const LfsrWgrad& g, hipStream_t st) {
+  Wgrad3Args p{};
+  LFSR_RC(conv3_args(g, WT_R, p));
+  const int smem = (WX_PIX + WG_PIX) * LDS_ROW * 4;
+  static std::atomic<bool> attr_set[64];
+  LFSR_RC(lds_opt_in(attr_set, reinterpret_cast<const void*>(k_wgrad_conv3_halo), smem));
+  hipLaunchKernelGGL(k_wgrad_conv3_halo, dim3((unsigned)lfsr_wgrad_conv3_blocks(p.n_img, p.H, p.W, true)), dim3(512), smem, st, p);
+  LFSR_CHECK_LAUNCH();
+  return LFSR_OK;
+}
+
+int lfsr_wgrad_reduce(const LfsrWgrad& g, int slabs, const float* part2, int slabs2, hipStream_t st) {
+  LfsrOpTimer op_t("wgrad_reduce", g.O, g.C * g.T, st);
+  const int c_valid = g.c_valid <= 0 || g.c_valid > g.C ? g.C : g.c_valid;
+  if (!g.part || !g.dW || g.O <= 0 || g.C <= 0 || g.T <= 0) return LFSR_E_ARG;
+  const int Npad = g.chunk_mode ? npad32(g.ch) : npad32(g.O);
+  long long total = (long long)g.T * Npad * g.C;
+  hipLaunchKernelGGL(k_wgrad_reduce, dim3(lfsr_blocks(total, 64)), dim3(64, 8), 0, st, g.part, slabs, part2, part2 ? slabs2 : 0, g.dW, g.O, g.C, g.T, Npad, g.perm, g.ch,
+                     g.accumulate, c_valid, g.chunk_mode);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }
@@ -750,64 +754,48 @@ int lfsr_pack_weight_T_m(const float* w, float* out, int O, int C, int T, int fl
 }
 
 
-// EPIConv.0 weight gradient in EPI-line form (A = 5, lines of <= 32 pixels); LFSR_E_ARG = not covered (the caller keeps the gather form).
-// LFSR_WGRAD_EPI=gather forces the gather form (A/B runs).
-// vert: 0 horizontal pass (dE), 1 vertical pass (dE), 2 both in one launch (dE = horizontal, dE_v = vertical): one slab set for the shared weights
-int lfsr_wgrad_epi0_blocks(int B, int A, int h, int w, int vert) {
-  const long long nl = (long long)B * A * (vert == 2 ? h + w : vert ? w : h);
-  return (int)(nl < 256 ? nl : 256);
+// EPIConv.0 weight gradient in EPI-line form, both passes in one launch (G = horizontal, G2 = vertical): one slab set for the shared weights
+int lfsr_wgrad_epi0_blocks(int B, int A, int h, int w) {
+  const long long nl = (long long)B * A * (h + w);   // the lines of both passes
+  return (int)(nl < LFSR_WGRAD_MAX_BLOCKS ? nl : LFSR_WGRAD_MAX_BLOCKS);
 }
 
-int lfsr_wgrad_epi0_launch(const float* dE, const float* dE_v, const float* X, int x_stride, int x_choff, float* P, int B, int A, int h, int w, int vert, hipStream_t st) {
-  LfsrOpTimer op_t("epi0_wgrad", B, h * w, st);
-  if (!dE || !X || !P || B <= 0 || h <= 0 || w <= 0 || ((x_stride | x_choff) & 3) || vert < 0 || vert > 2 || (vert == 2 && !dE_v)) return LFSR_E_ARG;
-  const char* sel = lfsr_sel("LFSR_WGRAD_EPI");
-  if (A != 5 || (vert != 0 && h > 32) || (vert != 1 && w > 32) || (sel && sel[0] == 'g')) return LFSR_E_ARG;
-  if ((long long)B * A * A * h * w * x_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;
-  if (lfsr_branch_grad_arith_bf16())   // the same lines, slabs and block count on bf16 operands (epi0_grad_bf16.hip)
-    return lfsr_wgrad_epi0_bf16_launch(dE, dE_v, X, x_stride, x_choff, P, B, h, w, vert, lfsr_wgrad_epi0_blocks(B, A, h, w, vert), st);
-  static std::atomic<bool> attr_set[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
+int lfsr_wgrad_epi0_launch(const LfsrWgrad& g, hipStream_t st) {
+  const int B = g.B, A = g.A, h = g.h, w = g.w;
+  if (!g.G || !g.G2 || !g.X || !g.part || B <= 0 || h <= 0 || w <= 0 || ((g.x_stride | g.x_choff) & 3)) return LFSR_E_ARG;
+  if (A != 5 || h > 32 || w > 32) return LFSR_E_ARG;
+  if ((long long)B * A * A * h * w * g.x_stride * 4 >= (1LL << 31)) return LFSR_E_ARG;
+  LfsrOpTimer op_t("epi0_wgrad", B, h * w, st);      // (behind the coverage test: a declined call leaves no record)
   constexpr int smem = 2 * (5 * WE_PX * WE_SI + 32 * WE_SE) * 4;
-  if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_epi0_lines<5>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) return LFSR_HIP_ERR(e);
-    attr_set[dev] = true;
-  }
+  static std::atomic<bool> attr_set[64];
+  LFSR_RC(lds_opt_in(attr_set, reinterpret_cast<const void*>(k_wgrad_epi0_lines<5>), smem));
   WgradEpiArgs p{};
-  p.G = dE; p.G2 = dE_v; p.X = X; p.x_stride = x_stride; p.x_choff = x_choff; p.P = P;
-  p.g_bytes = (int)((long long)B * A * h * w * 32 * 4); p.x_bytes = (int)((long long)B * A * A * h * w * x_stride * 4);
-  p.B = B; p.A = A; p.H = h; p.W = w; p.vert = vert;
-  hipLaunchKernelGGL(k_wgrad_epi0_lines<5>, dim3((unsigned)lfsr_wgrad_epi0_blocks(B, A, h, w, vert)), dim3(512), smem, st, p);
+  p.G = g.G; p.G2 = g.G2; p.X = g.X; p.x_stride = g.x_stride; p.x_choff = g.x_choff; p.P = g.part;
+  p.g_bytes = (int)((long long)B * A * h * w * 32 * 4); p.x_bytes = (int)((long long)B * A * A * h * w * g.x_stride * 4);
+  p.B = B; p.A = A; p.H = h; p.W = w; p.vert = 2;
+  hipLaunchKernelGGL(k_wgrad_epi0_lines<5>, dim3((unsigned)lfsr_wgrad_epi0_blocks(B, A, h, w)), dim3(512), smem, st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }
 
 
-// fuse.0-shaped 1x1 weight gradient (N = 64, K = 144): one slab per block; LFSR_E_ARG = not covered.  LFSR_WGRAD_PW=gather keeps the generic kernel.
-int lfsr_wgrad_pw144_blocks(int M) {
-  const int nchunks = (M + PW_ROWS - 1) / PW_ROWS;
-  return nchunks < 256 ? nchunks : 256;
+// fuse.0-shaped 1x1 weight gradient (N = 64, K = 144): one slab per block
+int lfsr_wgrad_pw144_blocks(long long M) {
+  const long long nchunks = (M + PW_ROWS - 1) / PW_ROWS;
+  return (int)(nchunks < LFSR_WGRAD_MAX_BLOCKS ? nchunks : LFSR_WGRAD_MAX_BLOCKS);
 }
 
-int lfsr_wgrad_pw144_launch(const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff, float* P, int M, hipStream_t st) {
-  LfsrOpTimer op_t("pw144_wgrad", M, 0, st);
-  if (!G || !X || !P || M <= 0 || ((g_stride | g_choff | x_stride | x_choff) & 3) || g_stride < g_choff + 64 || x_stride < x_choff + 144) return LFSR_E_ARG;
-  const char* sel = lfsr_sel("LFSR_WGRAD_PW");
-  if (sel && sel[0] == 'g') return LFSR_E_ARG;
-  static std::atomic<bool> attr_set[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
+int lfsr_wgrad_pw144_launch(const LfsrWgrad& g, hipStream_t st) {
+  LfsrOpTimer op_t("pw144_wgrad", (int)g.M, 0, st);
+  if (!g.G || !g.X || !g.part || g.M <= 0 || g.M > 0x7fffffffLL || ((g.g_stride | g.g_choff | g.x_stride | g.x_choff) & 3) || g.g_stride < g.g_choff + 64 ||
+      g.x_stride < g.x_choff + 144)
+    return LFSR_E_ARG;
   constexpr int smem = 2 * PW_ROWS * (PW_GS + PW_XS) * 4;
-  if (!attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_pw144), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (e != hipSuccess) return LFSR_HIP_ERR(e);
-    attr_set[dev] = true;
-  }
+  static std::atomic<bool> attr_set[64];
+  LFSR_RC(lds_opt_in(attr_set, reinterpret_cast<const void*>(k_wgrad_pw144), smem));
   WgradPwArgs p{};
-  p.G = G; p.g_stride = g_stride; p.g_choff = g_choff; p.X = X; p.x_stride = x_stride; p.x_choff = x_choff; p.P = P; p.M = M;
-  hipLaunchKernelGGL(k_wgrad_pw144, dim3((unsigned)lfsr_wgrad_pw144_blocks(M)), dim3(512), smem, st, p);
+  p.G = g.G; p.g_stride = g.g_stride; p.g_choff = g.g_choff; p.X = g.X; p.x_stride = g.x_stride; p.x_choff = g.x_choff; p.P = g.part; p.M = (int)g.M;
+  hipLaunchKernelGGL(k_wgrad_pw144, dim3((unsigned)lfsr_wgrad_pw144_blocks(g.M)), dim3(512), smem, st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }

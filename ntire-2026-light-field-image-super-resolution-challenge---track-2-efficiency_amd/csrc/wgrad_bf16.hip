@@ -1,4 +1,4 @@
-// Weight gradient of the per-view 3x3 conv 64 -> 64 with bf16 OPERANDS: the kernel of lfsr_set_grad_arithmetic(LFSR_GRAD_ARITH_BF16) behind lfsr_wgrad_conv3_launch.
+// Weight gradient of the per-view 3x3 conv 64 -> 64 with bf16 OPERANDS: the kernel of lfsr_set_grad_arithmetic(LFSR_GRAD_ARITH_BF16) behind the CONV3 form of lfsr_wgrad_run (wgrad.cpp).
 //   dW[tap][n][k] = sum over pixels p of dY[p][n] * X[p + shift(tap)][k]   (zero outside the view)
 // dY and X are rounded to bf16 (v_cvt_pk_bf16_f32: nearest even) on their way into LDS, the products are exact and run on v_mfma_f32_32x32x16_bf16 with the PIXEL index
 // as the MFMA's K, accumulation and the partial slabs are fp32.  Gradients and activations stay fp32 in memory: the mode changes arithmetic, not storage.
@@ -182,17 +182,17 @@ __global__ __launch_bounds__(512) void k_wgrad_conv3_bf16(WgradB16Args p) {
 
 }  // namespace
 
-int lfsr_wgrad_conv3_bf16_launch(const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff, float* P,
-                                 int n_img, int h, int w, int blocks, hipStream_t st) {
-  if (!G || !X || !P || n_img <= 0 || h <= 0 || w <= 0 || blocks <= 0 || ((g_stride | g_choff | x_stride | x_choff) & 3)) return LFSR_E_ARG;
-  if (g_stride < g_choff + 64 || x_stride < x_choff + 64) return LFSR_E_ARG;
-  if ((long long)n_img * h * w * (x_stride > g_stride ? x_stride : g_stride) * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
+int lfsr_wgrad_conv3_bf16_launch(const LfsrWgrad& g, hipStream_t st) {
+  const int n_img = g.n_img(), h = g.h, w = g.w;
+  if (!g.G || !g.X || !g.part || n_img <= 0 || h <= 0 || w <= 0 || ((g.g_stride | g.g_choff | g.x_stride | g.x_choff) & 3)) return LFSR_E_ARG;
+  if (g.g_stride < g.g_choff + 64 || g.x_stride < g.x_choff + 64) return LFSR_E_ARG;
+  if ((long long)n_img * h * w * (g.x_stride > g.g_stride ? g.x_stride : g.g_stride) * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
   WgradB16Args p{};
-  p.G = G; p.g_stride = g_stride; p.g_choff = g_choff; p.X = X; p.x_stride = x_stride; p.x_choff = x_choff; p.P = P;
-  p.g_bytes = (int)((long long)n_img * h * w * g_stride * 4); p.x_bytes = (int)((long long)n_img * h * w * x_stride * 4);
+  p.G = g.G; p.g_stride = g.g_stride; p.g_choff = g.g_choff; p.X = g.X; p.x_stride = g.x_stride; p.x_choff = g.x_choff; p.P = g.part;
+  p.g_bytes = (int)((long long)n_img * h * w * g.g_stride * 4); p.x_bytes = (int)((long long)n_img * h * w * g.x_stride * 4);
   p.n_img = n_img; p.H = h; p.W = w; p.tiles_y = (h + TR - 1) / TR; p.tiles_x = (w + TC - 1) / TC;
   p.ntiles = n_img * p.tiles_y * p.tiles_x;
-  hipLaunchKernelGGL(k_wgrad_conv3_bf16, dim3((unsigned)blocks), dim3(512), SMEM_BYTES, st, p);
+  hipLaunchKernelGGL(k_wgrad_conv3_bf16, dim3((unsigned)lfsr_wgrad_conv3_blocks(n_img, h, w, false)), dim3(512), SMEM_BYTES, st, p);
   LFSR_CHECK_LAUNCH();
   return LFSR_OK;
 }

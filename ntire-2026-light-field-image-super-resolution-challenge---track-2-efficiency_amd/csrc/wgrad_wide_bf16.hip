@@ -1,5 +1,5 @@
 // Weight gradient of LF_InterNet's wide per-view 3x3 convs (SpaConvSq 128 -> 64, BottleNeck.SpaBottle 320 -> 64) with bf16 OPERANDS: the kernel of
-// lfsr_set_wide_train_arithmetic(LFSR_WIDE_TRAIN_ARITH_BF16_WGRAD | LFSR_WIDE_TRAIN_ARITH_BF16) behind lfsr_wide_wgrad_run (internet_train.hip).
+// lfsr_set_wide_train_arithmetic(LFSR_WIDE_TRAIN_ARITH_BF16_WGRAD | LFSR_WIDE_TRAIN_ARITH_BF16) behind the WIDE3 form of lfsr_wgrad_run (wgrad.cpp).
 //   dW[tap][n][k] = sum over pixels p of dY[p][n] * X[p + shift(tap)][k]   (zero outside the view),  n < 64, k < cin
 // dY and X are rounded to bf16 (v_cvt_pk_bf16_f32: nearest even) on their way into LDS, the products are exact and run on v_mfma_f32_32x32x16_bf16 with the PIXEL index
 // as the MFMA's K, accumulation and the partial slabs are fp32.  Gradients and activations stay fp32 in memory: the mode changes arithmetic, not storage.
@@ -213,23 +213,23 @@ int lfsr_wgrad_wide_bf16_blocks(int cin, int n_img, int h, int w) {
   return (int)(tiles < cap ? tiles : cap);
 }
 
-int lfsr_wgrad_wide_bf16_launch(const float* G, int g_stride, int g_choff, const float* X, int x_stride, int x_choff, int cin, float* P,
-                                int n_img, int h, int w, hipStream_t st) {
+int lfsr_wgrad_wide_bf16_launch(const LfsrWgrad& g, hipStream_t st) {
+  const int cin = g.K, n_img = g.n_img(), h = g.h, w = g.w;
   const int blocks = lfsr_wgrad_wide_bf16_blocks(cin, n_img, h, w);
-  if (!G || !X || !P || blocks <= 0 || g_choff < 0 || x_choff < 0 || ((g_stride | g_choff | x_stride | x_choff) & 3)) return LFSR_E_ARG;
-  if (g_stride < g_choff + 64 || x_stride < x_choff + cin) return LFSR_E_ARG;
-  if ((long long)n_img * h * w * (x_stride > g_stride ? x_stride : g_stride) * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
+  if (!g.G || !g.X || !g.part || blocks <= 0 || g.g_choff < 0 || g.x_choff < 0 || ((g.g_stride | g.g_choff | g.x_stride | g.x_choff) & 3)) return LFSR_E_ARG;
+  if (g.g_stride < g.g_choff + 64 || g.x_stride < g.x_choff + cin) return LFSR_E_ARG;
+  if ((long long)n_img * h * w * (g.x_stride > g.g_stride ? g.x_stride : g.g_stride) * 4 >= (1LL << 31)) return LFSR_E_ARG;   // 32-bit byte offsets
   static std::atomic<bool> attr_set[64];   // per device: the >64 KB dynamic-LDS opt-in is a per-device function attribute
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_E_ARG;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return LFSR_HIP_ERR(hipErrorInvalidDevice);
   if (!attr_set[dev]) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_wgrad_wide_bf16), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM_BYTES);
     if (e != hipSuccess) return LFSR_HIP_ERR(e);
     attr_set[dev] = true;
   }
   WgradWideArgs p{};
-  p.G = G; p.g_stride = g_stride; p.g_choff = g_choff; p.X = X; p.x_stride = x_stride; p.x_choff = x_choff; p.P = P;
-  p.g_bytes = (int)((long long)n_img * h * w * g_stride * 4); p.x_bytes = (int)((long long)n_img * h * w * x_stride * 4);
+  p.G = g.G; p.g_stride = g.g_stride; p.g_choff = g.g_choff; p.X = g.X; p.x_stride = g.x_stride; p.x_choff = g.x_choff; p.P = g.part;
+  p.g_bytes = (int)((long long)n_img * h * w * g.g_stride * 4); p.x_bytes = (int)((long long)n_img * h * w * g.x_stride * 4);
   p.cin = cin; p.n_img = n_img; p.H = h; p.W = w; p.tiles_y = (h + TR - 1) / TR; p.tiles_x = (w + TC - 1) / TC;
   p.ntiles = n_img * p.tiles_y * p.tiles_x;
   hipLaunchKernelGGL(k_wgrad_wide_bf16, dim3((unsigned)blocks, (unsigned)chunk_pairs(cin)), dim3(512), SMEM_BYTES, st, p);

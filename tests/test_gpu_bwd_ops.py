@@ -396,7 +396,7 @@ def test_pointwise_dgrad_wgrad_every_form(M, cout, cin, masked, monkeypatch):
             assert torch.equal(got[""], got["f32"]) and torch.equal(got[""], got["gather"])           # gather-GEMM, the same bits
     _select(monkeypatch)
     xb = _embed(x, cin + 4, 4)
-    # (LFSR_WGRAD_PW is read by the model driver's k_wgrad_pw144 launch alone, not behind this entry point:
+    # (LFSR_WGRAD_PW moves the PW144 form of the weight-gradient dispatcher alone, which only the model driver submits, not this entry point:
     # tests/test_gpu_distgssr_geometries.py::test_fuse0_weight_gradient_streaming_and_generic_form)
     n_ws = lib.lfsr_pointwise_wgrad_workspace_floats(M, cout, cin)
     ws = torch.full((n_ws + BAND,), SENTINEL, device="cuda")

@@ -73,9 +73,9 @@ def reach(model, geom, train):
     # ANG_ARITH_BF16: lfsr_angconv3x3_fwd alone (ang3x3.hip:121), LFSSR's operator: none of the four
     if train:
         # GRAD_ARITH_BF16: the 3x3 data gradient (conv3x3.cpp:53) of all four backwards (trans_bwd.hip:541, internet_train.hip:394-395, DistgSSR's conv backward) and
-        # the 64 -> 64 weight gradient (wgrad.hip:701)
+        # the 64 -> 64 weight gradient (the CONV3 chain of wgrad.cpp)
         out.add("grad")
-        # LIN_GRAD_ARITH_BF16: dgemm_launch and lfsr_linear_wgrad_run of the shared transformer backward (trans_bwd.hip:400, 456): EPIT and LFT
+        # LIN_GRAD_ARITH_BF16: dgemm_launch (trans_bwd.hip) and the LINEAR form of lfsr_wgrad_run (wgrad.cpp) of the shared transformer backward: EPIT and LFT
         if transformer:
             out.add("lin_grad")
         # BRANCH_GRAD_ARITH_BF16: EPIConv.0's EPI-line gradients at A = 5: the data gradient per pass with lines of at most 32 pixels (bwd_ops.hip:272-274,

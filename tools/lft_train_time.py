@@ -43,6 +43,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--hip-only", action="store_true", help="without the stock-torch yardstick: a short process, for alternating two builds (LFSR_HIP_LIB)")
     a = ap.parse_args()
     A, h, w, s, B, iters = 5, 32, 32, 4, a.batch, a.iters
     net = M.get_model(Namespace(angRes_in=A, angRes_out=A, scale_factor=s)).cuda()
@@ -83,20 +84,21 @@ def main():
     del opt, net
     torch.cuda.empty_cache()
 
-    # the stock-torch yardstick: autograd over the port's graph, fp32, same inputs and weights (PE and mask built on the device)
-    with torch.device("cuda"):
-        params = {k: torch.tensor(v, requires_grad=True) for k, v in sd.items()}
+    if not a.hip_only:
+        # the stock-torch yardstick: autograd over the port's graph, fp32, same inputs and weights (PE and mask built on the device)
+        with torch.device("cuda"):
+            params = {k: torch.tensor(v, requires_grad=True) for k, v in sd.items()}
 
-        def torch_step():
-            for p in params.values():
-                p.grad = None
-            out = lft_forward.__wrapped__(x, params, A, s)
-            torch.nn.functional.l1_loss(out, label).backward()
+            def torch_step():
+                for p in params.values():
+                    p.grad = None
+                out = lft_forward.__wrapped__(x, params, A, s)
+                torch.nn.functional.l1_loss(out, label).backward()
 
-        torch_step()
-        torch.cuda.synchronize()
-        r["torch_fwd_bwd_ms"] = timed(torch_step, max(3, iters // 2))
-    r["speedup_vs_torch"] = r["torch_fwd_bwd_ms"] / r["fwd_bwd_ms"]
+            torch_step()
+            torch.cuda.synchronize()
+            r["torch_fwd_bwd_ms"] = timed(torch_step, max(3, iters // 2))
+        r["speedup_vs_torch"] = r["torch_fwd_bwd_ms"] / r["fwd_bwd_ms"]
     res = {"tool": "lft_train_time", "config": f"LFT 5x5 32x32 x{s} B={B} fp32", "device": torch.cuda.get_device_name(0)}
     res.update({k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()})
     print(json.dumps(res))
